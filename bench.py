@@ -236,6 +236,32 @@ def free_port():
     return p
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loss, tr):
+    """--dump-outputs: what the last timed step handed back -- its loss, the global gradient norm the optimizer clipped with, and the
+    fp32 trainable parameters it updated (the flat master buffer, in the trainer's parameter order) -- as out_dir/<name>.npy.  Past
+    DUMP_MAX_BYTES the parameters are a fixed, seeded sample: trainable_params_index.npy holds the sampled positions."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    flat = tr.flat
+    params = flat.flat_p[:flat.total].cpu()
+    arrays = {"loss": np.asarray(loss.float().cpu().numpy(), dtype=np.float32).reshape(1),
+              "grad_norm": np.asarray(tr.optim.norm.cpu().numpy(), dtype=np.float32).reshape(1)}
+    if params.numel() * 4 + 4096 <= DUMP_MAX_BYTES:
+        arrays["trainable_params"] = params.numpy()
+    else:
+        k = (DUMP_MAX_BYTES - 4096) // 12            # float32 value + float64 index per sampled position
+        idx = torch.randperm(params.numel(), generator=torch.Generator().manual_seed(0))[:k].sort().values
+        arrays["trainable_params"] = params[idx].numpy()
+        arrays["trainable_params_index"] = idx.numpy().astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    print(f"[bench] dumped {', '.join(f'{n} {a.shape}' for n, a in arrays.items())} to {out_dir}", file=sys.stderr, flush=True)
+
+
 def build_model(args, dev, dtype):
     import vlpet_amd.host.bart as HB
     import vlpet_amd.train as TR
@@ -297,7 +323,7 @@ def main():
                     help="(default) build and apply the reference's default attention mask input_ids.ne(pad) every step "
                          "(src/modeling_bart.py:817-818), although the synthetic rows have no pad tokens")
     ap.add_argument("--no-pad-mask", dest="pad_mask", action="store_false",
-                    help="tell the host that the rows carry no padding, so it builds no mask (A/B: about +3 %)")
+                    help="tell the host that the rows carry no padding, so it builds no mask (A/B: about +3 %%)")
     ap.add_argument("--k1-previous-split", action="store_true",
                     help="A/B: the round-2 form of the gated K1 backward (row kernel + streaming weight gradients) instead of pass 1 + column-parallel pass")
     ap.add_argument("--overlap-wgrad", action="store_true",
@@ -320,7 +346,13 @@ def main():
                          "overlap kept under replay) instead of after the replay.  Tested with a one-rank RCCL communicator only.")
     ap.add_argument("--model", default="bart", choices=["bart", "t5", "lora", "video"])
     ap.add_argument("--lora-r", type=int, default=64, help="LoRA rank for --model lora (BASELINE configs[3]: 8 / 64; script: 128)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0: its loss, the global gradient norm, the "
+                         "updated fp32 trainable parameters) as DIR/<name>.npy, at most 64 MB; the settling rounds then always run their "
+                         "maximum count, so that runs with the same arguments compute the same steps")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("bench.py: --steps must be at least 1")
     if args.scaling is None:
         args.scaling = "strong" if args.gpus > 1 else "weak"
     if args.emulate_ranks > 1 and args.gpus != 1:
@@ -441,6 +473,8 @@ def main():
     settling = [timed_round()]
     while len(settling) < 4:
         settling.append(timed_round())
+        if args.dump_outputs:       # a fixed number of steps before the timed region: the dumped outputs must not depend on timing
+            continue
         settled = all(settling[-2][t_] <= 1.15 * settling[-1][t_] for t_ in tasks)
         if world > 1:       # every rank must run the same number of rounds (each step is a collective): one more unless ALL have settled
             flag = torch.tensor([0.0 if settled else 1.0], device=dev)
@@ -464,7 +498,7 @@ def main():
     for i in range(args.warmup, args.warmup + args.steps):
         b = batches[order[i]]
         step_ev[i - args.warmup].record()
-        tr.step(b)
+        loss = tr.step(b)
         samples += b["input_ids"].shape[0]
     step_ev[args.steps].record()
     torch.cuda.synchronize()
@@ -474,6 +508,8 @@ def main():
     dt = time.perf_counter() - t0
     step_ms = [round(step_ev[k].elapsed_time(step_ev[k + 1]), 3) for k in range(args.steps)]
     peak_gb = round(torch.cuda.max_memory_allocated(dev) / 1e9, 3)     # peak of torch's allocator up to the end of the timed region (all task shapes seen)
+    if args.dump_outputs and rank == 0:      # before the eager region / kernel-table steps below update the parameters again
+        dump_outputs(args.dump_outputs, loss, tr)
     timer, VF.TIMER = VF.TIMER, None
     eager_region = None
     if graph_on:
