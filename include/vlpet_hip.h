@@ -7,7 +7,8 @@
  *
  * Conventions
  *   - every pointer is a DEVICE pointer owned by the caller (PyTorch caching allocator in the
- *     shipped host code); the library allocates nothing and keeps no state between calls;
+ *     shipped host code); the library allocates nothing and keeps no state between calls except
+ *     the dropout seed counter of vlpet_set_seed_counter;
  *   - activations are row-major [M, d], contiguous, 16-byte aligned; d % 64 == 0;
  *   - io_dtype: VLPET_BF16 (performance mode) or VLPET_F32 (parity mode: bf16 hi/lo split
  *     products, fp32 accumulate); gradients of parameters are always fp32;
@@ -124,19 +125,17 @@ int vlpet_adapter_gate_bwd_phase(int phases, const void* dy, const void* x1, con
  * (bf16, r, r_g <= 96, d % 128 == 0), 1 = pass 1 + the older column-parallel pass (csrc/pet_gate_bwd3.hip: r = 192, fp32 small M),
  * 0 = row kernel + weight-gradient kernels; < 0: bad arguments.  (What a bench labels its kernel brackets with.) */
 int vlpet_adapter_gate_bwd_form(int64_t M, int d, int tiles, int io_dtype);
-/* 1: that form ends in a separate finalize launch at this shape (`phases` bit 4 runs it alone); 0: it does not -- since round 6 the
- * column-parallel pass at r, r_g <= 96 and M >= 8,192 rows sums its row-chunk partials INSIDE the launch (csrc/cols_reduce.h: the workgroups of a column
- * block each take a slice once all of them have published; bounded waits, the last arriver finishes what an owner gave up, results
- * bit-identical to the two-launch form).  `phases` bit 5 (32) of the *_bwd_saved* entry points keeps the round-3 two-launch form for
- * same-box A/Bs.  The reduce-scatter's control words are zeroed by pass 1, so `phases` = 2 alone presumes that pass 1 of the same
- * backward ran on the same workspace before (as the bench's per-kernel brackets do). */
+/* For a call WITHOUT `phases` bit 5 -- 1: that form ends in a separate finalize launch at this shape (`phases` bit 4 runs it alone);
+ * 0: it does not -- since round 6 the column-parallel pass at r, r_g <= 96 and M >= 8,192 rows (below that the finalize launch
+ * measured ahead) sums its row-chunk partials INSIDE the launch (csrc/cols_reduce.h: the workgroups of a column block each take a
+ * slice once all of them have published; bounded waits, the last arriver finishes what an owner gave up, results bit-identical to the
+ * two-launch form).  A call with `phases` bit 5 (32) of the *_bwd_saved* entry points always takes the round-3 two-launch form:
+ * set it where other kernels run BESIDE the backward (gradient collectives on their own stream overlapping it, a second process on
+ * the device) -- a workgroup waiting for partners that cannot start keeps its CU for as long as the foreign kernel lasts (bounded:
+ * ~3 ms, then it gives up and the last arriver sums its slice -- results unchanged, time lost), where the two-launch form runs in two
+ * rounds.  The reduce-scatter's control words are zeroed by pass 1, so `phases` = 2 alone presumes that pass 1 of the same backward
+ * ran on the same workspace before (as the bench's per-kernel brackets do). */
 int vlpet_adapter_gate_bwd_finalize_launch(int64_t M, int d, int tiles, int io_dtype);
-/* Process-wide: 0 = pass 2 of the gated K1 backward always leaves its partial slabs to a finalize launch; 1 (default) = at r <= 96 and
- * from 8,192 rows it sums them inside the launch (below that the finalize launch measured ahead).  Turn it off where other kernels run BESIDE the backward (gradient
- * collectives on their own stream overlapping it, a second process on the device): a workgroup waiting for partners that cannot
- * start keeps its CU for as long as the foreign kernel lasts (bounded: ~3 ms, then it gives up and the last arriver sums its slice --
- * results unchanged, time lost), where the two-launch form runs in two rounds.  Returns the previous setting. */
-int vlpet_set_in_launch_reduce(int on);
 
 /* Dropout seeds under graph replay (train.Trainer(graph=True): forward + backward of a step captured once with hipGraph and replayed).
  * A replayed launch repeats its kernel arguments, so the per-call `seed` values of the dropout-carrying entry points below
@@ -166,7 +165,8 @@ int vlpet_test_hold_cus(int workgroups, int lds_bytes, void* release_flag, int m
  * needs dx1 / dx2 right after bit 0 (weight gradients on another stream) adds bit 2 to BOTH calls: the previous split
  * (bit 0: dx1, dx2 + [M, d] side products; bit 1: weight gradients from them).  phases = 3 is the full call either way.
  * For event brackets around single kernels (form 2 only): bit 3 with bit 1 = pass 2 WITHOUT the finalize launch (the row-chunk
- * partial sums stay in the workspace), bit 4 alone = the finalize launch only. */
+ * partial sums stay in the workspace), bit 4 alone = the finalize launch only.  Bit 5: no in-launch reduce of pass 2 (see
+ * vlpet_adapter_gate_bwd_finalize_launch). */
 int vlpet_adapter_gate_bwd_saved(int phases, const void* dy, const void* x1, const void* x2, const void* saved,
                                  const void* packed_a, const void* packed_g,
                                  void* dx1, void* dx2,
@@ -426,23 +426,6 @@ int vlpet_sublayer_tail_bwd_out(const void* dout, const void* out_save, const fl
  * straight at the parameters' slots of its flat gradient buffer. */
 int vlpet_sublayer_tail_reduce(const float* dgb_partials, int n_partials, int d, float* dgamma, float* dbeta,
                                vlpet_stream_t stream);
-/* ---- deferred finalize of the weight gradients ------------------------------------------------
- * Every backward entry point above that produces weight gradients ends with a "finalize" launch: the sum of its row-chunk partial
- * blocks (in the call's workspace) into dW / db.  A training step holds one per adapter call and nobody reads a weight gradient
- * before the optimizer, so a caller may collect them:
- *   vlpet_finalize_defer(1)   from now on backward calls made by THIS host thread queue that launch instead of issuing it (returns
- *                             the previous setting); the queue itself is per process -- a framework's autograd worker thread
- *                             fills it, the thread that called backward() flushes it.  The call's workspace and its gradient outputs must stay allocated -- and the
- *                             outputs are incomplete -- until the flush.
- *   vlpet_finalize_flush(s)   launches everything queued on stream s (which must be ordered after the queued calls' streams), up to
- *                             16 calls per launch; same arithmetic and order of additions per call: bit-identical results.
- *   vlpet_finalize_pending()  queue length;  vlpet_finalize_discard()  drops the queue (error paths).
- * (The reference leaves this to autograd's per-parameter AccumulateGrad: src/trainer_base.py / multitask.py:682-695.) */
-int vlpet_finalize_defer(int on);
-int vlpet_finalize_pending(void);
-int vlpet_finalize_discard(void);
-int vlpet_finalize_flush(vlpet_stream_t stream);
-
 /* Deferred form of the two reductions above, for a trainer (nobody reads a parameter gradient before the optimizer step):
  * vlpet_colsum_partial runs only the first pass of vlpet_colsum (workspace [vlpet_sublayer_tail_partials(M)][n]); vlpet_reduce_batch
  * sums n_jobs partial blocks in ONE launch per 96 jobs: job j reduces partials[j] viewed as [n_partials[j]][2 d[j]] into out0[j] [d]

@@ -25,6 +25,14 @@ def test_exports_every_declared_symbol():
     assert set(syms) == set(_lib.SIGNATURES), "ctypes table and header disagree"
 
 
+def test_no_process_wide_switches_in_the_header():
+    """The in-launch reduce is chosen per call (`phases` bit 5) and finalize launches are not queued: the library's only state between
+    calls is the dropout seed counter."""
+    syms = declared_symbols()
+    assert "vlpet_set_in_launch_reduce" not in syms
+    assert not [s for s in syms if s.startswith("vlpet_finalize_")]
+
+
 def test_diagnosis_build_is_not_stale():
     """The experiment-switch tests load vl-pet_amd/lib/libvlpet_hip_dbg.so (a DEBUG=1 build of the same sources) in child processes: if it
     exists it must export what the header declares -- a product rebuild that added an entry point without rebuilding it (__graft_entry__.build()

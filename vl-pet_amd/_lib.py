@@ -44,14 +44,9 @@ SIGNATURES = {
                                                                                            c_int64, c_int, c_int, c_int,
                                                                                            c_float, c_float, c_float, c_int,
                                                                                            c_void_p]),
-    "vlpet_finalize_defer": (c_int, [c_int]),
-    "vlpet_finalize_pending": (c_int, []),
-    "vlpet_finalize_discard": (c_int, []),
-    "vlpet_finalize_flush": (c_int, [c_void_p]),
     "vlpet_bwd_workspace_bytes": (c_size_t, [c_int64, c_int, c_int, c_int, c_int]),
     "vlpet_adapter_gate_bwd_form": (c_int, [c_int64, c_int, c_int, c_int]),
     "vlpet_adapter_gate_bwd_finalize_launch": (c_int, [c_int64, c_int, c_int, c_int]),
-    "vlpet_set_in_launch_reduce": (c_int, [c_int]),
     "vlpet_debug_build": (c_int, []),
     "vlpet_test_hold_cus": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p]),
     "vlpet_set_seed_counter": (c_int, [c_void_p]),

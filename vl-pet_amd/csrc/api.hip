@@ -8,7 +8,7 @@
 #include <stdio.h>
 #include <vector>
 
-#define VLPET_VERSION 600      // 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_set_in_launch_reduce, vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
+#define VLPET_VERSION 610      // 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
 #define VLPET_VERSION_R3 300      // 300: column-parallel K1 backward pass (pet_cols.hip), phases bits 3 / 4, vlpet_adapter_gate_bwd_form;
 #define VLPET_VERSION_R2 221      // 221: vlpet_sublayer_tail_reduce, vlpet_layernorm_bwd_xhat, vlpet_rmsnorm_{fwd,bwd}, vlpet_colsum;  round 2: LoRA dropout generator ABI, sliced AdamW, K3 training form; 210: strided attention entry points, streaming weight gradients; 220: low-rank visual projector
 
@@ -156,18 +156,16 @@ extern "C" int vlpet_set_seed_counter(const uint64_t* device_counter) {
     return 0;
 }
 
-// Round 6: the column-parallel backward passes (gated K1 at r <= 96, K2 / K3) sum their row-chunk partials inside the launch
-// (cols_reduce.h) -- unless the caller has said that OTHER kernels may run beside the backward (gradient collectives on their own
-// stream, a second process on the device): a workgroup that waits for partners which cannot start holds its CU for as long as the
-// foreign kernel lasts, where the two-launch form simply runs in two rounds.  Process-wide, like the seed counter; default on.
-static std::atomic<int> g_in_launch_reduce{1};
-extern "C" int vlpet_set_in_launch_reduce(int on) { return g_in_launch_reduce.exchange(on != 0 ? 1 : 0); }
-// ... and only where it was measured ahead (profiles/r06_in_launch_reduce_ab.txt, ABBA on one box): the configs[1] step at the full
+// Round 6: pass 2 of the gated K1 backward (r <= 96) sums its row-chunk partials inside the launch (cols_reduce.h) -- unless the call
+// sets `phases` bit 5 (32) because OTHER kernels may run beside the backward (gradient collectives on their own stream, a second
+// process on the device): a workgroup that waits for partners which cannot start holds its CU for as long as the foreign kernel
+// lasts, where the two-launch form simply runs in two rounds.  And only where it was measured ahead
+// (profiles/r06_in_launch_reduce_ab.txt, ABBA on one box): the configs[1] step at the full
 // batch (15,272-46,648 rows per call) 27.92 / 27.94 k samples/s with it against 27.73 / 27.45 k with the finalize launch, the K1
 // backward op 137.5 vs 138.9 us; at the per-rank sizes of an 8-GPU run (1,900-5,800 rows, replayed graph) 5.45 / 5.47 ms per step with it
 // against 5.43 / 5.43 without -- so small launches keep the finalize launch
 static bool k1_in_launch_reduce(int64_t M) {
-    return g_in_launch_reduce.load() != 0 && vlpet_tuning().cols_red != 0 && (vlpet_tuning().cols_red == 2 || M >= 8192);
+    return vlpet_tuning().cols_red != 0 && (vlpet_tuning().cols_red == 2 || M >= 8192);
 }
 
 // p in [0, 1): explicit mask (keep_mask != NULL) or the in-kernel generator keyed by `seed`; p == 0: no dropout
@@ -395,7 +393,7 @@ static int run_bwd(const void* dy, const void* xa, const void* res, const void* 
                    float* dwgd, float* dbgd, float* dwgu, float* dbgu, int r, int rg,
                    void* workspace, size_t workspace_bytes, int64_t M, int d, int tiles,
                    float s2, float sd, float gs, int flags, int io_dtype, vlpet_stream_t stream,
-                   int phases = 3 /* bit0: row-parallel kernel, bit1: weight gradients; bit3: skip the finalize of bit1, bit4: finalize only */,
+                   int phases = 3 /* bit0: row-parallel kernel, bit1: weight gradients; bit3: skip the finalize of bit1, bit4: finalize only, bit5: no in-launch reduce */,
                    const void* saved = nullptr /* vlpet_adapter_gate_fwd_save's block */,
                    const void* dx1_in = nullptr /* gated K1: added to dxg (must not alias it) */,
                    const void* yout = nullptr /* gated K1: the forward's output (PetBwdArgs::y) */) {
@@ -451,7 +449,7 @@ static int run_bwd(const void* dy, const void* xa, const void* res, const void* 
     // column-parallel pass of pet_cols_ng.hip (dx and both weight gradients from one read of dy and x)
     const bool ng2 = !gate && phases == 3 && vlpet_tuning().ng2 != 0 && ng_two_pass_applies(b, io_dtype == VLPET_F32);
     // round 6: pass 2 sums its row-chunk partials inside the launch (cols_reduce.h) -- no finalize launch; `phases` bit 5 keeps the
-    // round-3 two-launch form (same-box A/Bs; the results are bit-identical)
+    // round-3 two-launch form where other kernels may run beside the call (k1_in_launch_reduce; the results are bit-identical)
     const bool red4 = cols4 && !cols6 && !(phases & 32) && k1_in_launch_reduce(M);
     if (red4) { b.red_ctrl = reinterpret_cast<unsigned*>(ws + w.red_ctrl); b.red_words = (d / 128) * COLS_RED_STRIDE; }
     int gs3 = 0, ng3 = 0;
@@ -588,8 +586,8 @@ extern "C" int vlpet_adapter_gate_bwd_form(int64_t M, int d, int tiles, int io_d
     return 0;
 }
 
-// 1: the two-pass form at this shape ends in a separate finalize launch (`phases` bit 4 runs it); 0: pass 2 sums its row chunks itself
-// (round 6, cols_reduce.h) or the form is not the two-pass one
+// For a call without `phases` bit 5 -- 1: the two-pass form at this shape ends in a separate finalize launch (`phases` bit 4 runs
+// it); 0: pass 2 sums its row chunks itself (round 6, cols_reduce.h) or the form is not the two-pass one
 extern "C" int vlpet_adapter_gate_bwd_finalize_launch(int64_t M, int d, int tiles, int io_dtype) {
     if (check_common(M, d, tiles, io_dtype)) return -1;
     PetBwdArgs b{};
@@ -651,7 +649,7 @@ extern "C" int vlpet_adapter_gate_bwd_saved(int phases, const void* dy, const vo
     if (!dbd || !dbu || !saved || (phases & 19) == 0) return VLPET_E_NULL;
     return run_bwd(dy, x2, x2, x1, packed_a, packed_g, NO_DROP, dx2, dx1, dwd, dbd, dwu, dbu,
                    dwgd, dbgd, dwgu, dbgu, r, rg, workspace, workspace_bytes, M, d, tiles,
-                   x2_scale, delta_scale, flags ? gate_scale : 1.f, flags, io_dtype, stream, phases & 31, saved);
+                   x2_scale, delta_scale, flags ? gate_scale : 1.f, flags, io_dtype, stream, phases & 63, saved);
 }
 
 extern "C" int vlpet_adapter_gate_bwd_saved_acc(int phases, const void* dy, const void* x1, const void* x2, const void* saved,
@@ -666,7 +664,7 @@ extern "C" int vlpet_adapter_gate_bwd_saved_acc(int phases, const void* dy, cons
     if (!dbd || !dbu || !saved || !dx1_in || !flags || (phases & 19) == 0) return VLPET_E_NULL;
     return run_bwd(dy, x2, x2, x1, packed_a, packed_g, NO_DROP, dx2, dx1, dwd, dbd, dwu, dbu,
                    dwgd, dbgd, dwgu, dbgu, r, rg, workspace, workspace_bytes, M, d, tiles,
-                   x2_scale, delta_scale, gate_scale, flags, io_dtype, stream, phases & 31, saved, dx1_in);
+                   x2_scale, delta_scale, gate_scale, flags, io_dtype, stream, phases & 63, saved, dx1_in);
 }
 
 // The same with the forward's output y at hand (round 5): pass 1 of the two-pass forms then needs the gate chain's up projection
@@ -683,7 +681,7 @@ extern "C" int vlpet_adapter_gate_bwd_saved_y(int phases, const void* dy, const 
     if (!dbd || !dbu || !saved || !flags || (phases & 19) == 0) return VLPET_E_NULL;
     return run_bwd(dy, x2, x2, x1, packed_a, packed_g, NO_DROP, dx2, dx1, dwd, dbd, dwu, dbu,
                    dwgd, dbgd, dwgu, dbgu, r, rg, workspace, workspace_bytes, M, d, tiles,
-                   x2_scale, delta_scale, gate_scale, flags, io_dtype, stream, phases & 31, saved, dx1_in, y);
+                   x2_scale, delta_scale, gate_scale, flags, io_dtype, stream, phases & 63, saved, dx1_in, y);
 }
 
 extern "C" int vlpet_parallel_adapter_bwd(const void* dy, const void* x, const void* packed, void* dx,
@@ -1231,12 +1229,6 @@ extern "C" int vlpet_colsum_partial(const void* x, int64_t M, int n, float* work
     if (!aligned16(x)) return VLPET_E_ALIGN;
     return herr(launch_colsum_partial(x, M, n, workspace, io_dtype == VLPET_F32, (hipStream_t)stream));
 }
-
-// Deferred weight-gradient finalize passes (csrc/wgrad.hip finalize_flush): see include/vlpet_hip.h
-extern "C" int vlpet_finalize_defer(int on) { return finalize_defer(on); }
-extern "C" int vlpet_finalize_pending(void) { return finalize_pending(); }
-extern "C" int vlpet_finalize_discard(void) { finalize_discard(); return 0; }
-extern "C" int vlpet_finalize_flush(vlpet_stream_t stream) { return herr(finalize_flush((hipStream_t)stream)); }
 
 extern "C" int vlpet_reduce_batch(const float* const* partials, float* const* out0, float* const* out1, const int* n_partials,
                                   const int* d, int n_jobs, vlpet_stream_t stream) {

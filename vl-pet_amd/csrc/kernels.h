@@ -138,11 +138,6 @@ __host__ __device__ inline WgradLayout wgrad_layout(const WgradArgs& a) {
 }
 size_t wgrad_workspace_bytes(int njobs, int RT, int xcols_max, int row_chunks);
 hipError_t launch_wgrad_finalize(const WgradArgs& a, hipStream_t stream);      // sums the row-chunk partials into the outputs
-// ... or queues that pass (per host thread) while finalize_defer(1) is in force; finalize_flush launches the queue, up to 16 calls per launch
-int finalize_defer(int on);            // returns the previous setting
-int finalize_pending();
-void finalize_discard();
-hipError_t finalize_flush(hipStream_t stream);
 void wgrad_plan(int64_t M, int njobs, int xcols_max, int* row_chunks, int64_t* rows_per_chunk);
 hipError_t launch_wgrad(const WgradArgs& a, int io_fp32, hipStream_t stream);
 // Backward without a gate (K2, adapter-only K1, K3 without dropout) in two passes (pet_cols_ng.hip; bf16, r <= 96, saved activations)

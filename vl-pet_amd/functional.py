@@ -68,80 +68,11 @@ WGRAD_STREAM: Optional["torch.cuda.Stream"] = None
 # trainer leaves the switch off.
 DEFER_REDUCES = False
 _PENDING_REDUCES: list = []
-# ... and, round 5, the finalize launches of the weight-gradient kernels (the sum of a call's row-chunk partials into dW / db): with
-# the switch on, a backward op whose gradients all go to sinks queues that launch inside the library (vlpet_finalize_defer) and
-# flush_reduces() issues the queue, 16 calls per launch (19 launches -> 2 in a BART-base step, 37 -> 3 in T5-base).  The call's
-# workspace (the partial sums) is kept alive here until then.  Bit-identical (tests/test_gpu_graph.py) -- and measured worth NOTHING:
-# BART-base 17.07 / 17.65 vs 17.19 / 16.96 ms per step, emulated rank 1 of 8 5.34 vs 5.35 ms, T5-base 24.2 vs 24.2, 9.30 vs 9.27
-# (profiles/r05_deferred_finalize_ab.txt): the batched launch reads the same partial sums, by then out of the caches.  Off by default.
-DEFER_FINALIZE = False
-_PENDING_FINALIZE_KEEP: list = []
-
-
-class _deferred_finalize:
-    """``with _deferred_finalize(all_sinks, ws, ...):`` around a backward call -- its finalize launch is queued when a trainer defers."""
-
-    __slots__ = ("on", "keep")
-
-    def __init__(self, all_sinks: bool, *keep):
-        self.on = bool(DEFER_REDUCES and DEFER_FINALIZE and all_sinks)
-        self.keep = keep
-
-    def __enter__(self):
-        if self.on:
-            _lib.load().vlpet_finalize_defer(1)
-        return self
-
-    def __exit__(self, *exc):
-        if self.on:
-            _lib.load().vlpet_finalize_defer(0)
-            _PENDING_FINALIZE_KEEP.extend(self.keep)
-        return False
-
-
-# Under graph capture the finalize launch of a gated K1 backward (12 / 24 per step; ~10 us of a few dozen workgroups each) is issued on a
-# side stream: a parallel branch of the captured graph, joined by flush_reduces() at the end of the backward.  Nobody reads a weight
-# gradient before that, and the partial sums it reads are still warm (unlike the deferred + batched form above, which read them cold).
-# Eager steps keep it in line: two stream switches per op cost the host more than the launch hides.
-# MEASURED (profiles/r05_finalize_side_stream_ab.txt): the replayed step gets SLOWER -- 6.02 vs 5.37 ms (BART, emulated rank 1 of 8), 10.45 vs 9.17 ms
-# (T5), 24.9 vs 24.0 ms at T5's full batch: a fork + join inside a hipGraph costs ~50 us here (12 / 24 of them per step), five times the
-# launch it hides.  Off.
-FINALIZE_SIDE_STREAM = False
-_FIN_STREAM = None
-_FIN_PENDING = False
-_FIN_KEEP: list = []
-
-
-def _finalize_on_side(fn, *keep):
-    """``fn(stream_handle)`` = the finalize-only call of a backward op, issued on the side stream after everything queued on the current one."""
-    global _FIN_STREAM, _FIN_PENDING
-    cur = torch.cuda.current_stream()
-    if _FIN_STREAM is None:
-        _FIN_STREAM = torch.cuda.Stream()
-    _FIN_STREAM.wait_stream(cur)
-    with torch.cuda.stream(_FIN_STREAM):
-        rc = fn(_FIN_STREAM.cuda_stream)
-    _FIN_PENDING = True
-    _FIN_KEEP.extend(keep)            # (the partial sums live in the op's workspace: not to be recycled before the join)
-    return rc
-
-
-def join_finalize_stream():
-    global _FIN_PENDING
-    if _FIN_PENDING:
-        torch.cuda.current_stream().wait_stream(_FIN_STREAM)
-        _FIN_PENDING = False
-    _FIN_KEEP.clear()
 
 
 def discard_pending():
     """Error path of a trainer's backward: nothing queued survives the step."""
     _PENDING_REDUCES.clear()
-    if _PENDING_FINALIZE_KEEP:
-        _PENDING_FINALIZE_KEEP.clear()
-    lib = _lib.load()
-    if lib.vlpet_finalize_pending():
-        lib.vlpet_finalize_discard()
 
 
 def reduce_partials(part: torch.Tensor, nb: int, d: int, out0: Optional[torch.Tensor], out1: Optional[torch.Tensor], deferrable: bool):
@@ -154,12 +85,6 @@ def reduce_partials(part: torch.Tensor, nb: int, d: int, out0: Optional[torch.Te
 
 
 def flush_reduces():
-    lib = _lib.load()
-    join_finalize_stream()
-    if lib.vlpet_finalize_pending():
-        rc = lib.vlpet_finalize_flush(_stream())
-        _PENDING_FINALIZE_KEEP.clear()
-        _lib.check(rc, "vlpet_finalize_flush")
     if not _PENDING_REDUCES:
         return 0
     jobs, n = list(_PENDING_REDUCES), len(_PENDING_REDUCES)
@@ -267,10 +192,10 @@ K1_BWD_PREVIOUS_SPLIT = False
 # activations: dq = dy * y * (1 - g), so pass 1 recomputes the gate's up projection only (vlpet_adapter_gate_bwd_saved_y).
 # False = from x2 (recompute h = s2 * x2 + sd * up_A(z_a)), the rounds 2-4 form.
 K1_BWD_FROM_OUTPUT = True
-# round 6: pass 2 of the gated backward (r <= 96) sums its row-chunk partials inside the launch (csrc/cols_reduce.h).  True = the
-# round-3 form (partial slabs + a finalize launch, ABI phases bit 5) for same-box A/Bs; the results are bit-identical.  (The
-# library-wide switch vlpet_set_in_launch_reduce -- train.Trainer turns it off where gradient collectives overlap the backward --
-# covers K2 / K3 as well.)
+# round 6: pass 2 of the gated K1 backward (r <= 96) sums its row-chunk partials inside the launch (csrc/cols_reduce.h).  True = the
+# round-3 form (partial slabs + a finalize launch, ABI phases bit 5), read per call; the results are bit-identical.  Set it where
+# other kernels run beside the backward: train.Trainer does so around a backward that overlaps gradient collectives or the side-stream
+# weight gradients.
 K1_BWD_FINALIZE_LAUNCH = False
 
 WEIGHTS_EPOCH = 0
@@ -713,7 +638,7 @@ class _AdapterGateFn(torch.autograd.Function):
         # NOT free: the sublayer tail that consumes it saves its own output / pre-norm sum, not y, so one more [M, d] tensor of
         # the IO dtype lives from this forward to its backward -- 12 of them in a BART-base encoder, 24 in T5-base (43 MB each at 28,000
         # rows: +0.5 GB of peak activation memory at the configs[1] batch, measured by bench.py's peak_memory_GB with
-        # VLPET_K1_BWD_FROM_X2=1 beside the default; profiles/r06_peak_memory_from_output_ab.txt).  On a 288 GB device the 3 % faster pass 1
+        # VLPET_K1_BWD_FROM_X2=1 beside the default).  On a 288 GB device the 3 % faster pass 1
         # is the better trade; memory-constrained runs set K1_BWD_FROM_OUTPUT = False.
         ctx.has_y = bool(K1_BWD_FROM_OUTPUT and act is not None and gate_mode == GATE_MUL)
         ctx.save_for_backward(x1f if x1f is not None else x2f, x2f, *params, *((out,) if ctx.has_y else ()))
@@ -792,14 +717,8 @@ class _AdapterGateFn(torch.autograd.Function):
             rc = _timed("k1_bwd_rows", M, lambda: phase(1 | 4, args))
             if rc == 0:
                 rc = _timed("k1_bwd_wgrad", M, lambda: phase(2 | 4, args))
-        elif (FINALIZE_SIDE_STREAM and gate and act is not None and TIMER is None and all(s is not None for s in sinks)
-              and torch.cuda.is_current_stream_capturing() and lib.vlpet_adapter_gate_bwd_form(M, d, pk_a.tiles, io) == 2):
-            rc = phase(3 | 8, args)                    # pass 1 + pass 2; the finalize launch as a parallel branch of the captured graph
-            if rc == 0:
-                rc = _finalize_on_side(lambda st: phase(16, args[:-1] + (st,)), ws)
         elif TIMER is None or not TIMER.wants("k1_bwd_rows"):
-            with _deferred_finalize(all(s is not None for s in sinks), ws):
-                rc = phase(3, args)
+            rc = phase(3, args)
         elif not gate:
             # adapter-only K1 (small / middle gate scripts): its two-pass form is taken for the WHOLE op only (csrc/api.hip ng2), so the
             # bracketed path issues it as one call too -- split phases would time the round-2 row kernel instead of what ships
@@ -847,7 +766,10 @@ def adapter_gate(x1, x2, down_w, down_b, up_w, up_b, gate_params, pk_a: PackedPa
                  out_link: Optional[ResidualLink] = None):
     """Encoder granularity-controlled adapter (+ low-rank gate).  ``gate_params`` =
     (gate_down_w, gate_down_b, gate_up_w, gate_up_b) or None.  ``link``: see ResidualLink (the tail's d/dx1 comes in);
-    ``out_link``: armed by the sublayer's first GEMM (linear_acc) -- this op's d/dx1 goes out through it."""
+    ``out_link``: armed by the sublayer's first GEMM (linear_acc) -- this op's d/dx1 goes out through it.
+    A caller outside ``train.Trainer`` whose other kernels share the device during the backward (gradient collectives on another
+    stream, a second trainer) sets ``K1_BWD_FINALIZE_LAUNCH = True`` around it: the in-launch reduce of pass 2 waits for partner
+    workgroups, which such kernels can keep from starting (a bounded wait: the results stay right, the time is lost)."""
     params = list(down_w) + list(down_b) + [up_w, up_b]
     if gate_mode != GATE_NONE:
         params += list(gate_params)
@@ -902,15 +824,14 @@ class _ParallelAdapterFn(torch.autograd.Function):
         nws = lib.vlpet_bwd_workspace_bytes(M, d, pk.tiles, 0, io)
         ws = torch.empty(nws, dtype=torch.uint8, device=xf.device)
         act = ctx.act
-        with _deferred_finalize(s0 is not None and s1 is not None and s2 is not None and (s3 is not None or bu is None), ws, dbu):
-            if act is not None:
-                rc = _timed("k2_bwd", M, lambda: lib.vlpet_parallel_adapter_bwd_saved(
-                    dyf.data_ptr(), xf.data_ptr(), act.data_ptr(), pk.buf.data_ptr(), dx.data_ptr(), dwd.data_ptr(), dbd.data_ptr(),
-                    dwu.data_ptr(), dbu.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io, _stream()))
-            else:
-                rc = _timed("k2_bwd", M, lambda: lib.vlpet_parallel_adapter_bwd(
-                    dyf.data_ptr(), xf.data_ptr(), pk.buf.data_ptr(), dx.data_ptr(), dwd.data_ptr(), dbd.data_ptr(),
-                    dwu.data_ptr(), dbu.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io, _stream()))
+        if act is not None:
+            rc = _timed("k2_bwd", M, lambda: lib.vlpet_parallel_adapter_bwd_saved(
+                dyf.data_ptr(), xf.data_ptr(), act.data_ptr(), pk.buf.data_ptr(), dx.data_ptr(), dwd.data_ptr(), dbd.data_ptr(),
+                dwu.data_ptr(), dbu.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io, _stream()))
+        else:
+            rc = _timed("k2_bwd", M, lambda: lib.vlpet_parallel_adapter_bwd(
+                dyf.data_ptr(), xf.data_ptr(), pk.buf.data_ptr(), dx.data_ptr(), dwd.data_ptr(), dbd.data_ptr(),
+                dwu.data_ptr(), dbu.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io, _stream()))
         ctx.act = None
         _lib.check(rc, "vlpet_parallel_adapter_bwd")
         gw = _finish([(dwd, s0, wd), (dbd, s1, bd), (dwu, s2, wu)])
@@ -1002,15 +923,14 @@ class _LoraDeltaFn(torch.autograd.Function):
         nws = lib.vlpet_bwd_workspace_bytes(M, d, pk.tiles, 0, io)
         ws = torch.empty(nws, dtype=torch.uint8, device=xf.device)
         act = ctx.act
-        with _deferred_finalize(s0 is not None and s1 is not None, ws):
-            if act is not None:
-                rc = _timed("k3_bwd", M, lambda: lib.vlpet_lora_delta_bwd_saved(
-                    dyf.data_ptr(), xf.data_ptr(), act.data_ptr(), pk.buf.data_ptr(), _ptr(ctx.keep), p, seed, dx.data_ptr(),
-                    da.data_ptr(), db.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io, _stream()))
-            else:
-                rc = _timed("k3_bwd", M, lambda: lib.vlpet_lora_delta_bwd(
-                    dyf.data_ptr(), xf.data_ptr(), pk.buf.data_ptr(), _ptr(ctx.keep), p, seed, dx.data_ptr(), da.data_ptr(),
-                    db.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io, _stream()))
+        if act is not None:
+            rc = _timed("k3_bwd", M, lambda: lib.vlpet_lora_delta_bwd_saved(
+                dyf.data_ptr(), xf.data_ptr(), act.data_ptr(), pk.buf.data_ptr(), _ptr(ctx.keep), p, seed, dx.data_ptr(),
+                da.data_ptr(), db.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io, _stream()))
+        else:
+            rc = _timed("k3_bwd", M, lambda: lib.vlpet_lora_delta_bwd(
+                dyf.data_ptr(), xf.data_ptr(), pk.buf.data_ptr(), _ptr(ctx.keep), p, seed, dx.data_ptr(), da.data_ptr(),
+                db.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io, _stream()))
         ctx.act = None
         _lib.check(rc, "vlpet_lora_delta_bwd")
         gx = dx.view(shape)

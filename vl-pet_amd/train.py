@@ -538,7 +538,6 @@ CPU_OPTIMIZER_FACTORY = None
 _REGISTERED_SEED_CTR = None     # address of the device step counter currently registered with the library (Trainer.enable_graph / close)
 MAX_GRAPHS = 16              # captured step shapes a trainer keeps (least recently replayed evicted); ragged data beyond it runs eager + capture
 LABEL_CHECK_EVERY = 100      # steps between reads of the device-side bad-label tally (0: never)
-IN_LAUNCH_REDUCE = True         # A/B switch (tools/ab_switches.py): False = the K1 / K2 / K3 backward passes always end in a finalize launch (round 3)
 DEFER_PARAM_REDUCES = True      # A/B switch (tools/ab_switches.py): False = one reduce launch per parameter gradient, as before round 4
 
 
@@ -662,23 +661,23 @@ class Trainer:
         loss = task_loss(per_token, batch["labels"], batch.get("scores"), batch["task"])
         if self.flat.flat.is_cuda:
             from . import functional as VF
+            alone = (not self.flat.dp) or self.flat.defer      # no bucket all-reduce starts from inside the backward
             # parameter-gradient reductions of this backward (bias column sums, LayerNorm gradients) as one batched launch at its
             # end -- unless bucket all-reduces start from inside the backward (they would read the buckets before the flush)
-            VF.DEFER_REDUCES = DEFER_PARAM_REDUCES and ((not self.flat.dp) or self.flat.defer)
-            # ... and the column-parallel backward passes sum their row-chunk partials inside the launch (csrc/cols_reduce.h) only while
-            # nothing else runs beside the backward: with bucket all-reduces overlapping it (or the weight gradients on a side stream) a
-            # workgroup waiting for partners that cannot start would hold its CU for the collective's duration -- the two-launch form then
-            from . import _lib
-            was = _lib.load().vlpet_set_in_launch_reduce(
-                1 if IN_LAUNCH_REDUCE and VF.WGRAD_STREAM is None and ((not self.flat.dp) or self.flat.defer) else 0)
+            VF.DEFER_REDUCES = DEFER_PARAM_REDUCES and alone
+            # ... and the gated K1 backward sums its row-chunk partials inside the launch (csrc/cols_reduce.h) only while nothing else
+            # runs beside the backward: with bucket all-reduces overlapping it (or the weight gradients on a side stream) a workgroup
+            # waiting for partners that cannot start would hold its CU for the collective's duration -- the two-launch form (ABI phases
+            # bit 5) then simply runs in two rounds
+            fin_was = VF.K1_BWD_FINALIZE_LAUNCH
+            VF.K1_BWD_FINALIZE_LAUNCH = bool(fin_was or VF.WGRAD_STREAM is not None or not alone)
             try:
                 loss.backward()
                 VF.flush_reduces()
             finally:
-                _lib.load().vlpet_set_in_launch_reduce(was)
+                VF.K1_BWD_FINALIZE_LAUNCH = fin_was
                 VF.DEFER_REDUCES = False
                 VF.discard_pending()              # (empty after a clean flush)
-                VF._FIN_KEEP.clear()
         else:
             loss.backward()
         return loss
