@@ -22,7 +22,6 @@ ALLOWED = [
     (r"^void visproj_fwd_kernel<", "4-wave K4 forward: VLPET_K4_WAVES4 of a debug build only"),
     (r"^void visproj_fwd2_kernel<float, ", "fp32 IO = parity mode"),
     (r"^void visproj_fwd2_kernel<__bf16, 24>", "round-2 fused K4 forward: superseded by visproj_gemm_kernel (round 5) wherever d_model is a multiple of 256 (both backbones); left for other widths and for visproj.K4_FORM = \"fused\" A/Bs"),
-    (r"^void attn_bwd_kernel<3, 4, true>", "backbone pass (SURVEY 8d: ungraded): three waves per SIMD with 7 spilled registers measured faster than two without (DESIGN.md, round 2 fourth session)"),
 ]
 
 
@@ -61,7 +60,7 @@ def test_every_object_has_a_resource_report_and_kernels():
     assert len(rows) > 300 and {"tail.res", "pet_cols.res", "pet_dz2.res", "visproj.res", "pet_fwd2p.res"} <= objs, sorted(objs)
 
 
-def test_no_vector_register_spills_on_the_default_path():
+def test_no_vector_register_spills_outside_the_allow_list():
     rows = _reports()
     bad, used = [], set()
     for r in rows:
@@ -75,6 +74,19 @@ def test_no_vector_register_spills_on_the_default_path():
     assert not bad, "kernels that spill vector registers and are not on the allow-list:\n" + "\n".join(map(str, bad))
     stale = [ALLOWED[i][0] for i in range(len(ALLOWED)) if i not in used]
     assert not stale, f"allow-list entries that no longer match a spilling kernel (remove them): {stale}"
+
+
+def test_attention_backward_kernels_do_not_spill():
+    """The short-sequence attention backward (csrc/attn.hip), every instantiation: no spilled registers, and the three-tile forms
+    (65-96 keys) within 168 registers -- three waves per SIMD.  The three-tile form with a bias once spilled 7 registers at that
+    occupancy (allow-listed as measured faster than two waves without); since the dropout element hash takes a rotation before its
+    second multiply, none of the forms spills."""
+    rows = [r for r in _reports() if r["file"] == "attn.res" and r["demangled"].startswith("void attn_bwd_kernel<")]
+    assert len(rows) >= 4, [r["demangled"] for r in rows]
+    for r in rows:
+        assert r["spill"] == 0, r
+        if r["demangled"].startswith("void attn_bwd_kernel<3,"):
+            assert r["vgpr"] + r["agpr"] <= 168, r
 
 
 def test_k5_row_kernels_keep_four_waves_per_simd_at_d768():

@@ -18,7 +18,7 @@
 //     = key, registers = queries), P and dS elementwise, then dV^T += dO^T P, dK^T += Q^T dS (contraction over queries:
 //     B operand = the registers, A operand = transpose-read of the dO / Q image);
 //   phase Q (a wave owns a 32-query block, loops over the key tiles):  the swapped form again, dQ^T += K^T dS.
-// Dropout keeps element (b, h, i, j) iff hash32(row_key(b, h, i) + j * golden) >= p * 2^32: a function of the element index
+// Dropout keeps element (b, h, i, j) iff hash_elem(row_key(b, h, i) + j * golden) >= p * 2^32: a function of the element index
 // and the call's seed only, so the three places that need the mask regenerate it.
 #include <cstdlib>
 #include "common.h"
@@ -38,13 +38,23 @@ __device__ __forceinline__ uint32_t hash32(uint32_t x) {
     x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
     return x;
 }
-// per-row key of the dropout mask: rows are (b, h, i) triples
+// per-row key of the dropout mask: rows are (b, h, i) triples.  The seed is hashed down to a 32-bit key before the row index is
+// added: the earlier form hashed seed_lo ^ row, so the seeds s and s ^ 1 gave the same rows in swapped pairs (row r of one mask =
+// row r ^ 1 of the other).  Once per row, not per element.
 __device__ __forceinline__ uint32_t row_key(uint64_t seed, int64_t row) {
-    return hash32((uint32_t)seed ^ (uint32_t)row) ^ hash32((uint32_t)(seed >> 32) + (uint32_t)((uint64_t)row >> 32));
+    const uint32_t k = hash32((uint32_t)seed ^ hash32((uint32_t)(seed >> 32) + (uint32_t)((uint64_t)row >> 32)));
+    return hash32(k + (uint32_t)row);
 }
-// element (row, j): one multiply-xorshift round over the row's key (a full hash32 of the seed and the row index) plus a Weyl step per
-// column -- four VALU operations per element instead of nine (the backward kernels are bound by their instruction count)
-__device__ __forceinline__ uint32_t hash_elem(uint32_t x) { x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; return x; }
+// element (row, j): the row's key plus a Weyl step per column, one multiply-xorshift round, a rotation by 16 and a second multiply
+// (v_alignbit_b32 + v_mul_lo_u32 more than the first form; a full hash32 is nine operations -- the backward kernels are bound by
+// their instruction count).  The second multiply is needed: with one round the top bits of columns j and j + k stayed nearly a
+// constant offset apart, and column pairs of a mask were correlated by up to 0.037 at any number of rows (tests/test_dropout_spec.py;
+// independent columns give 0).  The rotation brings the bits the xorshift mixed to the bottom, where the multiply spreads them
+// upwards -- and the compiler keeps the three-tile backward kernels within 168 registers with it, where a bare second multiply spilled.
+__device__ __forceinline__ uint32_t hash_elem(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15;
+    return __builtin_amdgcn_alignbit(x, x, 16) * 0x846ca68bU;
+}
 __device__ __forceinline__ bool keep_elem(uint32_t rk, int j, uint32_t thr) { return hash_elem(rk + (uint32_t)j * 0x9E3779B9U) >= thr; }
 
 // A operand from a row-major LDS image: lane (c = lane & 31, hh = lane >> 5) gets column cb + c of rows
