@@ -12,6 +12,12 @@ multitask.py:682-695).  ``--scaling weak`` (default): that batch per GPU; ``--sc
 GLOBAL batch, split across the ranks.  Synthetic CLIP-feature + token batches are resident in
 HBM before the timed region.  Rank 0 prints ONE JSON line.
 
+A plain run does only what that line's headline needs: set-up, the W warm-up steps and the settling rounds, the K timed steps,
+--dump-outputs, and the line (`value`, `ms_per_step`, the per-step times, peak memory).  ``--full`` adds everything that runs work
+of its own: the eager re-run of the timed steps and the per-kernel pass behind `roofline` / `kernels` (`eager_region`), the other
+scaling with N > 1 ranks (`other_scaling`), the measured gradient exchange of --emulate-ranks, and the CPU baseline (`cpu_baseline`,
+unless --no-cpu-baseline).  The timed steps are the same with and without it.
+
 Other workloads (parity-tested configs, not the headline): ``--model t5`` configs[2] (T5-base, r = 192),
 ``--model lora`` configs[3] (BART-base + LoRA r = --lora-r on q_proj / v_proj of all 18 attentions: the K3 path),
 ``--model video`` configs[4] (BART-base + VL-PET-large, video-text: batch 50, 600 text tokens + 64 frame features of 512).
@@ -262,6 +268,119 @@ def dump_outputs(out_dir, loss, tr):
     print(f"[bench] dumped {', '.join(f'{n} {a.shape}' for n, a in arrays.items())} to {out_dir}", file=sys.stderr, flush=True)
 
 
+def kernel_report(args, cfg, dtype, agg):
+    """--full: `roofline` (the dominant hand-written op against the HBM peak) and `kernels` (every bracketed launch group), from
+    the HIP-event brackets in `agg` (functional.KernelTimer.summary())."""
+    import torch
+    import vlpet_amd.functional as VF
+    esz = 2 if dtype == torch.bfloat16 else 4
+    d = cfg.d_model
+    # algorithmic bytes per row (SURVEY.md 8d): K1 fwd reads x1, x2, writes y; K1 bwd (the whole op: rows kernel + weight
+    # gradients) reads dy, x1, x2, writes dx1, dx2; K2 / K3 fwd read x, y|base, write out; K2 / K3 bwd read dy, x, write dx;
+    # K5 fwd reads y, x1, writes out; K5 bwd reads dout, writes dx1, dy (the saved pre-norm sum is extra traffic)
+    # Form of the gated K1 backward at this shape (vlpet_adapter_gate_bwd_form): 2 = pass 1 (k1_dz2_kernel / pet_gate_dz_kernel: reads dy, x2,
+    # writes only the [M, r] dpre) + the column-parallel pass (k1_cols_kernel: reads dy, x1, x2, writes dx1, dx2 and the
+    # weight-gradient partials) + the finalize launch; otherwise rows kernel + weight-gradient kernels as in round 2.
+    k1_tiles = 6 if args.model == "t5" else 3
+    # ... asked for THIS run's row counts (every K1 launch size the timers saw), not for a fixed size (ADVICE r03 / VERDICT r04 #11)
+    k1_rows = sorted(agg["k1_bwd_rows"]["by_rows"]) if "k1_bwd_rows" in agg else []
+    k1_forms = {int(m): int(VF._lib.load().vlpet_adapter_gate_bwd_form(int(m), d, k1_tiles, 1 if dtype == torch.bfloat16 else 0)) for m in k1_rows}
+    k1_form = max(set(k1_forms.values()), key=list(k1_forms.values()).count) if k1_forms else \
+        VF._lib.load().vlpet_adapter_gate_bwd_form(28000, d, k1_tiles, 1 if dtype == torch.bfloat16 else 0)
+    two_pass = k1_form == 2 and not args.k1_previous_split
+    per_row = {"k1_fwd": 3 * d * esz, "k1_bwd_rows": (2 if two_pass else 5) * d * esz, "k1_bwd_wgrad": (5 if two_pass else 0) * d * esz,
+               "k1_bwd_fin": 0, "k2_fwd": 3 * d * esz,
+               "k2_bwd": 3 * d * esz, "k3_fwd": 3 * d * esz, "k3_bwd": 3 * d * esz, "k5_fwd": 3 * d * esz,
+               "k5_bwd": 3 * d * esz, "k4_ln_bwd": 3 * d * esz, "k4_pos_fwd": d * esz, "k4_pos_bwd": d * esz,     # (R written / dout read)
+               "rms_fwd": 2 * d * esz, "rms_bwd": 3 * d * esz}      # (K4's LayerNorm backward: dout, xhat read, dpre written)
+    d_ff = int(getattr(cfg, "encoder_ffn_dim", 0) or getattr(cfg, "d_ff", 0))
+    per_row.update({"ffn_act_fwd": 2 * d_ff * esz, "ffn_act_bwd": 3 * d_ff * esz})   # backbone FFN activation + dropout pass
+    # backbone attention on the short-sequence kernels: q, k, v read + o written / q, k, v, o, do read + dq, dk, dv written
+    per_row.update({"attn_fwd": 4 * d * esz, "attn_bwd": 8 * d * esz})
+    V_head = int(cfg.vocab_size)
+    per_row.update({"ce_fwd": V_head * esz, "ce_bwd": 2 * V_head * esz})              # LM-head loss: one read / read + write of the logits
+    F_in = int(cfg.feat_dim)
+    flops_per_row = {"k4_fwd": 2.0 * F_in * d, "k4_wgrad": 2.0 * F_in * d}
+    kernels = {}
+    for name, a in agg.items():
+        by = per_row.get(name, 0) * a["rows"]
+        k = dict(launches=a["launches"], avg_us=round(a["total_us"] / a["launches"], 2),
+                 total_ms=round(a["total_us"] / 1e3, 3),
+                 algorithmic_GBps=round(by / a["total_us"] / 1e3, 1) if by else None)
+        if k["algorithmic_GBps"]:
+            k["hbm_frac"] = round(k["algorithmic_GBps"] / HBM_PEAK_GBS, 4)
+        if name in flops_per_row:
+            tf = flops_per_row[name] * a["rows"] / a["total_us"] / 1e6
+            k["TFLOPps"] = round(tf, 1)
+            k["mfma_frac"] = round(tf / MFMA_PEAK_TFLOPS, 4)
+        kernels[name] = k
+    # the K1 backward as ONE op (rows kernel + weight-gradient kernels): SURVEY 8d's 5*d*b per row over their summed time
+    if "k1_bwd_rows" in agg and "k1_bwd_wgrad" in agg:
+        a, w = agg["k1_bwd_rows"], agg["k1_bwd_wgrad"]
+        op_us = a["total_us"] + w["total_us"] + (agg["k1_bwd_fin"]["total_us"] if "k1_bwd_fin" in agg else 0.0)
+        gbps = 5 * d * esz * a["rows"] / op_us / 1e3
+        kernels["k1_bwd_op"] = dict(launches=a["launches"], avg_us=round(op_us / a["launches"], 2),
+                                    total_ms=round(op_us / 1e3, 3), algorithmic_GBps=round(gbps, 1),
+                                    hbm_frac=round(gbps / HBM_PEAK_GBS, 4),
+                                    note=(("pass 1 + column-parallel pass + finalize launch" if "k1_bwd_fin" in agg else
+                                           "pass 1 + column-parallel pass (weight gradients reduced in-launch)") + " of one K1 backward, 5*d*b per row" if two_pass
+                                          else "rows kernel + weight-gradient kernels of one K1 backward, 5*d*b per row"))
+    # dominant HIP kernel of the hot path by time
+    if args.model == "lora":
+        dom = "k3_bwd" if "k3_bwd" in agg else "k3_fwd"
+    else:
+        dom = ("k1_bwd_wgrad" if two_pass and "k1_bwd_wgrad" in agg else "k1_bwd_rows") if "k1_bwd_rows" in agg else "k1_fwd"
+    a = agg[dom]
+    kernel_achieved = per_row[dom] * a["rows"] / a["total_us"] / 1e3     # GB/s of the dominant kernel alone
+    tiles = 6 if args.model == "t5" else 3
+    lora_drop = args.model == "lora" and float(getattr(cfg, "lora_dropout", 0.0) or 0.0) > 0.0
+    kname = {"k1_bwd_rows": (f"k1_dz2_kernel<{tiles}>" if two_pass and tiles <= 3 else
+                             f"pet_gate_dz_kernel<{args.dtype},{tiles}>" if two_pass else
+                             f"pet_gate_bwd2_kernel<{args.dtype},{tiles}>" if tiles <= 3 else f"pet_bwd_kernel<{args.dtype},{tiles},gate>"),
+             "k1_bwd_wgrad": (f"k1_cols_kernel<{tiles}>" if tiles <= 3 else "k1_cols6_kernel<6>") +
+                             " (column-parallel pass of the K1 backward: reads dy, x1, x2, writes dx1, dx2)",
+             "k1_fwd": f"pet_gate_fwd_kernel<{args.dtype},{tiles}> / k1_down_kernel + k1_up_kernel (by shape)",
+             "k3_bwd": ("ng_dz_kernel + ng_cols_kernel<drop> + wgrad_finalize_kernel" if lora_drop else
+                        "ng_dz_kernel + ng_cols_kernel + wgrad_finalize_kernel") + " (one K3 backward, two-pass form of csrc/pet_cols_ng.hip)",
+             "k3_fwd": f"pet_fwd_kernel<{args.dtype},act_id{',drop' if lora_drop else ''}>"}[dom]
+    traffic = None
+    PMC_TRAFFIC = PMC_TRAFFIC_FORMS[("two_pass_t5" if args.model == "t5" else "two_pass") if (args.model != "lora" and two_pass)
+                                    else "previous_split"]
+    def pmc_avg(group):          # average PMC bytes per launch over THIS run's launch sizes
+        tab = PMC_TRAFFIC["bytes_by_rows"][group]
+        br = a["by_rows"]
+        return round(sum(pmc_bytes(tab, m) * c[0] for m, c in br.items()) / max(1, sum(c[0] for c in br.values())))
+    if dom in PMC_TRAFFIC["bytes_by_rows"] and args.dtype == "bf16" and args.model in ("bart", "t5", "video"):
+        traffic = pmc_avg(dom)
+    # Headline fraction = the whole K1 backward OP (SURVEY 8d's 5*d*b per row is the op's byte count; the op is three launches):
+    # algorithmic bytes / (pass 1 + column-parallel pass + finalize).  The dominant kernel's own figures stay beside it.
+    op = kernels.get("k1_bwd_op") if dom in ("k1_bwd_rows", "k1_bwd_wgrad") else None
+    if op is not None:
+        achieved, launch_us, what = op["algorithmic_GBps"], op["avg_us"], "K1 backward op = " + \
+            (("pass 1 + column-parallel pass + finalize launch" if "k1_bwd_fin" in agg else
+              "pass 1 + column-parallel pass (in-launch reduce-scatter where M >= 8192, finalize launch below)") if two_pass
+             else "rows kernel + weight-gradient kernels")
+        algo_row = 5 * d * esz
+        if traffic:
+            traffic = pmc_avg("k1_bwd_op")
+    else:
+        achieved, launch_us, what, algo_row = kernel_achieved, a["total_us"] / a["launches"], kname, per_row[dom]
+    roof = dict(bound="hbm", kernel=what, achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s",
+                frac=round(achieved / HBM_PEAK_GBS, 4), traffic=traffic,
+                traffic_source=(f"{PMC_TRAFFIC['source']}: PMC passes at M = {PMC_TRAFFIC['measured_at_rows']}, interpolated per launch "
+                                f"over this run's launch sizes") if traffic else None,
+                avg_launch_us=round(launch_us, 2),
+                avg_rows_per_launch=round(a["rows"] / a["launches"], 1),
+                algorithmic_bytes_per_row=algo_row,
+                dominant_kernel=dict(name=kname, avg_launch_us=round(a["total_us"] / a["launches"], 2),
+                                     achieved=round(kernel_achieved, 1), frac=round(kernel_achieved / HBM_PEAK_GBS, 4),
+                                     note="the op's algorithmic bytes over this ONE launch's time (the pre-round-4 headline)"))
+    if op is not None:
+        roof["op_frac"] = op["hbm_frac"]
+        roof["op_avg_us"] = op["avg_us"]
+    return roof, kernels
+
+
 def build_model(args, dev, dtype):
     import vlpet_amd.host.bart as HB
     import vlpet_amd.train as TR
@@ -316,7 +435,11 @@ def main():
                     help="one GPU, the batch ONE of R strong-scaled ranks would see (global task batch / R): a 1-GPU upper-bound "
                          "estimate of the R-GPU step time before any multi-GPU run (value stays this rank's samples/s)")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what runs work of its own after the timed region: the roofline and per-kernel table "
+                         "(eager_region, roofline, kernels), other_scaling (N > 1), the gradient exchange of --emulate-ranks, "
+                         "and the CPU baseline; off: only the headline line")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU baseline")
     ap.add_argument("--buckets", type=int, default=3)
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL over xGMI); gloo only to exercise the DP path on a 1-GPU box")
     ap.add_argument("--pad-mask", action="store_true", default=True,
@@ -332,15 +455,16 @@ def main():
                     help="TunableOp table for the backbone's library GEMMs: on = use vl-pet_amd/tuning/tunableop_gfx950.csv, "
                          "tune = measure this run's shapes into gpurun_out/tunableop_gfx950_new.csv (slow), off = library defaults")
     ap.add_argument("--kernel-table", default="after", choices=["after", "inline", "off"],
-                    help="where the per-kernel table is measured: a separate pass after the timed region (default; the timed "
-                         "region brackets only the roofline's op), inline (every launch bracketed inside the timed region), off")
+                    help="where the per-kernel table of --full is measured: a separate pass after the timed region (default; the "
+                         "timed region brackets only the roofline's op), inline (every launch bracketed inside the timed region), off")
     ap.add_argument("--graph", default="auto", choices=["auto", "on", "off"],
                     help="train.Trainer(graph=True): forward + backward of a step captured per task shape with hipGraph and replayed "
                          "(optimizer and gradient exchange eager).  auto = on wherever the trainer can replay (same box, round 6: the "
                          "headline workload 16.99 ms replayed vs 17.93 ms eager -- the eager step's ~150 host launches are no longer hidden "
                          "behind the kernels).  A replayed step runs no host code, and events recorded inside a captured graph cannot be "
-                         "read on this stack (tools/graph_event_probe.py), so the same K-step schedule runs once more eagerly right after "
-                         "the timed region with the roofline op bracketed (`eager_region`).  off = the eager step timed, brackets inside it")
+                         "read on this stack (tools/graph_event_probe.py), so with --full the same K-step schedule runs once more eagerly "
+                         "right after the timed region with the roofline op bracketed (`eager_region`).  off = the eager step timed, "
+                         "brackets inside it")
     ap.add_argument("--capture-collectives", action="store_true",
                     help="graph mode, --gpus > 1: launch the bucket all-reduces from inside the captured backward (RCCL collectives as graph nodes: "
                          "overlap kept under replay) instead of after the replay.  Tested with a one-rank RCCL communicator only.")
@@ -442,6 +566,7 @@ def main():
     batches = {t: TR.synthetic_batch(t, rank_batch(t), cfg, dev, gen, no_padding=not args.pad_mask) for t in tasks}
     order = [tasks[i % len(tasks)] for i in range(args.warmup + args.steps)]
     total_steps = max(args.steps + args.warmup + setup_steps, 10) + 8 + 5 * len(tasks) + args.steps     # (+ the settling rounds, + the eager region after a replayed one)
+    # (the same schedule without --full: the timed steps then see the same learning rates whether or not the steps after them run)
     tr.total, tr.warmup = total_steps, int(total_steps * 0.1)
 
     for i in range(setup_steps):
@@ -487,7 +612,8 @@ def main():
     torch.cuda.synchronize()
     # Live HIP-event brackets inside the timed region: only the launches of the roofline's op (every bracket is two marker
     # packets on the launch stream; bracketing all ~150 launches of a step cost the step a few percent).  The full per-kernel
-    # table comes from a separate pass after the timed region (--kernel-table inline restores the old behaviour).
+    # table comes from a separate pass after the timed region (--kernel-table inline restores the old behaviour).  The brackets are
+    # set without --full too, which then does not report them: the timed steps stay the same with and without it.
     dom_names = ("k3_bwd", "k3_fwd") if args.model == "lora" else ("k1_bwd_rows", "k1_bwd_wgrad", "k1_bwd_fin")
     VF.K1_BWD_PREVIOUS_SPLIT = bool(args.k1_previous_split)
     VF.TIMER = VF.KernelTimer(None if args.kernel_table == "inline" else dom_names)
@@ -512,7 +638,7 @@ def main():
         dump_outputs(args.dump_outputs, loss, tr)
     timer, VF.TIMER = VF.TIMER, None
     eager_region = None
-    if graph_on:
+    if graph_on and args.full:
         # a replayed step runs no host code, so nothing was bracketed above (and an event recorded inside a captured graph cannot be
         # read back: tools/graph_event_probe.py, "invalid resource handle").  The SAME K-step schedule runs once more, eagerly, in this
         # process right after the timed region, with the roofline op bracketed on the launch stream exactly as --graph off brackets
@@ -536,9 +662,10 @@ def main():
                         "samples_per_s_this_rank": round(samples / e_dt, 2),
                         "note": "the same K steps, eager launches, right after the timed region; the roofline op's HIP-event brackets are from these steps"}
     table_timer = None
-    if args.kernel_table == "after" and rank == 0:
+    kernel_pass = args.full and args.kernel_table == "after"
+    if kernel_pass and rank == 0:
         table_timer = VF.TIMER = VF.KernelTimer()
-    if args.kernel_table == "after":               # every rank steps (the gradient exchange is collective); untimed
+    if kernel_pass:                                # every rank steps (the gradient exchange is collective); untimed
         for t_ in tasks:
             tr.step(batches[t_])
         torch.cuda.synchronize()
@@ -554,7 +681,7 @@ def main():
     # batch partitioned across the ranks, a few thousand encoder rows per rank).  The other reading -- the same per-GPU batch on every
     # rank (weak) -- is measured on the same ranks right after the timed region and reported beside it (`other_scaling`).
     strong = None
-    if n_ranks > 1:
+    if n_ranks > 1 and args.full:
         other = "weak" if args.scaling == "strong" else "strong"
 
         def other_batch(t):
@@ -581,7 +708,7 @@ def main():
                   "note": f"same ranks, {other} scaling (timed right after the main region)"}
 
     exchange = None
-    if args.emulate_ranks > 1 and dev.type == "cuda":
+    if args.full and args.emulate_ranks > 1 and dev.type == "cuda":
         own_group = not dist.is_initialized()
         if own_group:           # (a one-rank RCCL group of this process: rendezvous on 127.0.0.1)
             dist.init_process_group(backend="nccl", init_method=f"tcp://127.0.0.1:{free_port()}", rank=0, world_size=1, device_id=dev)
@@ -609,115 +736,12 @@ def main():
             dist.destroy_process_group()
 
     if rank == 0:
-        esz = 2 if dtype == torch.bfloat16 else 4
-        d = cfg.d_model
-        agg = timer.summary()
-        if table_timer is not None:                 # the other launch groups: one step per task after the timed region
-            for name, a in table_timer.summary().items():
-                agg.setdefault(name, a)
-        # algorithmic bytes per row: K1 fwd reads x1, x2, writes y; K1 bwd (the whole op: rows kernel + weight
-        # gradients) reads dy, x1, x2, writes dx1, dx2; K2 / K3 fwd read x, y|base, write out; K2 / K3 bwd read dy, x, write dx;
-        # K5 fwd reads y, x1, writes out; K5 bwd reads dout, writes dx1, dy (the saved pre-norm sum is extra traffic)
-        # Form of the gated K1 backward at this shape (vlpet_adapter_gate_bwd_form): 2 = pass 1 (k1_dz2_kernel / pet_gate_dz_kernel: reads dy, x2,
-        # writes only the [M, r] dpre) + the column-parallel pass (k1_cols_kernel: reads dy, x1, x2, writes dx1, dx2 and the
-        # weight-gradient partials) + the finalize launch; otherwise rows kernel + weight-gradient kernels as in round 2.
-        k1_tiles = 6 if args.model == "t5" else 3
-        # ... asked for THIS run's row counts (every K1 launch size the timers saw), not for a fixed size (ADVICE r03 / VERDICT r04 #11)
-        k1_rows = sorted(agg["k1_bwd_rows"]["by_rows"]) if "k1_bwd_rows" in agg else []
-        k1_forms = {int(m): int(VF._lib.load().vlpet_adapter_gate_bwd_form(int(m), d, k1_tiles, 1 if dtype == torch.bfloat16 else 0)) for m in k1_rows}
-        k1_form = max(set(k1_forms.values()), key=list(k1_forms.values()).count) if k1_forms else \
-            VF._lib.load().vlpet_adapter_gate_bwd_form(28000, d, k1_tiles, 1 if dtype == torch.bfloat16 else 0)
-        two_pass = k1_form == 2 and not args.k1_previous_split
-        per_row = {"k1_fwd": 3 * d * esz, "k1_bwd_rows": (2 if two_pass else 5) * d * esz, "k1_bwd_wgrad": (5 if two_pass else 0) * d * esz,
-                   "k1_bwd_fin": 0, "k2_fwd": 3 * d * esz,
-                   "k2_bwd": 3 * d * esz, "k3_fwd": 3 * d * esz, "k3_bwd": 3 * d * esz, "k5_fwd": 3 * d * esz,
-                   "k5_bwd": 3 * d * esz, "k4_ln_bwd": 3 * d * esz, "k4_pos_fwd": d * esz, "k4_pos_bwd": d * esz,     # (R written / dout read)
-                   "rms_fwd": 2 * d * esz, "rms_bwd": 3 * d * esz}      # (K4's LayerNorm backward: dout, xhat read, dpre written)
-        d_ff = int(getattr(cfg, "encoder_ffn_dim", 0) or getattr(cfg, "d_ff", 0))
-        per_row.update({"ffn_act_fwd": 2 * d_ff * esz, "ffn_act_bwd": 3 * d_ff * esz})   # backbone FFN activation + dropout pass
-        # backbone attention on the short-sequence kernels: q, k, v read + o written / q, k, v, o, do read + dq, dk, dv written
-        per_row.update({"attn_fwd": 4 * d * esz, "attn_bwd": 8 * d * esz})
-        V_head = int(cfg.vocab_size)
-        per_row.update({"ce_fwd": V_head * esz, "ce_bwd": 2 * V_head * esz})              # LM-head loss: one read / read + write of the logits
-        F_in = int(cfg.feat_dim)
-        flops_per_row = {"k4_fwd": 2.0 * F_in * d, "k4_wgrad": 2.0 * F_in * d}
-        kernels = {}
-        for name, a in agg.items():
-            by = per_row.get(name, 0) * a["rows"]
-            k = dict(launches=a["launches"], avg_us=round(a["total_us"] / a["launches"], 2),
-                     total_ms=round(a["total_us"] / 1e3, 3),
-                     algorithmic_GBps=round(by / a["total_us"] / 1e3, 1) if by else None)
-            if k["algorithmic_GBps"]:
-                k["hbm_frac"] = round(k["algorithmic_GBps"] / HBM_PEAK_GBS, 4)
-            if name in flops_per_row:
-                tf = flops_per_row[name] * a["rows"] / a["total_us"] / 1e6
-                k["TFLOPps"] = round(tf, 1)
-                k["mfma_frac"] = round(tf / MFMA_PEAK_TFLOPS, 4)
-            kernels[name] = k
-        # the K1 backward as ONE op (rows kernel + weight-gradient kernels): SURVEY 8d's 5*d*b per row over their summed time
-        if "k1_bwd_rows" in agg and "k1_bwd_wgrad" in agg:
-            a, w = agg["k1_bwd_rows"], agg["k1_bwd_wgrad"]
-            op_us = a["total_us"] + w["total_us"] + (agg["k1_bwd_fin"]["total_us"] if "k1_bwd_fin" in agg else 0.0)
-            gbps = 5 * d * esz * a["rows"] / op_us / 1e3
-            kernels["k1_bwd_op"] = dict(launches=a["launches"], avg_us=round(op_us / a["launches"], 2),
-                                        total_ms=round(op_us / 1e3, 3), algorithmic_GBps=round(gbps, 1),
-                                        hbm_frac=round(gbps / HBM_PEAK_GBS, 4),
-                                        note=(("pass 1 + column-parallel pass + finalize launch" if "k1_bwd_fin" in agg else
-                                               "pass 1 + column-parallel pass (weight gradients reduced in-launch)") + " of one K1 backward, 5*d*b per row" if two_pass
-                                              else "rows kernel + weight-gradient kernels of one K1 backward, 5*d*b per row"))
-        # dominant HIP kernel of the hot path by time
-        if args.model == "lora":
-            dom = "k3_bwd" if "k3_bwd" in agg else "k3_fwd"
-        else:
-            dom = ("k1_bwd_wgrad" if two_pass and "k1_bwd_wgrad" in agg else "k1_bwd_rows") if "k1_bwd_rows" in agg else "k1_fwd"
-        a = agg[dom]
-        kernel_achieved = per_row[dom] * a["rows"] / a["total_us"] / 1e3     # GB/s of the dominant kernel alone
-        tiles = 6 if args.model == "t5" else 3
-        lora_drop = args.model == "lora" and float(getattr(cfg, "lora_dropout", 0.0) or 0.0) > 0.0
-        kname = {"k1_bwd_rows": (f"k1_dz2_kernel<{tiles}>" if two_pass and tiles <= 3 else
-                                 f"pet_gate_dz_kernel<{args.dtype},{tiles}>" if two_pass else
-                                 f"pet_gate_bwd2_kernel<{args.dtype},{tiles}>" if tiles <= 3 else f"pet_bwd_kernel<{args.dtype},{tiles},gate>"),
-                 "k1_bwd_wgrad": (f"k1_cols_kernel<{tiles}>" if tiles <= 3 else "k1_cols6_kernel<6>") +
-                                 " (column-parallel pass of the K1 backward: reads dy, x1, x2, writes dx1, dx2)",
-                 "k1_fwd": f"pet_gate_fwd_kernel<{args.dtype},{tiles}> / k1_down_kernel + k1_up_kernel (by shape)",
-                 "k3_bwd": ("ng_dz_kernel + ng_cols_kernel<drop> + wgrad_finalize_kernel" if lora_drop else
-                            "ng_dz_kernel + ng_cols_kernel + wgrad_finalize_kernel") + " (one K3 backward, two-pass form of csrc/pet_cols_ng.hip)",
-                 "k3_fwd": f"pet_fwd_kernel<{args.dtype},act_id{',drop' if lora_drop else ''}>"}[dom]
-        traffic = None
-        PMC_TRAFFIC = PMC_TRAFFIC_FORMS[("two_pass_t5" if args.model == "t5" else "two_pass") if (args.model != "lora" and two_pass)
-                                        else "previous_split"]
-        def pmc_avg(group):          # average PMC bytes per launch over THIS run's launch sizes
-            tab = PMC_TRAFFIC["bytes_by_rows"][group]
-            br = a["by_rows"]
-            return round(sum(pmc_bytes(tab, m) * c[0] for m, c in br.items()) / max(1, sum(c[0] for c in br.values())))
-        if dom in PMC_TRAFFIC["bytes_by_rows"] and args.dtype == "bf16" and args.model in ("bart", "t5", "video"):
-            traffic = pmc_avg(dom)
-        # Headline fraction = the whole K1 backward OP (SURVEY 8d's 5*d*b per row is the op's byte count; the op is three launches):
-        # algorithmic bytes / (pass 1 + column-parallel pass + finalize).  The dominant kernel's own figures stay beside it.
-        op = kernels.get("k1_bwd_op") if dom in ("k1_bwd_rows", "k1_bwd_wgrad") else None
-        if op is not None:
-            achieved, launch_us, what = op["algorithmic_GBps"], op["avg_us"], "K1 backward op = " + \
-                (("pass 1 + column-parallel pass + finalize launch" if "k1_bwd_fin" in agg else
-                  "pass 1 + column-parallel pass (in-launch reduce-scatter where M >= 8192, finalize launch below)") if two_pass
-                 else "rows kernel + weight-gradient kernels")
-            algo_row = 5 * d * esz
-            if traffic:
-                traffic = pmc_avg("k1_bwd_op")
-        else:
-            achieved, launch_us, what, algo_row = kernel_achieved, a["total_us"] / a["launches"], kname, per_row[dom]
-        roof = dict(bound="hbm", kernel=what, achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s",
-                    frac=round(achieved / HBM_PEAK_GBS, 4), traffic=traffic,
-                    traffic_source=(f"{PMC_TRAFFIC['source']}: PMC passes at M = {PMC_TRAFFIC['measured_at_rows']}, interpolated per launch "
-                                    f"over this run's launch sizes") if traffic else None,
-                    avg_launch_us=round(launch_us, 2),
-                    avg_rows_per_launch=round(a["rows"] / a["launches"], 1),
-                    algorithmic_bytes_per_row=algo_row,
-                    dominant_kernel=dict(name=kname, avg_launch_us=round(a["total_us"] / a["launches"], 2),
-                                         achieved=round(kernel_achieved, 1), frac=round(kernel_achieved / HBM_PEAK_GBS, 4),
-                                         note="the op's algorithmic bytes over this ONE launch's time (the pre-round-4 headline)"))
-        if op is not None:
-            roof["op_frac"] = op["hbm_frac"]
-            roof["op_avg_us"] = op["avg_us"]
+        if args.full:
+            agg = timer.summary()
+            if table_timer is not None:                 # the other launch groups: one step per task after the timed region
+                for name, a in table_timer.summary().items():
+                    agg.setdefault(name, a)
+            roof, kernels = kernel_report(args, cfg, dtype, agg)
         per_task = {t: TR.TASK_BATCH[t](args.batch) for t in tasks}
         enc_rows = {t: rank_batch(t) * (TR.TEXT_LEN[t] + (72 if t == "nlvr" else (64 if t in VIDEO_TASKS else 36))) for t in tasks}
         out = {
@@ -732,7 +756,8 @@ def main():
                                {t: rank_batch(t) for t in tasks}, settling, n_ranks),
             "peak_memory_GB": peak_gb,
             **({"eager_region": eager_region} if eager_region else {}),
-            "roofline": roof, "kernels": kernels, "backbone_gemm_table": gemm_table,
+            **({"roofline": roof, "kernels": kernels} if args.full else {}),
+            "backbone_gemm_table": gemm_table,
             **({"ab_switches": ab_switches} if ab_switches else {}),
             **({"other_scaling": strong} if strong is not None else {}),
             **({"emulated_ranks": {"ranks": args.emulate_ranks, "estimate_samples_per_s_all_ranks": round(samples / dt * args.emulate_ranks, 2),
@@ -747,17 +772,18 @@ def main():
                if args.emulate_ranks > 1 else {}),
             "step_mode": (f"hipGraph replay: forward + loss + backward captured once per task shape (train.Trainer(graph=True); {setup_steps} "
                           "untimed setup steps before the warm-up; the batches live in the captured steps' input buffers, Trainer.input_buffers), "
-                          "gradient exchange + clip + AdamW eager; roofline brackets from the "
-                          "same K steps run eagerly right after the timed region (eager_region)") if graph_on
+                          "gradient exchange + clip + AdamW eager" + ("; roofline brackets from the same K steps run eagerly right after the "
+                                                                      "timed region (eager_region)" if args.full else "")) if graph_on
                          else f"eager launches (roofline op bracketed inside the timed region; {setup_steps} untimed setup steps, one per task shape, before the warm-up)",
             "attention_mask": ("default input_ids.ne(pad) mask built and applied every step, as the reference does" if args.pad_mask
                                else "none built (--no-pad-mask: the synthetic rows carry no padding)"),
-            "kernel_table": {"after": ("roofline op bracketed in the eager region (the timed region's K steps again, eager); " if graph_on
-                                       else "roofline op bracketed inside the timed region; ") + "the other launch groups in one step per task after it",
-                             "inline": "every launch group bracketed inside the " + ("eager region" if graph_on else "timed region"),
-                             "off": "roofline op only"}[args.kernel_table],
         }
-        if n_ranks == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out["kernel_table"] = {"after": ("roofline op bracketed in the eager region (the timed region's K steps again, eager); " if graph_on
+                                             else "roofline op bracketed inside the timed region; ") + "the other launch groups in one step per task after it",
+                                   "inline": "every launch group bracketed inside the " + ("eager region" if graph_on else "timed region"),
+                                   "off": "roofline op only"}[args.kernel_table]
+        if args.full and n_ranks == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

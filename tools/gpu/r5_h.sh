@@ -6,7 +6,7 @@ timeout 900 python -m pytest tests/test_gpu_act.py tests/test_gpu_attention.py t
 for rep in 1 2; do
 for lib in pre new; do
   if [ $lib = pre ]; then export VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_pre.so; else unset VLPET_LIB; fi
-  timeout 600 python bench.py --steps 16 --warmup 4 --no-cpu-baseline > $O/bench_bart_${lib}_$rep.json.log 2>&1
+  timeout 600 python bench.py --full --steps 16 --warmup 4 --no-cpu-baseline > $O/bench_bart_${lib}_$rep.json.log 2>&1
   python - $O/bench_bart_${lib}_$rep.json.log $lib <<'PY'
 import json,sys
 l=[x for x in open(sys.argv[1]).read().splitlines() if x.startswith("{")]

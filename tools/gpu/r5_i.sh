@@ -11,7 +11,7 @@ done; done 2>&1 | tee $O/k1bench_cold.txt
 for rep in 1 2; do
 for lib in head p1aux0; do
   if [ $lib = p1aux0 ]; then export VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_p1aux0.so; else unset VLPET_LIB; fi
-  timeout 600 python bench.py --steps 16 --warmup 4 --no-cpu-baseline > $O/bench_bart_${lib}_$rep.json.log 2>&1
+  timeout 600 python bench.py --full --steps 16 --warmup 4 --no-cpu-baseline > $O/bench_bart_${lib}_$rep.json.log 2>&1
   python - $O/bench_bart_${lib}_$rep.json.log $lib <<'PY'
 import json,sys
 l=[x for x in open(sys.argv[1]).read().splitlines() if x.startswith("{")]

@@ -8,7 +8,7 @@ for v in head nofuse noboth; do
   unset VLPET_NO_TAIL_NORM_FUSION VLPET_NO_ALIAS_RESIDUAL_GRAD
   if [ $v = nofuse ]; then export VLPET_NO_TAIL_NORM_FUSION=1; fi
   if [ $v = noboth ]; then export VLPET_NO_TAIL_NORM_FUSION=1 VLPET_NO_ALIAS_RESIDUAL_GRAD=1; fi
-  VLPET_AB=1 timeout 600 python bench.py --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5_${v}_$rep.json.log 2>&1
+  VLPET_AB=1 timeout 600 python bench.py --full --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5_${v}_$rep.json.log 2>&1
   python - $O/bench_t5_${v}_$rep.json.log $v <<'PY'
 import json,sys
 l=[x for x in open(sys.argv[1]).read().splitlines() if x.startswith("{")]

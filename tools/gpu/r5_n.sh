@@ -20,10 +20,10 @@ for cap in 128 256 512 1024; do
   VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so VLPET_DBG=$cap python tools/k5abi.py 500 1000 2000 3500 5000 6000 8000 2>&1 | cut -c1-420 | tee -a $O/k5abi_small.txt
 done
 for rep in 1 2; do
-  timeout 600 python bench.py --steps 16 --warmup 5 --no-cpu-baseline > $O/bench_bart_y_$rep.json.log 2>&1
-  VLPET_AB=1 VLPET_K1_BWD_FROM_X2=1 timeout 600 python bench.py --steps 16 --warmup 5 --no-cpu-baseline > $O/bench_bart_x2_$rep.json.log 2>&1
-  timeout 600 python bench.py --model t5 --steps 10 --warmup 4 --no-cpu-baseline > $O/bench_t5_y_$rep.json.log 2>&1
-  VLPET_AB=1 VLPET_K1_BWD_FROM_X2=1 timeout 600 python bench.py --model t5 --steps 10 --warmup 4 --no-cpu-baseline > $O/bench_t5_x2_$rep.json.log 2>&1
+  timeout 600 python bench.py --full --steps 16 --warmup 5 --no-cpu-baseline > $O/bench_bart_y_$rep.json.log 2>&1
+  VLPET_AB=1 VLPET_K1_BWD_FROM_X2=1 timeout 600 python bench.py --full --steps 16 --warmup 5 --no-cpu-baseline > $O/bench_bart_x2_$rep.json.log 2>&1
+  timeout 600 python bench.py --full --model t5 --steps 10 --warmup 4 --no-cpu-baseline > $O/bench_t5_y_$rep.json.log 2>&1
+  VLPET_AB=1 VLPET_K1_BWD_FROM_X2=1 timeout 600 python bench.py --full --model t5 --steps 10 --warmup 4 --no-cpu-baseline > $O/bench_t5_x2_$rep.json.log 2>&1
 done
 python - <<'P'
 import json, glob

@@ -10,10 +10,10 @@ for r in 96 192; do
   SZ="3500 8232 28000"; [ $r = 192 ] && SZ="2128 18250 28000"
   K1BENCH_R=$r python tools/k1bench.py head $SZ 2>&1 | grep -v amdgpu.ids | tee -a $O/k1bench.txt
 done
-timeout 600 python bench.py --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_bart.json.log 2>&1
-timeout 600 python bench.py --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5.json.log 2>&1
-timeout 600 python bench.py --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_bart_rank1of8.json.log 2>&1
-timeout 600 python bench.py --model t5 --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_t5_rank1of8.json.log 2>&1
+timeout 600 python bench.py --full --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_bart.json.log 2>&1
+timeout 600 python bench.py --full --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5.json.log 2>&1
+timeout 600 python bench.py --full --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_bart_rank1of8.json.log 2>&1
+timeout 600 python bench.py --full --model t5 --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_t5_rank1of8.json.log 2>&1
 python - <<'P' | tee gpurun_out/r5p/summary.txt
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r5p/bench_*.json.log")):

@@ -13,10 +13,10 @@ done
 for rep in 1 2; do
   for m in bart t5; do
     extra=""; [ $m = t5 ] && extra="--model t5"
-    timeout 600 python bench.py $extra --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_${m}_defer_$rep.json.log 2>&1
-    VLPET_AB=1 VLPET_NO_DEFER_FINALIZE=1 timeout 600 python bench.py $extra --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_${m}_nodefer_$rep.json.log 2>&1
-    timeout 600 python bench.py $extra --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_${m}_rank1of8_defer_$rep.json.log 2>&1
-    VLPET_AB=1 VLPET_NO_DEFER_FINALIZE=1 timeout 600 python bench.py $extra --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_${m}_rank1of8_nodefer_$rep.json.log 2>&1
+    timeout 600 python bench.py --full $extra --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_${m}_defer_$rep.json.log 2>&1
+    VLPET_AB=1 VLPET_NO_DEFER_FINALIZE=1 timeout 600 python bench.py --full $extra --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_${m}_nodefer_$rep.json.log 2>&1
+    timeout 600 python bench.py --full $extra --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_${m}_rank1of8_defer_$rep.json.log 2>&1
+    VLPET_AB=1 VLPET_NO_DEFER_FINALIZE=1 timeout 600 python bench.py --full $extra --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_${m}_rank1of8_nodefer_$rep.json.log 2>&1
   done
 done
 python - <<'P' | tee gpurun_out/r5q/summary.txt

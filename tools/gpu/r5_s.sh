@@ -10,8 +10,8 @@ for rep in 1 2; do
   done
   K1BENCH_COLD=1 K1BENCH_R=192 python tools/k1bench.py head 18250 2>&1 | grep -v amdgpu.ids | tee -a $O/k1bench_dz6.txt
   VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dz6_serial.so K1BENCH_COLD=1 K1BENCH_R=192 python tools/k1bench.py head_dz6_serial 18250 2>&1 | grep -v amdgpu.ids | tee -a $O/k1bench_dz6.txt
-  timeout 600 python bench.py --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5_$rep.json.log 2>&1
-  VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dz6_serial.so timeout 600 python bench.py --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5_serial_$rep.json.log 2>&1
+  timeout 600 python bench.py --full --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5_$rep.json.log 2>&1
+  VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dz6_serial.so timeout 600 python bench.py --full --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5_serial_$rep.json.log 2>&1
 done
 python - <<'P' | tee gpurun_out/r5s/summary.txt
 import json, glob

@@ -11,8 +11,8 @@ for rep in 1 2; do
   done
   VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so VLPET_COLS6Y=1 K1BENCH_COLD=1 K1BENCH_R=192 python tools/k1bench.py "cols6y=1" 18250 2>&1 | grep -v amdgpu.ids | tee -a $O/k1bench.txt
   VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so VLPET_COLS6Y=0 K1BENCH_COLD=1 K1BENCH_R=192 python tools/k1bench.py "cols6y=0" 18250 2>&1 | grep -v amdgpu.ids | tee -a $O/k1bench.txt
-  timeout 600 python bench.py --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5_$rep.json.log 2>&1
-  VLPET_AB=1 VLPET_K1_BWD_FROM_X2=1 timeout 600 python bench.py --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5_x2_$rep.json.log 2>&1
+  timeout 600 python bench.py --full --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5_$rep.json.log 2>&1
+  VLPET_AB=1 VLPET_K1_BWD_FROM_X2=1 timeout 600 python bench.py --full --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5_x2_$rep.json.log 2>&1
 done
 python - <<'P' | tee gpurun_out/r5t/summary.txt
 import json, glob

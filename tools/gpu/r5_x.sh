@@ -10,8 +10,8 @@ for rep in 1 2; do
       VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so VLPET_LORA8_BWD=$v python tools/k3bench.py $M 2>&1 | grep -v amdgpu.ids | grep -E "^r=   8" | cut -c1-260 | tee -a $O/k3bench.txt
     done
   done
-  timeout 600 python bench.py --model lora --lora-r 8 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_lora8_$rep.json.log 2>&1
-  VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so VLPET_LORA8_BWD=0 timeout 600 python bench.py --model lora --lora-r 8 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_lora8_mfma_bwd_$rep.json.log 2>&1
+  timeout 600 python bench.py --full --model lora --lora-r 8 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_lora8_$rep.json.log 2>&1
+  VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so VLPET_LORA8_BWD=0 timeout 600 python bench.py --full --model lora --lora-r 8 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_lora8_mfma_bwd_$rep.json.log 2>&1
 done
 python - <<'P' | tee gpurun_out/r5x/summary.txt
 import json, glob

@@ -10,8 +10,8 @@ for rep in 1 2; do
   done
   VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so VLPET_COLSY=1 K1BENCH_COLD=1 python tools/k1bench.py "colsy=1" 28000 2>&1 | grep -v amdgpu.ids | tee -a $O/k1bench.txt
   VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so VLPET_COLSY=0 K1BENCH_COLD=1 python tools/k1bench.py "colsy=0" 28000 2>&1 | grep -v amdgpu.ids | tee -a $O/k1bench.txt
-  timeout 600 python bench.py --steps 16 --warmup 5 --no-cpu-baseline > $O/bench_bart_$rep.json.log 2>&1
-  VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so VLPET_COLSY=0 timeout 600 python bench.py --steps 16 --warmup 5 --no-cpu-baseline > $O/bench_bart_cols_$rep.json.log 2>&1
+  timeout 600 python bench.py --full --steps 16 --warmup 5 --no-cpu-baseline > $O/bench_bart_$rep.json.log 2>&1
+  VLPET_LIB=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so VLPET_COLSY=0 timeout 600 python bench.py --full --steps 16 --warmup 5 --no-cpu-baseline > $O/bench_bart_cols_$rep.json.log 2>&1
 done
 python - <<'P' | tee gpurun_out/r5ze/summary.txt
 import json, glob

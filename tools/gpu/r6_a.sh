@@ -3,7 +3,7 @@
 O=gpurun_out/r6a; mkdir -p $O
 export HIP_FORCE_DEV_KERNARG=1
 timeout 900 python -m pytest tests/test_gpu_k4.py -x -q 2>&1 | tail -15 | tee $O/pytest_k4.txt
-timeout 600 python bench.py --steps 20 --warmup 4 > $O/bench_bart.json.log 2>&1
+timeout 600 python bench.py --full --steps 20 --warmup 4 > $O/bench_bart.json.log 2>&1
 python - <<'P' | tee $O/summary.txt
 import json
 for l in open("gpurun_out/r6a/bench_bart.json.log"):

@@ -6,7 +6,7 @@ export HIP_FORCE_DEV_KERNARG=1
 timeout 1500 python -m pytest tests/test_gpu_cols.py tests/test_gpu_ng.py tests/test_gpu_kernels.py tests/test_gpu_fullsize.py -x -q 2>&1 | tail -8 | tee $O/pytest.txt
 DBG=$PWD/vl-pet_amd/lib/libvlpet_hip_dbg.so
 for arm in 1 0 0 1; do
-  VLPET_LIB=$DBG VLPET_COLS_RED=$arm timeout 600 python bench.py --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_red${arm}_$RANDOM.json.log 2>&1
+  VLPET_LIB=$DBG VLPET_COLS_RED=$arm timeout 600 python bench.py --full --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_red${arm}_$RANDOM.json.log 2>&1
 done
 python - <<'P' | tee $O/summary.txt
 import json, glob

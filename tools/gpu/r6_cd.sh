@@ -5,9 +5,9 @@ export HIP_FORCE_DEV_KERNARG=1
 timeout 1500 python -m pytest tests/test_gpu_act.py tests/test_host_golden.py tests/test_gpu_graph.py tests/test_gpu_modules.py tests/test_gpu_dp.py tests/test_gpu_crosskeys.py tests/test_gpu_video.py -q -x 2>&1 | grep -v amdgpu.ids | tail -8 | tee $O/pytest.txt
 for tag in cd_a nocd_a nocd_b cd_b; do
   case $tag in nocd*) export VLPET_NO_CONCAT_DROPOUT=1;; *) unset VLPET_NO_CONCAT_DROPOUT;; esac
-  VLPET_AB=1 timeout 600 python bench.py --steps 40 --warmup 4 --no-cpu-baseline > $O/bench_$tag.json.log 2>&1
-  VLPET_AB=1 timeout 600 python bench.py --model t5 --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_t5_$tag.json.log 2>&1
-  VLPET_AB=1 timeout 600 python bench.py --emulate-ranks 8 --steps 40 --warmup 6 --no-cpu-baseline > $O/bench_r8_$tag.json.log 2>&1
+  VLPET_AB=1 timeout 600 python bench.py --full --steps 40 --warmup 4 --no-cpu-baseline > $O/bench_$tag.json.log 2>&1
+  VLPET_AB=1 timeout 600 python bench.py --full --model t5 --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_t5_$tag.json.log 2>&1
+  VLPET_AB=1 timeout 600 python bench.py --full --emulate-ranks 8 --steps 40 --warmup 6 --no-cpu-baseline > $O/bench_r8_$tag.json.log 2>&1
 done
 unset VLPET_NO_CONCAT_DROPOUT
 python - <<'P' | tee $O/summary.txt

@@ -6,10 +6,10 @@ export HIP_FORCE_DEV_KERNARG=1
 timeout 1500 python -m pytest tests/test_gpu_cols.py tests/test_gpu_k4.py tests/test_gpu_ng.py tests/test_gpu_kernels.py tests/test_gpu_fullsize.py tests/test_gpu_graph.py tests/test_gpu_dp.py -x -q -s 2>&1 | grep -v amdgpu.ids | grep -E "held|passed|failed|Error|error|assert" | tail -20 | tee $O/pytest.txt
 timeout 200 python tools/held_probe.py 2>&1 | grep -v amdgpu.ids | tee $O/held_probe.txt
 for arm in 0 1 1 0; do
-  VLPET_AB=1 VLPET_FINALIZE_LAUNCH=$arm timeout 600 python bench.py --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_full_fin${arm}_$RANDOM.json.log 2>&1
+  VLPET_AB=1 VLPET_FINALIZE_LAUNCH=$arm timeout 600 python bench.py --full --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_full_fin${arm}_$RANDOM.json.log 2>&1
 done
 for arm in 0 1 1 0; do
-  VLPET_AB=1 VLPET_FINALIZE_LAUNCH=$arm timeout 600 python bench.py --emulate-ranks 8 --steps 24 --warmup 6 --no-cpu-baseline > $O/bench_rank8_fin${arm}_$RANDOM.json.log 2>&1
+  VLPET_AB=1 VLPET_FINALIZE_LAUNCH=$arm timeout 600 python bench.py --full --emulate-ranks 8 --steps 24 --warmup 6 --no-cpu-baseline > $O/bench_rank8_fin${arm}_$RANDOM.json.log 2>&1
 done
 python - <<'P' | tee $O/summary.txt
 import json, glob

@@ -4,8 +4,8 @@ O=gpurun_out/r6e; mkdir -p $O
 export HIP_FORCE_DEV_KERNARG=1
 timeout 2700 python -m pytest tests -m gpu -q -x 2>&1 | grep -v amdgpu.ids | tail -25 | tee $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -3 | tee $O/smoke.txt
-timeout 600 python bench.py --steps 20 --warmup 4 > $O/bench_bart.json.log 2>&1
-timeout 600 python bench.py --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5.json.log 2>&1
+timeout 600 python bench.py --full --steps 20 --warmup 4 > $O/bench_bart.json.log 2>&1
+timeout 600 python bench.py --full --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5.json.log 2>&1
 python - <<'P' | tee $O/summary.txt
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r6e/bench_*.json.log")):

@@ -5,14 +5,14 @@ O=gpurun_out/r6f; mkdir -p $O
 export HIP_FORCE_DEV_KERNARG=1
 timeout 2700 python -m pytest tests -m gpu -q 2>&1 | grep -v amdgpu.ids | tail -12 | tee $O/pytest_gpu.txt
 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -3 | tee $O/smoke.txt
-timeout 600 python bench.py --steps 20 --warmup 4 > $O/bench_bart.json.log 2>&1
-timeout 600 python bench.py --graph off --steps 20 --warmup 4 --no-cpu-baseline > $O/bench_bart_eager.json.log 2>&1
-timeout 600 python bench.py --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5.json.log 2>&1
-timeout 600 python bench.py --model lora --steps 20 --warmup 4 --no-cpu-baseline > $O/bench_lora.json.log 2>&1
-timeout 600 python bench.py --model lora --lora-r 8 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_lora_r8.json.log 2>&1
-timeout 600 python bench.py --model video --steps 8 --warmup 3 --no-cpu-baseline > $O/bench_video.json.log 2>&1
-timeout 600 python bench.py --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_bart_rank1of8.json.log 2>&1
-timeout 600 python bench.py --model t5 --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_t5_rank1of8.json.log 2>&1
+timeout 600 python bench.py --full --steps 20 --warmup 4 > $O/bench_bart.json.log 2>&1
+timeout 600 python bench.py --full --graph off --steps 20 --warmup 4 --no-cpu-baseline > $O/bench_bart_eager.json.log 2>&1
+timeout 600 python bench.py --full --model t5 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_t5.json.log 2>&1
+timeout 600 python bench.py --full --model lora --steps 20 --warmup 4 --no-cpu-baseline > $O/bench_lora.json.log 2>&1
+timeout 600 python bench.py --full --model lora --lora-r 8 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_lora_r8.json.log 2>&1
+timeout 600 python bench.py --full --model video --steps 8 --warmup 3 --no-cpu-baseline > $O/bench_video.json.log 2>&1
+timeout 600 python bench.py --full --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_bart_rank1of8.json.log 2>&1
+timeout 600 python bench.py --full --model t5 --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_t5_rank1of8.json.log 2>&1
 python - <<'P' | tee $O/summary.txt
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r6f/bench_*.log")):

@@ -3,10 +3,10 @@
 O=gpurun_out/r6i; mkdir -p $O
 export HIP_FORCE_DEV_KERNARG=1
 timeout 1200 python -m pytest tests/test_gpu_lowrank.py tests/test_gpu_graph.py tests/test_gpu_k4.py tests/test_gpu_dp.py -q 2>&1 | grep -v amdgpu.ids | tail -6 | tee $O/pytest.txt
-timeout 600 python bench.py --model lora --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_lora.json.log 2>&1
-timeout 600 python bench.py --model lora --lora-r 8 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_lora_r8.json.log 2>&1
-timeout 600 python bench.py --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_bart_rank1of8.json.log 2>&1
-timeout 600 python bench.py --gpus 2 --backend gloo --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_bart_2ranks_gloo_1gpu.json.log 2>&1
+timeout 600 python bench.py --full --model lora --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_lora.json.log 2>&1
+timeout 600 python bench.py --full --model lora --lora-r 8 --steps 12 --warmup 4 --no-cpu-baseline > $O/bench_lora_r8.json.log 2>&1
+timeout 600 python bench.py --full --emulate-ranks 8 --steps 20 --warmup 6 --no-cpu-baseline > $O/bench_bart_rank1of8.json.log 2>&1
+timeout 600 python bench.py --full --gpus 2 --backend gloo --steps 6 --warmup 2 --no-cpu-baseline > $O/bench_bart_2ranks_gloo_1gpu.json.log 2>&1
 python - <<'P' | tee $O/summary.txt
 import json, glob
 for f in sorted(glob.glob("gpurun_out/r6i/bench_*.log")):

@@ -3,12 +3,12 @@
 # carries the roofline brackets): stability (three default runs + a 100-step run), the eager line beside it, rocprofv3 stats of the default command
 O=gpurun_out/r6n; mkdir -p $O
 export HIP_FORCE_DEV_KERNARG=1
-for i in 1 2 3; do timeout 600 python bench.py $( [ $i != 1 ] && echo --no-cpu-baseline ) > $O/bench_bart_$i.json.log 2>&1; done
-timeout 600 python bench.py --graph off --no-cpu-baseline > $O/bench_bart_eager.json.log 2>&1
-timeout 600 python bench.py --steps 100 --warmup 4 --no-cpu-baseline > $O/bench_bart_100.json.log 2>&1
-timeout 600 python bench.py --no-cpu-baseline > $O/bench_bart_4.json.log 2>&1
+for i in 1 2 3; do timeout 600 python bench.py --full $( [ $i != 1 ] && echo --no-cpu-baseline ) > $O/bench_bart_$i.json.log 2>&1; done
+timeout 600 python bench.py --full --graph off --no-cpu-baseline > $O/bench_bart_eager.json.log 2>&1
+timeout 600 python bench.py --full --steps 100 --warmup 4 --no-cpu-baseline > $O/bench_bart_100.json.log 2>&1
+timeout 600 python bench.py --full --no-cpu-baseline > $O/bench_bart_4.json.log 2>&1
 cd /tmp && export TMPDIR=/tmp
-timeout 900 rocprofv3 --kernel-trace --stats -d $GRAFT_REPO_ROOT/$O/prof -o bart -- python $GRAFT_REPO_ROOT/bench.py --no-cpu-baseline > $GRAFT_REPO_ROOT/$O/bench_bart_under_rocprofv3.json.log 2>&1
+timeout 900 rocprofv3 --kernel-trace --stats -d $OLDPWD/$O/prof -o bart -- python $OLDPWD/bench.py --full --no-cpu-baseline > $OLDPWD/$O/bench_bart_under_rocprofv3.json.log 2>&1
 cd $GRAFT_REPO_ROOT
 find $O/prof -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_bart.csv \;
 find $O/prof -type f ! -name "*kernel_stats.csv" -delete

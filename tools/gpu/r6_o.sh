@@ -6,11 +6,11 @@ export HIP_FORCE_DEV_KERNARG=1
 timeout 900 python -m pytest tests/test_gpu_k4.py tests/test_gpu_lowrank.py tests/test_host_golden.py -q -x 2>&1 | grep -v amdgpu.ids | tail -15 | tee $O/pytest_k4.txt
 for tag in pos_a nopos_a nopos_b pos_b; do
   case $tag in nopos*) export VLPET_NO_POS_KERNEL=1;; *) unset VLPET_NO_POS_KERNEL;; esac
-  VLPET_AB=1 timeout 600 python bench.py --steps 40 --warmup 4 --no-cpu-baseline > $O/bench_$tag.json.log 2>&1
+  VLPET_AB=1 timeout 600 python bench.py --full --steps 40 --warmup 4 --no-cpu-baseline > $O/bench_$tag.json.log 2>&1
 done
 unset VLPET_NO_POS_KERNEL
 for tag in gemm_a library_a library_b gemm_b; do
-  VLPET_AB=1 VLPET_K4_FORM=${tag%_*} timeout 600 python bench.py --steps 40 --warmup 4 --no-cpu-baseline > $O/bench_k4_$tag.json.log 2>&1
+  VLPET_AB=1 VLPET_K4_FORM=${tag%_*} timeout 600 python bench.py --full --steps 40 --warmup 4 --no-cpu-baseline > $O/bench_k4_$tag.json.log 2>&1
 done
 python - <<'P' | tee $O/summary.txt
 import json, glob

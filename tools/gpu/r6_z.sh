@@ -5,13 +5,13 @@ export HIP_FORCE_DEV_KERNARG=1
 timeout 1500 python -m pytest tests/test_gpu_fanout.py tests/test_host_golden.py tests/test_gpu_graph.py tests/test_gpu_modules.py tests/test_gpu_video.py tests/test_gpu_dp.py tests/test_host_caches.py -q -x 2>&1 | grep -v amdgpu.ids | tail -6 | tee $O/pytest.txt
 for tag in fan_a nofan_a nofan_b fan_b; do
   case $tag in nofan*) export VLPET_NO_FANOUT_SUM=1;; *) unset VLPET_NO_FANOUT_SUM;; esac
-  VLPET_AB=1 timeout 600 python bench.py --steps 40 --warmup 4 --no-cpu-baseline > $O/bench_$tag.json.log 2>&1
+  VLPET_AB=1 timeout 600 python bench.py --full --steps 40 --warmup 4 --no-cpu-baseline > $O/bench_$tag.json.log 2>&1
 done
 unset VLPET_NO_FANOUT_SUM
 for tag in fan_a nofan_a nofan_b fan_b; do
   case $tag in nofan*) export VLPET_NO_FANOUT_SUM=1;; *) unset VLPET_NO_FANOUT_SUM;; esac
-  VLPET_AB=1 timeout 600 python bench.py --model t5 --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_t5_$tag.json.log 2>&1
-  VLPET_AB=1 timeout 600 python bench.py --emulate-ranks 8 --steps 40 --warmup 6 --no-cpu-baseline > $O/bench_r8_$tag.json.log 2>&1
+  VLPET_AB=1 timeout 600 python bench.py --full --model t5 --steps 24 --warmup 4 --no-cpu-baseline > $O/bench_t5_$tag.json.log 2>&1
+  VLPET_AB=1 timeout 600 python bench.py --full --emulate-ranks 8 --steps 40 --warmup 6 --no-cpu-baseline > $O/bench_r8_$tag.json.log 2>&1
 done
 python - <<'P' | tee $O/summary.txt
 import json, glob
