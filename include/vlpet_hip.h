@@ -620,6 +620,31 @@ int vlpet_adamw_step_sliced(float* p, float* g, float* m, float* v, const uint8_
                             const float* slice_bc, int variant, int zero_grad, float* norm_out,
                             vlpet_stream_t stream);
 
+/* ---- greedy generation: the two kernels of a cached decode step (csrc/decode.hip) --------------------------------------
+ * HF 4.2.1 greedy_search as the reference evaluates with it (src/multitask.py test_step -> generate(num_beams = 1)); host:
+ * vlpet_amd/decode.py, generate() of host/bart.py and host/t5.py.  Both launches allocate, copy and synchronise nothing.
+ *
+ * vlpet_attn_decode: o[b, h*D:(h+1)*D] = softmax(scale * q_bh . k_bhj + bias[h, j] (+ masked: excluded)) v_bhj over the keys j of
+ *   one query row per sequence.  q [B, H*D] (row stride ld_q: a q block of a fused q|k|v row), caches [B, Lk, H*D] with row strides
+ *   ld_k / ld_v and batch strides bs_k / bs_v (a cross-attention key cache may be a column block of the decoder's fused key
+ *   projection [B, Lk, n_layers * H*D]), o [B, H*D] (ld_o).  k_new / v_new [B, H*D] (row stride ld_new) given: written into cache
+ *   row `pos` (0 <= pos < Lk), keys 0..pos attended (self-attention step); NULL: keys 0..Lk-1.  key_mask [B, Lk] u8 (row stride
+ *   ld_mask, 0 = masked) and bias [H, Lk] fp32 (head stride ld_bias: T5's relative position bias row of the query position) are
+ *   optional.  D = 16 or 64, Lk <= 1024, io_dtype bf16 / fp32, softmax in fp32.  Tensor pointers 16-byte aligned, strides
+ *   multiples of 8 elements.
+ * vlpet_greedy_pick: per row b of logits [B, ld] (columns >= V ignored; ld >= V rounded up to 8, V <= 65536): ban eos while
+ *   pos + 1 < min_length, ban the tokens that would repeat an n-gram of ids[b, 0..pos] (n = no_repeat_ngram_size, 0 = off), take
+ *   the argmax (lowest index on ties), emit pad instead when unfinished[b] == 0, write ids[b, pos + 1] (int64, row stride ld_ids),
+ *   clear unfinished[b] when the token is eos, and add the row's unfinished flag to *counter (int32, zeroed by the caller once per
+ *   generate() call: one slot per step).  eos_token_id < 0: no eos (no ban, no pad, nothing finishes). */
+int vlpet_attn_decode(const void* q, int64_t ld_q, void* k_cache, void* v_cache, int64_t ld_k, int64_t bs_k, int64_t ld_v,
+                      int64_t bs_v, const void* k_new, const void* v_new, int64_t ld_new, int pos, const uint8_t* key_mask,
+                      int64_t ld_mask, const float* bias, int64_t ld_bias, void* o, int64_t ld_o, int B, int H, int D, int Lk,
+                      float scale, int io_dtype, vlpet_stream_t stream);
+int vlpet_greedy_pick(const void* logits, int64_t ld, int V, int64_t* ids, int64_t ld_ids, int pos, int* unfinished, int* counter,
+                      int B, int eos_token_id, int pad_token_id, int min_length, int no_repeat_ngram_size, int io_dtype,
+                      vlpet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,181 @@
+#!/usr/bin/env python3
+"""Greedy-generation speed at the evaluation shapes (BART-base VL-PET, configs[1], bf16): per-step ms and generated tokens/s of
+
+  hip      VLBart.generate: per-layer caches, decode.decode_attention / decode.greedy_pick on csrc/decode.hip
+  torch    the same cached loop on the torch forms (decode.EAGER, host.bart.EAGER_ATTENTION: SDPA, eager argmax + processors)
+  nocache  what a user writes without generate(): the training-path decoder re-run on the whole prefix at every step
+
+Every path runs max_length - 1 steps (min_length = max_length bans eos throughout).  Shapes: VQA (B = 500, S_enc = 20 + 36 = 56,
+max_length 20), caption (B = 416, S_enc = 40 + 36 = 76, max_length 40).
+
+    python tools/genbench.py [--shapes vqa caption] [--paths hip torch nocache] [--reps 3] [--out FILE]
+    python tools/genbench.py --stats kernel_stats.csv     # rocprofv3 --kernel-trace --stats output of a `--paths hip --reps 1`
+                                                          # run at the VQA shape -> both kernels' time against their bytes
+"""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+SHAPES = {"vqa": dict(task="vqa", B=500, max_length=20, S_enc=56), "caption": dict(task="caption", B=416, max_length=40, S_enc=76)}
+HBM = 8.0e12          # bytes/s: the HBM rate the repository's roofline figures use
+
+
+def decode_bytes(B, S_enc, E, n_layers, max_length, V, esz=2):
+    """algorithmic bytes of one generate() call: attention (q, K, V read, o written; self-attention keys 0..pos plus the appended
+    row written) and logits (one read of [B, V] per step)"""
+    steps = max_length - 1
+    cross = n_layers * steps * B * (2 * S_enc * E + 2 * E) * esz
+    selfa = n_layers * sum(B * (2 * (p + 1) * E + 2 * E + 2 * E) * esz for p in range(steps))
+    logits = steps * B * V * esz
+    return dict(attn=cross + selfa, attn_calls=2 * n_layers * steps, pick=logits, pick_calls=steps)
+
+
+def build(dev):
+    import torch
+    import vlpet_amd.host.bart as HB
+    import vlpet_amd.train as TR
+    torch.manual_seed(0)
+    cfg = HB.vlpet_config()
+    model = HB.VLBart(cfg)
+    TR.trainable_names(model, cfg)
+    model.to(dev)
+    TR.cast_frozen(model, torch.bfloat16)
+    return model.eval(), cfg
+
+
+def nocache_generate(model, ids, vis, task, max_length, eos, start):
+    import torch
+    import torch.nn.functional as F
+    from vlpet_amd.lmloss import _padded_head
+    with torch.no_grad():
+        enc, mask = model.model.encoder(ids, vis, None, task, False)
+        w = model.model.shared.weight
+        head = _padded_head(w, enc.dtype)
+        out = torch.full((ids.shape[0], 1), start, dtype=torch.long, device=ids.device)
+        for _ in range(max_length - 1):
+            h = model.model.decoder(out, enc, mask, task)[:, -1]
+            scores = F.linear(h, head)[:, :w.shape[0]].float()
+            scores[:, eos] = float("-inf")              # min_length = max_length
+            out = torch.cat([out, scores.argmax(-1, keepdim=True)], 1)
+        return out
+
+
+def run(args):
+    import torch
+    import vlpet_amd.decode as D
+    import vlpet_amd.host.bart as HB
+    import vlpet_amd.train as TR
+    dev = "cuda"
+    model, cfg = build(dev)
+    rows = []
+    for shape in args.shapes:
+        sh = SHAPES[shape]
+        gen = torch.Generator(device=dev).manual_seed(1)
+        b = TR.synthetic_batch(sh["task"], sh["B"], cfg, dev, gen, no_padding=False)
+        ids, vis, ml = b["input_ids"], b["vis_inputs"], sh["max_length"]
+        steps = ml - 1
+        with torch.no_grad():
+            for _ in range(2):
+                model.model.encoder(ids, vis, None, sh["task"], False)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(args.reps):
+                model.model.encoder(ids, vis, None, sh["task"], False)
+            torch.cuda.synchronize()
+            enc_ms = (time.perf_counter() - t) * 1e3 / args.reps
+        outs = {}
+        for path in args.paths:
+            def call():
+                if path == "nocache":
+                    return nocache_generate(model, ids, vis, sh["task"], ml, 2, cfg.decoder_start_token_id)
+                return model.generate(ids, vis, sh["task"], max_length=ml, min_length=ml)
+            saved = (D.EAGER, HB.EAGER_ATTENTION)
+            D.EAGER = HB.EAGER_ATTENTION = path == "torch"
+            try:
+                for _ in range(args.warmup):
+                    call()
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for _ in range(args.reps):
+                    out = call()
+                torch.cuda.synchronize()
+                ms = (time.perf_counter() - t) * 1e3 / args.reps
+            finally:
+                D.EAGER, HB.EAGER_ATTENTION = saved
+            outs[path] = out
+            assert out.shape == (sh["B"], ml), out.shape
+            row = dict(shape=shape, path=path, B=sh["B"], S_enc=sh["S_enc"], max_length=ml, total_ms=round(ms, 2),
+                       encoder_ms=round(enc_ms, 2), step_ms=round((ms - enc_ms) / steps, 3),
+                       tokens_per_s=round(sh["B"] * steps / (ms / 1e3), 1))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        if "hip" in outs:
+            for p, o in outs.items():       # bf16 paths may part ways where two logits are within rounding: report, do not fail
+                agree = float((o == outs["hip"]).float().mean())
+                print(json.dumps(dict(shape=shape, tokens_equal_to_hip=p, fraction=round(agree, 4))), flush=True)
+    return rows
+
+
+def table(rows):
+    lines = ["| shape | path | B | S_enc | max_length | total ms | encoder ms | ms / step | tokens / s |", "|---|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append(f"| {r['shape']} | {r['path']} | {r['B']} | {r['S_enc']} | {r['max_length']} | {r['total_ms']} | {r['encoder_ms']} | "
+                     f"{r['step_ms']} | {r['tokens_per_s']} |")
+    return "\n".join(lines)
+
+
+def stats(path, shape="vqa"):
+    """rocprofv3 kernel stats of one `--paths hip --reps 1 --warmup 0` run at ``shape``: time of each decode kernel against its bytes"""
+    sh = SHAPES[shape]
+    by = decode_bytes(sh["B"], sh["S_enc"], 768, 6, sh["max_length"], 50465)
+    tot = {}
+    with open(path) as f:
+        for r in csv.DictReader(f):
+            name = r.get("Name") or r.get("KernelName") or ""
+            for key, pat in (("attn", "attn_decode_kernel"), ("pick", "greedy_pick_kernel")):
+                if pat in name:
+                    t = tot.setdefault(key, [0, 0.0])
+                    t[0] += int(r["Calls"])
+                    t[1] += float(r["TotalDurationNs"])
+    out = []
+    for key in ("attn", "pick"):
+        if key not in tot:
+            continue
+        calls, ns = tot[key]
+        reps = max(1, round(calls / by[key + "_calls"]))
+        rate = by[key] * reps / (ns * 1e-9)
+        out.append(dict(kernel="vlpet_attn_decode" if key == "attn" else "vlpet_greedy_pick", calls=calls, total_us=round(ns / 1e3, 1),
+                        us_per_call=round(ns / 1e3 / calls, 2), algorithmic_MB_per_call=round(by[key] / by[key + "_calls"] / 1e6, 2),
+                        TB_per_s=round(rate / 1e12, 2), hbm_fraction=round(rate / HBM, 3)))
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", nargs="+", default=["vqa", "caption"], choices=list(SHAPES))
+    ap.add_argument("--paths", nargs="+", default=["hip", "torch", "nocache"], choices=["hip", "torch", "nocache"])
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--stats", default=None)
+    args = ap.parse_args()
+    if args.stats:
+        for r in stats(args.stats):
+            print(json.dumps(r))
+        return
+    rows = run(args)
+    text = table(rows)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()

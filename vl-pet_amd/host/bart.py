@@ -342,6 +342,40 @@ class BartAttention(nn.Module):
         return _linear(self.out_proj, out)
 
 
+    # ---- generate(): one decoder token against the caches (decode.decode_attention; the same projections as forward)
+    def _step_qkv(self, x, task):
+        """q, k, v rows [B, E] of one token x [B, 1, E]: the fused q|k|v GEMM (column blocks read in place), or the LoRA q / v path"""
+        if self.use_lora:
+            return self.q_proj(x, task)[:, 0], _linear(self.k_proj, x)[:, 0], self.v_proj(x, task)[:, 0]
+        if FUSE_QKV:
+            w, b = self._fused_qkv(x.dtype)
+            qkv = F.linear(x[:, 0], w, b)
+            E = self.embed_dim
+            return qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
+        return _linear(self.q_proj, x)[:, 0], _linear(self.k_proj, x)[:, 0], _linear(self.v_proj, x)[:, 0]
+
+    def step_self(self, x, k_cache, v_cache, pos, task=None):
+        """causal self-attention of the token at ``pos``: its key / value rows go into cache row ``pos`` inside the attention launch"""
+        from ..decode import decode_attention
+        q, k, v = self._step_qkv(x, task)
+        out = decode_attention(q, k_cache, v_cache, self.num_heads, pos=pos, k_new=k, v_new=v, scale=self.head_dim ** -0.5)
+        return _linear(self.out_proj, out[:, None])
+
+    def cross_values(self, enc, task=None):
+        """the cross-attention value cache: v_proj(enc) (K3 under LoRA), the value-parallel adapter (K2) applied once -- the reference
+        skips K2 on cached steps because the value it feeds is cached (my_transformers/modeling_bart.py:419-430)"""
+        v = self.v_proj(enc, task) if self.use_lora else _linear(self.v_proj, enc)
+        if self.attn_value_parallel_adapter is not None:
+            v = self.attn_value_parallel_adapter(enc, task, y=v)
+        return v
+
+    def step_cross(self, x, k_cache, v_cache, key_mask, task=None):
+        from ..decode import decode_attention
+        q = self.q_proj(x, task) if self.use_lora else _linear(self.q_proj, x)
+        out = decode_attention(q[:, 0], k_cache, v_cache, self.num_heads, key_mask=key_mask, scale=self.head_dim ** -0.5)
+        return _linear(self.out_proj, out[:, None])
+
+
 class BartEncoderLayer(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -410,6 +444,17 @@ class BartDecoderLayer(nn.Module):
         h = ffn_activation(_first_linear(self.fc1, hidden, gl), "gelu", self.activation_dropout, self.training)
         h = _linear(self.fc2, h)
         return _tail_linked(residual, h, self.final_layer_norm, self.dropout, self.training, gl)             # K5
+
+
+    def step(self, x, cache, pos, task=None):
+        """generate(): the token x [B, 1, d] at position ``pos``; ``cache`` = (self k, self v, cross k, cross v, cross key mask)"""
+        ks, vs, kx, vx, km = cache
+        h = self.self_attn.step_self(x, ks, vs, pos, task)
+        x = sublayer_tail(x, h, self.self_attn_layer_norm, self.dropout, self.training)                     # K5
+        h = self.encoder_attn.step_cross(x, kx, vx, km, task)
+        x = sublayer_tail(x, h, self.encoder_attn_layer_norm, self.dropout, self.training)                  # K5
+        h = ffn_activation(_linear(self.fc1, x), "gelu", self.activation_dropout, self.training)
+        return sublayer_tail(x, _linear(self.fc2, h), self.final_layer_norm, self.dropout, self.training)   # K5
 
 
 class LearnedPositionalEmbedding(nn.Embedding):
@@ -525,6 +570,28 @@ class BartDecoder(nn.Module):
         return VF.cross_key_blocks(enc, c[1], c[2], len(mods))
 
 
+    def init_cache(self, enc, key_mask, task, max_length):
+        """generate(): per layer a self-attention key / value cache [B, max_length, E] (one allocation) and the cross-attention
+        caches of ``enc``: keys as column blocks of ONE fused projection where the layers allow it, values through K2 / K3 once"""
+        B, _, E = enc.shape
+        n = len(self.layers)
+        selfc = enc.new_empty(n, 2, B, max_length, E)
+        if FUSE_CROSS_KEYS and not EAGER_ATTENTION and n >= 2 and enc.is_cuda:
+            ks = self._cross_keys(enc)[0]
+        else:
+            ks = [_linear(l.encoder_attn.k_proj, enc) for l in self.layers]
+        vs = [l.encoder_attn.cross_values(enc, task) for l in self.layers]
+        return [(selfc[i, 0], selfc[i, 1], ks[i], vs[i], key_mask) for i in range(n)]
+
+    def step(self, tok, pos, caches, task=None):
+        """generate(): hidden state [B, d] of the tokens ``tok`` [B] at position ``pos`` (learned position pos + 2)"""
+        x = self.embed_tokens(tok)[:, None] * self.embed_scale + self.embed_positions.weight[pos + 2]
+        x = F.dropout(self.layernorm_embedding(x), p=self.dropout, training=self.training)
+        for layer, c in zip(self.layers, caches):
+            x = layer.step(x, c, pos, task)
+        return x[:, 0]
+
+
 class VLBartModel(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -583,3 +650,36 @@ class VLBart(nn.Module):
         dec_in = shift_tokens_right(labels, cfg.pad_token_id, cfg.decoder_start_token_id)
         h = self.model.decoder(dec_in, enc, mask, task)
         return lm_loss(h, self.model.shared.weight, labels, self._logits_bias())
+
+    def generate(self, input_ids, vis_inputs, task, attention_mask=None, max_length=20, min_length=0, no_repeat_ngram_size=0,
+                 eos_token_id=None, pad_token_id=None, no_padding=False):
+        """Greedy search with HF 4.2.1 semantics (num_beams = 1; the reference's evaluation, src/multitask.py test_step) on a per-layer
+        key / value cache: the encoder runs once, every step feeds one token (vlpet_amd.decode).  Returns the token ids
+        [B, <= max_length], starting with decoder_start_token_id; finished rows are padded.  eos / pad default to the config's
+        (BART: 2 / 1).  Pass the checkpoint's own generation settings (min_length, no_repeat_ngram_size) explicitly."""
+        from ..decode import greedy_generate
+        from ..lmloss import _padded_head
+        cfg = self.config
+        eos = getattr(cfg, "eos_token_id", 2) if eos_token_id is None else eos_token_id
+        pad = cfg.pad_token_id if pad_token_id is None else pad_token_id
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                enc, mask = self.model.encoder(input_ids, vis_inputs, attention_mask, task, no_padding)
+                key_mask = None if mask is None else mask[:, 0, 0, :].contiguous()
+                dec = self.model.decoder
+                caches = dec.init_cache(enc, key_mask, task, max_length)
+                V = self.model.shared.weight.shape[0]
+                head = _padded_head(self.model.shared.weight, enc.dtype)
+                bias = self._logits_bias()
+
+                def step(tok, pos):
+                    logits = F.linear(dec.step(tok, pos, caches, task), head)
+                    if bias is not None:
+                        logits[:, :V] += bias[0].to(logits.dtype)
+                    return logits
+                return greedy_generate(step, V, enc.shape[0], enc.device, max_length, cfg.decoder_start_token_id, eos, pad,
+                                       min_length, no_repeat_ngram_size)
+        finally:
+            self.train(was_training)

@@ -328,6 +328,33 @@ class T5Attention(nn.Module):
         return _linear(self.o, out.transpose(1, 2).reshape(B, Lq, self.inner))
 
 
+    # ---- generate(): one decoder token against the caches (decode.decode_attention, scale 1: T5 has no 1/sqrt(d))
+    def step_self(self, n, k_cache, v_cache, pos, bias_row):
+        """causal self-attention of the normed token n [B, 1, d] at ``pos``; ``bias_row`` [H, >= pos + 1]: row ``pos`` of the
+        decoder's relative position bias"""
+        from ..decode import decode_attention
+        E = self.inner
+        if FUSE_QKV:
+            qkv = F.linear(n[:, 0], self._fused_qkv(n.dtype))
+            q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
+        else:
+            q, k, v = _linear(self.q, n)[:, 0], _linear(self.k, n)[:, 0], _linear(self.v, n)[:, 0]
+        out = decode_attention(q, k_cache, v_cache, self.n_heads, pos=pos, k_new=k, v_new=v, bias=bias_row, scale=1.0)
+        return _linear(self.o, out[:, None])
+
+    def cross_values(self, enc, task=None):
+        """the cross-attention value cache with the value-parallel adapter (K2) applied once (``project_vpa`` on the cached value)"""
+        v = _linear(self.v, enc)
+        if self.attn_value_parallel_adapter is not None:
+            v = self.attn_value_parallel_adapter(enc, task, y=v)
+        return v
+
+    def step_cross(self, n, k_cache, v_cache, key_mask):
+        from ..decode import decode_attention
+        out = decode_attention(_linear(self.q, n)[:, 0], k_cache, v_cache, self.n_heads, key_mask=key_mask, scale=1.0)
+        return _linear(self.o, out[:, None])
+
+
 class T5DenseReluDense(nn.Module):
     def __init__(self, config):
         super().__init__()
@@ -403,6 +430,19 @@ class T5Block(nn.Module):
         if self.is_decoder:
             hidden = self.layer[1](hidden, enc, cross_bias, task, k_pre=k_pre)
         return self.layer[-1](hidden, task)
+
+
+def _block_step(blk, x, cache, pos, bias_row):
+    """generate(): one decoder block on the token x [B, 1, d]; ``cache`` = (self k, self v, cross k, cross v, cross key mask).  The
+    tails are forward's (_tail_linked: on the GPU each fused with the next sublayer's norm)."""
+    sa, ca, ff = blk.layer[0], blk.layer[1], blk.layer[-1]
+    ks, vs, kx, vx, km = cache
+    y = sa.SelfAttention.step_self(sa.layer_norm(x), ks, vs, pos, bias_row)
+    x = _tail_linked(x, y, sa.p, sa.training, None, layer=sa)
+    y = ca.EncDecAttention.step_cross(ca.layer_norm(x), kx, vx, km)
+    x = _tail_linked(x, y, ca.p, ca.training, None, layer=ca)
+    y = ff.DenseReluDense(ff.layer_norm(x))
+    return _tail_linked(x, y, ff.p, ff.training, None, layer=ff)
 
 
 def _pad_bias(mask, dtype):
@@ -504,6 +544,32 @@ class T5Decoder(nn.Module):
         return F.dropout(self.final_layer_norm(x), p=self.p, training=self.training)
 
 
+    def init_cache(self, enc, key_mask, task, max_length):
+        """generate(): self-attention caches [B, max_length, inner] per block (one allocation), cross-attention caches of ``enc`` (keys
+        as column blocks of ONE fused projection on the GPU), and the relative position bias of every query position as a
+        [max_length, H, max_length] fp32 table (row ``pos`` = compute_bias(max_length, max_length)[0, :, pos])"""
+        B, _, _ = enc.shape
+        n = len(self.block)
+        inner = self.block[0].layer[0].SelfAttention.inner
+        selfc = enc.new_empty(n, 2, B, max_length, inner)
+        atts = [blk.layer[1].EncDecAttention for blk in self.block]
+        if FUSE_CROSS_KEYS and not EAGER_ATTENTION and n >= 2 and enc.is_cuda:
+            ks = self._cross_keys(enc)[0]
+        else:
+            ks = [_linear(a.k, enc) for a in atts]
+        vs = [a.cross_values(enc, task) for a in atts]
+        rel = self.block[0].layer[0].SelfAttention.compute_bias(max_length, max_length)[0]        # [H, q, k]
+        table = rel.permute(1, 0, 2).float().contiguous()
+        return [(selfc[i, 0], selfc[i, 1], ks[i], vs[i], key_mask) for i in range(n)], table
+
+    def step(self, tok, pos, state):
+        caches, table = state
+        x = F.dropout(self.embed_tokens(tok)[:, None], p=self.p, training=self.training)
+        for blk, c in zip(self.block, caches):
+            x = _block_step(blk, x, c, pos, table[pos])
+        return F.dropout(self.final_layer_norm(x), p=self.p, training=self.training)[:, 0]
+
+
 def shift_right(labels, pad_id, start_id):
     """T5PreTrainedModel._shift_right (my_transformers/modeling_t5.py:1068-1087)."""
     out = labels.new_zeros(labels.shape)
@@ -551,3 +617,30 @@ class VLT5(nn.Module):
         dec_in = shift_right(labels, cfg.pad_token_id, cfg.decoder_start_token_id)
         h = self.decoder(dec_in, enc, keep, task) * (cfg.d_model ** -0.5)
         return lm_loss(h, self.shared.weight, labels)
+
+    def generate(self, input_ids, vis_inputs, task, attention_mask=None, max_length=20, min_length=0, no_repeat_ngram_size=0,
+                 eos_token_id=None, pad_token_id=None, no_padding=False):
+        """Greedy search with HF 4.2.1 semantics on per-block key / value caches (see host/bart.py VLBart.generate).  eos / pad
+        default to T5's 1 / 0; the output starts with decoder_start_token_id (0)."""
+        from ..decode import greedy_generate
+        from ..lmloss import _padded_head
+        cfg = self.config
+        eos = getattr(cfg, "eos_token_id", 1) if eos_token_id is None else eos_token_id
+        pad = cfg.pad_token_id if pad_token_id is None else pad_token_id
+        was_training = self.training
+        self.eval()
+        try:
+            with torch.no_grad():
+                enc, keep = self.encoder(input_ids, vis_inputs, attention_mask, task)
+                key_mask = (keep > 0.5).contiguous()
+                state = self.decoder.init_cache(enc, key_mask, task, max_length)
+                V = self.shared.weight.shape[0]
+                head = _padded_head(self.shared.weight, enc.dtype)
+                scale = cfg.d_model ** -0.5
+
+                def step(tok, pos):
+                    return F.linear(self.decoder.step(tok, pos, state) * scale, head)
+                return greedy_generate(step, V, enc.shape[0], enc.device, max_length, cfg.decoder_start_token_id, eos, pad,
+                                       min_length, no_repeat_ngram_size)
+        finally:
+            self.train(was_training)
