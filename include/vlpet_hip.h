@@ -645,6 +645,44 @@ int vlpet_greedy_pick(const void* logits, int64_t ld, int V, int64_t* ids, int64
                       int B, int eos_token_id, int pad_token_id, int min_length, int no_repeat_ngram_size, int io_dtype,
                       vlpet_stream_t stream);
 
+/* ---- beam search: HF 4.2.1 beam_search, num_return_sequences = 1 (src/multitask_video.py: generate(num_beams = 5)) ----------
+ * Rows are B * K (K = num_beams), item-major: row r = item * K + beam.  Host: vlpet_amd/decode.py beam_generate / beam_step,
+ * generate(num_beams = K) of host/bart.py and host/t5.py.  No launch allocates, copies or synchronises.
+ *
+ * vlpet_attn_decode_beam: vlpet_attn_decode with two more arguments; the caches are never expanded or reordered.
+ *   group >= 1: query row r reads cache batch r / group and key-mask row r / group (the cross-attention caches of an item serve its
+ *   K beams).  key_rows (int32 [B, ld_key_rows >= number of keys], may be NULL): key j of query row r lives in cache batch
+ *   key_rows[r, j], row j (a value outside 0..B-1 reads batch r).  k_new / v_new still go to batch r, row pos; with them group
+ *   must be 1.  Errors as vlpet_attn_decode, group <= 0 or a short key_rows row: -1.
+ * vlpet_beam_rows: per row r of logits [rows, ld] (V <= 65536 columns count) and column slice s (grid slices x rows; a slice is
+ *   ceil(V / slices) rounded up to 8 columns): force_eos set -> every column but eos is -inf (BART at cur_len = max_length - 1);
+ *   part_stats[(r * slices + s) * 2 + {0, 1}] = (max, sum of exp(x - max)) over the slice's columns (the log-sum-exp before the
+ *   bans); part_val / part_tok[(r * slices + s) * 2K + j] = the slice's j-th best (logit, token) with eos banned while
+ *   pos + 1 < min_length and the no_repeat_ngram_size bans of ids[r, 0..pos] (int64, row stride ld_ids) at -inf; ties to the lower
+ *   token, missing entries (-inf, INT_MAX).  num_beams 2..8, slices 1..64, 0 <= eos < V.
+ * vlpet_beam_advance: one wave per item b < B (state[b * 3 + 2] = done: its rows are copied over, pad appended).  Per live item:
+ *   log-sum-exp of each of its K rows from the slices, score = logit - lse + beam_scores[r], the top 2K of the item's flat
+ *   [K * V] scores (ties to the lower flat index), then BeamSearchScorer.process: an eos candidate of rank < K becomes a
+ *   hypothesis (ids_in[src, 0..pos], score / (pos + 1) ** length_penalty; kept among the item's K best: hyp_score [B*K],
+ *   hyp_meta [B*K, 2] = (length, insertion number), hyp_tokens [B*K, ld_hyp] int64, item_worst [B] (1e9 at the start),
+ *   item_state [B, 3] = (count, insertions, done)), other candidates fill the K beam slots in rank order.  Writes the new
+ *   beam_scores, ids_out[r, 0..pos + 1] (the source row's ids, then the token), key_rows_out likewise with key_rows_out[r, pos + 1]
+ *   = r (both NULL or both given), next_tokens[r], and adds the number of items not done to *counter.  ids_in / ids_out and the
+ *   key-row tables are separate (ping-pong) buffers; pos + 1 < ld_ids, ld_hyp and ld_key_rows. */
+int vlpet_attn_decode_beam(const void* q, int64_t ld_q, void* k_cache, void* v_cache, int64_t ld_k, int64_t bs_k, int64_t ld_v,
+                           int64_t bs_v, const void* k_new, const void* v_new, int64_t ld_new, int pos, const uint8_t* key_mask,
+                           int64_t ld_mask, const float* bias, int64_t ld_bias, void* o, int64_t ld_o, int B, int H, int D,
+                           int Lk, float scale, int group, const int* key_rows, int64_t ld_key_rows, int io_dtype,
+                           vlpet_stream_t stream);
+int vlpet_beam_rows(const void* logits, int64_t ld, int V, const int64_t* ids, int64_t ld_ids, int pos, int rows, int num_beams,
+                    int slices, int eos_token_id, int min_length, int no_repeat_ngram_size, int force_eos, float* part_stats,
+                    float* part_val, int* part_tok, int io_dtype, vlpet_stream_t stream);
+int vlpet_beam_advance(const float* part_stats, const float* part_val, const int* part_tok, int slices, int V, int B, int num_beams,
+                       float* beam_scores, const int64_t* ids_in, int64_t* ids_out, int64_t ld_ids, const int* key_rows_in,
+                       int* key_rows_out, int64_t ld_key_rows, int64_t* next_tokens, float* hyp_score, int* hyp_meta,
+                       int64_t* hyp_tokens, int64_t ld_hyp, float* item_worst, int* item_state, int* counter, int pos,
+                       int eos_token_id, int pad_token_id, float length_penalty, int early_stopping, vlpet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -11,6 +11,11 @@ max_length 20), caption (B = 416, S_enc = 40 + 36 = 76, max_length 40).
     python tools/genbench.py [--shapes vqa caption] [--paths hip torch nocache] [--reps 3] [--out FILE]
     python tools/genbench.py --stats kernel_stats.csv     # rocprofv3 --kernel-trace --stats output of a `--paths hip --reps 1`
                                                           # run at the VQA shape -> both kernels' time against their bytes
+
+Beam search (``--num-beams K``, K > 1): generate(num_beams = K) at the video captioning shape (task tvc, encoder length 600 + 64 =
+664, max_length 20, every step run: min_length = max_length) for BART-base VL-PET on the video config (B = 50) and T5-base VL-PET
+(B = 30), hip against torch (decode.EAGER).  ``--stats FILE --num-beams K`` reads the kernel stats of a `--num-beams K --paths hip
+--reps 1 --warmup 0 --models bart` run.
 """
 import argparse
 import csv
@@ -36,13 +41,32 @@ def decode_bytes(B, S_enc, E, n_layers, max_length, V, esz=2):
     return dict(attn=cross + selfa, attn_calls=2 * n_layers * steps, pick=logits, pick_calls=steps)
 
 
-def build(dev):
+BEAM_SHAPES = {"bart": dict(task="tvc", B=50, max_length=20, S_enc=664), "t5": dict(task="tvc", B=30, max_length=20, S_enc=664)}
+
+
+def beam_bytes(B, K, S_enc, E, n_layers, max_length, V, esz=2):
+    """algorithmic bytes of one generate(num_beams = K) call: attention (cross caches read once per item -- never expanded --, the
+    self-attention keys of each of the B * K rows, q / o / appended rows), beam_rows (one read of the [B * K, V] logits per step plus
+    the partials) and beam_advance (the partials, the ids / key rows moved)"""
+    rows, steps = B * K, max_length - 1
+    cross = n_layers * steps * (B * 2 * S_enc * E + rows * 2 * E) * esz
+    selfa = n_layers * sum(rows * (2 * (p + 1) * E + 4 * E) * esz for p in range(steps))
+    return dict(attn=cross + selfa, attn_calls=2 * n_layers * steps, rows=steps * rows * V * esz, rows_calls=steps,
+                advance=sum(rows * (4 * 2 * K + 2 * 8 * (p + 2) + 2 * 4 * (p + 2)) for p in range(steps)), advance_calls=steps)
+
+
+def build(dev, kind="bart", video=False):
     import torch
     import vlpet_amd.host.bart as HB
     import vlpet_amd.train as TR
     torch.manual_seed(0)
-    cfg = HB.vlpet_config()
-    model = HB.VLBart(cfg)
+    if kind == "t5":
+        import vlpet_amd.host.t5 as HT
+        cfg = HT.vlt5_config(feat_dim=512, n_boxes=64, tasks="tvqa,how2qa,tvc,yc2c") if video else HT.vlt5_config()
+        model = HT.VLT5(cfg)
+    else:
+        cfg = HB.vlpet_config(feat_dim=512, n_boxes=64, tasks="tvqa,how2qa,tvc,yc2c") if video else HB.vlpet_config()
+        model = HB.VLBart(cfg)
     TR.trainable_names(model, cfg)
     model.to(dev)
     TR.cast_frozen(model, torch.bfloat16)
@@ -122,11 +146,94 @@ def run(args):
     return rows
 
 
+def run_beams(args):
+    import torch
+    import vlpet_amd.decode as D
+    import vlpet_amd.host.bart as HB
+    import vlpet_amd.train as TR
+    dev = "cuda"
+    rows = []
+    for kind in args.models:
+        sh = BEAM_SHAPES[kind]
+        model, cfg = build(dev, kind, video=True)
+        gen = torch.Generator(device=dev).manual_seed(1)
+        b = TR.synthetic_batch(sh["task"], sh["B"], cfg, dev, gen, no_padding=False)
+        ids, vis, ml = b["input_ids"], b["vis_inputs"], sh["max_length"]
+        enc_len = ids.shape[1] + vis[0].shape[1]
+        outs = {}
+        for path in args.paths:
+            if path == "nocache":
+                continue
+            def call():
+                return model.generate(ids, vis, sh["task"], max_length=ml, min_length=ml, num_beams=args.num_beams)
+            saved = (D.EAGER, HB.EAGER_ATTENTION)
+            D.EAGER = HB.EAGER_ATTENTION = path == "torch"
+            try:
+                for _ in range(args.warmup):
+                    call()
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                for _ in range(args.reps):
+                    out = call()
+                torch.cuda.synchronize()
+                ms = (time.perf_counter() - t) * 1e3 / args.reps
+            finally:
+                D.EAGER, HB.EAGER_ATTENTION = saved
+            outs[path] = out
+            row = dict(model=kind, path=path, num_beams=args.num_beams, B=sh["B"], enc_len=enc_len, max_length=ml,
+                       total_ms=round(ms, 2), step_ms=round(ms / (ml - 1), 3))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        if "hip" in outs and "torch" in outs:
+            o, h = outs["torch"], outs["hip"]
+            agree = float((o == h).float().mean()) if o.shape == h.shape else 0.0
+            print(json.dumps(dict(model=kind, tokens_equal_to_hip="torch", fraction=round(agree, 4))), flush=True)
+        del model
+        torch.cuda.empty_cache()
+    return rows
+
+
+def beam_stats(path, K):
+    """rocprofv3 kernel stats of one `--num-beams K --paths hip --reps 1 --warmup 0 --models bart` run: each kernel's time against
+    its algorithmic bytes"""
+    sh = BEAM_SHAPES["bart"]
+    by = beam_bytes(sh["B"], K, sh["S_enc"], 768, 6, sh["max_length"], 50465)
+    tot = {}
+    with open(path) as f:
+        for r in csv.DictReader(f):
+            name = r.get("Name") or r.get("KernelName") or ""
+            for key, pat in (("attn", "attn_decode_kernel"), ("rows", "beam_rows_kernel"), ("advance", "beam_advance_kernel")):
+                if pat in name:
+                    t = tot.setdefault(key, [0, 0.0])
+                    t[0] += int(r["Calls"])
+                    t[1] += float(r["TotalDurationNs"])
+    names = dict(attn="vlpet_attn_decode_beam", rows="vlpet_beam_rows", advance="vlpet_beam_advance")
+    out = []
+    for key in ("attn", "rows", "advance"):
+        if key not in tot:
+            continue
+        calls, ns = tot[key]
+        reps = max(1, round(calls / by[key + "_calls"]))
+        rate = by[key] * reps / (ns * 1e-9)
+        out.append(dict(kernel=names[key], calls=calls, total_us=round(ns / 1e3, 1), us_per_call=round(ns / 1e3 / calls, 2),
+                        algorithmic_MB_per_call=round(by[key] / by[key + "_calls"] / 1e6, 3), TB_per_s=round(rate / 1e12, 2),
+                        hbm_fraction=round(rate / HBM, 3)))
+    return out
+
+
 def table(rows):
     lines = ["| shape | path | B | S_enc | max_length | total ms | encoder ms | ms / step | tokens / s |", "|---|---|---|---|---|---|---|---|---|"]
     for r in rows:
         lines.append(f"| {r['shape']} | {r['path']} | {r['B']} | {r['S_enc']} | {r['max_length']} | {r['total_ms']} | {r['encoder_ms']} | "
                      f"{r['step_ms']} | {r['tokens_per_s']} |")
+    return "\n".join(lines)
+
+
+def beam_table(rows):
+    lines = ["| model | path | num_beams | B | encoder length | max_length | total ms | ms / step |", "|---|---|---|---|---|---|---|---|"]
+    for r in rows:
+        lines.append(f"| {r['model']} | {r['path']} | {r['num_beams']} | {r['B']} | {r['enc_len']} | {r['max_length']} | "
+                     f"{r['total_ms']} | {r['step_ms']} |")
     return "\n".join(lines)
 
 
@@ -164,13 +271,19 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
     ap.add_argument("--stats", default=None)
+    ap.add_argument("--num-beams", type=int, default=1)
+    ap.add_argument("--models", nargs="+", default=["bart", "t5"], choices=list(BEAM_SHAPES))
     args = ap.parse_args()
     if args.stats:
-        for r in stats(args.stats):
+        for r in (stats(args.stats) if args.num_beams == 1 else beam_stats(args.stats, args.num_beams)):
             print(json.dumps(r))
         return
-    rows = run(args)
-    text = table(rows)
+    if args.num_beams > 1:
+        rows = run_beams(args)
+        text = beam_table(rows)
+    else:
+        rows = run(args)
+        text = table(rows)
     print(text)
     if args.out:
         with open(args.out, "w") as f:

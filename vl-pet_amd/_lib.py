@@ -146,6 +146,14 @@ SIGNATURES = {
                                   c_int, c_float, c_int, c_void_p]),
     "vlpet_greedy_pick": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int,
                                   c_int, c_int, c_int, c_void_p]),
+    "vlpet_attn_decode_beam": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p,
+                                       c_void_p, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int,
+                                       c_int, c_int, c_int, c_float, c_int, c_void_p, c_int64, c_int, c_void_p]),
+    "vlpet_beam_rows": (c_int, [c_void_p, c_int64, c_int, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "vlpet_beam_advance": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
+                                   c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
     "vlpet_lora_delta_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_uint64, c_void_p, c_void_p,
                                      c_void_p, c_int, c_void_p, c_size_t, c_int64, c_int, c_int, c_float, c_int,
                                      c_void_p]),

@@ -22,11 +22,12 @@ from . import _lib
 from .functional import _io_dtype, _stream
 
 EAGER = False                   # A/B switch: the torch forms for every call (tools/genbench.py "torch cached")
-LAUNCHES = {"attn_decode": 0, "greedy_pick": 0}      # kernel launches so far (tests assert that a GPU run reached both kernels)
+LAUNCHES = {"attn_decode": 0, "greedy_pick": 0, "beam_rows": 0, "beam_advance": 0}   # kernel launches so far (tests assert them)
 
 MAX_KEYS = 1024
 HEAD_DIMS = (16, 64)
 MAX_VOCAB = 65536
+MAX_BEAMS = 8                   # num_beams 2..MAX_BEAMS on the beam kernels
 
 
 def _rows_ok(t: torch.Tensor) -> bool:
@@ -34,7 +35,7 @@ def _rows_ok(t: torch.Tensor) -> bool:
     return (t.stride(-1) == 1 and t.data_ptr() % 16 == 0 and all(s % 8 == 0 for s in t.stride()[:-1]))
 
 
-def _kernel_attention_ok(q, k_cache, v_cache, num_heads, n_keys, k_new, v_new, key_mask, bias) -> bool:
+def _kernel_attention_ok(q, k_cache, v_cache, num_heads, n_keys, k_new, v_new, key_mask, bias, key_rows=None) -> bool:
     if EAGER or not q.is_cuda or q.dtype not in (torch.bfloat16, torch.float32):
         return False
     E = q.shape[-1]
@@ -48,18 +49,25 @@ def _kernel_attention_ok(q, k_cache, v_cache, num_heads, n_keys, k_new, v_new, k
         return False
     if key_mask is not None and (key_mask.stride(-1) != 1 or key_mask.dtype not in (torch.bool, torch.uint8)):
         return False
+    if key_rows is not None and (key_rows.dtype != torch.int32 or not key_rows.is_cuda or key_rows.stride(-1) != 1):
+        return False
     return bias is None or (bias.dtype == torch.float32 and bias.stride(-1) == 1)
 
 
 def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, num_heads: int, *, pos: Optional[int] = None,
                      k_new: Optional[torch.Tensor] = None, v_new: Optional[torch.Tensor] = None,
                      key_mask: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
-                     scale: Optional[float] = None) -> torch.Tensor:
+                     scale: Optional[float] = None, group: int = 1, key_rows: Optional[torch.Tensor] = None) -> torch.Tensor:
     """``softmax(scale * q k^T + bias + mask) v`` for one query row per sequence: q ``[B, H*D]`` (any row stride), caches
     ``[B, Lmax, H*D]`` (unit column stride: a column block of a wider buffer is read in place).  With ``k_new`` / ``v_new``
     ``[B, H*D]`` and ``pos``: they are written into cache row ``pos`` and keys ``0..pos`` are attended (self-attention step); else
     all ``Lmax`` keys.  ``key_mask`` ``[B, Lk]`` (bool / u8, False = masked), ``bias`` ``[H, >= Lk]`` fp32 (T5's relative position
-    bias row of the query position).  ``scale`` defaults to ``D**-0.5`` (BART); T5 passes 1.0.  Returns ``[B, H*D]``."""
+    bias row of the query position).  ``scale`` defaults to ``D**-0.5`` (BART); T5 passes 1.0.  Returns ``[B, H*D]``.
+
+    Beam search (``beam_generate``): ``group`` -- query row r reads cache batch ``r // group`` and key-mask row ``r // group`` (the
+    cross-attention caches of an item serve its ``group`` beams, never expanded); ``key_rows`` int32 ``[B, >= n_keys]`` -- key j of
+    query row r lives in cache batch ``key_rows[r, j]`` (a self-attention cache that is never reordered: the rows' histories are
+    followed through the table); the appended row still goes to batch r, row ``pos``."""
     B, E = q.shape
     D = E // num_heads
     scale = D ** -0.5 if scale is None else float(scale)
@@ -67,13 +75,32 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     if append and pos is None:
         raise ValueError("decode_attention: k_new / v_new need the cache row `pos`")
     n_keys = pos + 1 if append else k_cache.shape[1]
-    if not _kernel_attention_ok(q, k_cache, v_cache, num_heads, n_keys, k_new, v_new, key_mask, bias):
-        return _torch_attention(q, k_cache, v_cache, num_heads, pos, k_new, v_new, key_mask, bias, scale)
+    if append and group != 1:
+        raise ValueError("decode_attention: the appended row goes to batch r; group must be 1 with k_new / v_new")
+    if k_cache.shape[0] * group < B or v_cache.shape[0] * group < B:
+        raise ValueError("decode_attention: the caches hold fewer than B / group batches")
+    if key_rows is not None and (key_rows.shape[0] != B or key_rows.shape[1] < n_keys or k_cache.shape[0] < B):
+        raise ValueError("decode_attention: key_rows must be [B, >= n_keys] over caches of B batches")
+    if not _kernel_attention_ok(q, k_cache, v_cache, num_heads, n_keys, k_new, v_new, key_mask, bias, key_rows):
+        return _torch_attention(q, k_cache, v_cache, num_heads, pos, k_new, v_new, key_mask, bias, scale, group, key_rows)
     out = torch.empty(B, E, dtype=q.dtype, device=q.device)
     km = None
     if key_mask is not None:
         km = key_mask.view(torch.uint8) if key_mask.dtype == torch.bool else key_mask
     lib = _lib.load()
+    if group != 1 or key_rows is not None:
+        code = lib.vlpet_attn_decode_beam(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1),
+                                          k_cache.stride(0), v_cache.stride(1), v_cache.stride(0),
+                                          k_new.data_ptr() if append else None, v_new.data_ptr() if append else None,
+                                          k_new.stride(0) if append else 0, pos if append else 0,
+                                          None if km is None else km.data_ptr(), 0 if km is None else km.stride(0),
+                                          None if bias is None else bias.data_ptr(), 0 if bias is None else bias.stride(0),
+                                          out.data_ptr(), out.stride(0), B, num_heads, D, n_keys, scale, int(group),
+                                          None if key_rows is None else key_rows.data_ptr(),
+                                          0 if key_rows is None else key_rows.stride(0), _io_dtype(q), _stream())
+        _lib.check(code, "vlpet_attn_decode_beam")
+        LAUNCHES["attn_decode"] += 1
+        return out
     code = lib.vlpet_attn_decode(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1),
                                  k_cache.stride(0), v_cache.stride(1), v_cache.stride(0),
                                  k_new.data_ptr() if append else None, v_new.data_ptr() if append else None,
@@ -87,9 +114,9 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     return out
 
 
-def _torch_attention(q, k_cache, v_cache, num_heads, pos, k_new, v_new, key_mask, bias, scale):
+def _torch_attention(q, k_cache, v_cache, num_heads, pos, k_new, v_new, key_mask, bias, scale, group=1, key_rows=None):
     """The torch form: append with an indexed copy, then host.bart.attention_core with Lq = 1 (its 1/sqrt(D) is undone on q when
-    ``scale`` differs; the bias and the key mask become one additive mask)."""
+    ``scale`` differs; the bias and the key mask become one additive mask).  ``group`` / ``key_rows`` gather the caches per row."""
     from .host import bart as HB
     B, E = q.shape
     D = E // num_heads
@@ -99,6 +126,18 @@ def _torch_attention(q, k_cache, v_cache, num_heads, pos, k_new, v_new, key_mask
         k, v = k_cache[:, :pos + 1], v_cache[:, :pos + 1]
     else:
         k, v = k_cache, v_cache
+    if group != 1:
+        k, v = k.repeat_interleave(group, 0), v.repeat_interleave(group, 0)
+        if key_mask is not None:
+            key_mask = key_mask.repeat_interleave(group, 0)
+    if key_rows is not None:
+        n = k.shape[1]
+        kr = key_rows[:, :n].long()
+        if k_new is not None:
+            kr = kr.clone()
+            kr[:, pos] = torch.arange(B, device=kr.device)
+        j = torch.arange(n, device=kr.device)[None].expand(B, n)
+        k, v = k_cache[kr, j], v_cache[kr, j]
     Lk = k.shape[1]
     mask = None
     if bias is not None:
@@ -179,3 +218,249 @@ def greedy_generate(step: Callable[[torch.Tensor, int], torch.Tensor], vocab: in
         if eos_token_id is not None and int(counters[pos]) == 0:
             break
     return ids[:, :cur_len]
+
+
+# ---- beam search: HF 4.2.1 beam_search with num_return_sequences = 1 (src/multitask_video.py: generate(num_beams = 5)) ----------
+#
+# Rows are B * K, item-major (row = item * K + beam).  The cross-attention caches stay per item (decode_attention's ``group``), the
+# self-attention caches are never reordered (its ``key_rows``).  Per step two kernels follow the decoder: ``vlpet_beam_rows`` (per row
+# and column slice: log-sum-exp partials and the top 2K of the logits after BART's forced eos and the bans) and
+# ``vlpet_beam_advance`` (per item: the top 2K of the flat scores, BeamSearchScorer.process, the reordered ids / key rows, the next
+# tokens, the count of items not done).  ``finalize`` runs once, on the host.
+
+def _beam_slices(rows: int, vocab: int) -> int:
+    """column slices per row: enough workgroups to give every CU a few (250 rows x 5 slices at the video shape), >= 1024 columns each"""
+    return max(1, min(64, -(-1024 // rows), -(-vocab // 1024)))
+
+
+class BeamState:
+    """The device state of one beam_generate() call: ping-pong ids / key rows, beam scores, next tokens, the hypothesis table
+    (K slots per item: score, (length, insertion), tokens) and per item (worst score; count, insertions, done)."""
+
+    def __init__(self, B, K, max_length, device, start, pad, key_rows=None):
+        rows = B * K
+        self.B, self.K, self.L = B, K, max_length
+        self.ids = torch.full((2, rows, max_length), int(pad), dtype=torch.int64, device=device)
+        self.ids[:, :, 0] = int(start)
+        self.key_rows = key_rows
+        self.scores = torch.zeros(B, K, dtype=torch.float32, device=device)
+        self.scores[:, 1:] = -1e9
+        self.scores = self.scores.view(rows)
+        self.tokens = torch.full((rows,), int(start), dtype=torch.int64, device=device)
+        self.hyp_score = torch.zeros(rows, dtype=torch.float32, device=device)
+        self.hyp_meta = torch.zeros(rows, 2, dtype=torch.int32, device=device)
+        self.hyp_tokens = torch.full((rows, max_length), int(pad), dtype=torch.int64, device=device)
+        self.worst = torch.full((B,), 1e9, dtype=torch.float32, device=device)
+        self.state = torch.zeros(B, 3, dtype=torch.int32, device=device)
+        self.counters = torch.zeros(max(max_length, 1), dtype=torch.int32, device=device)
+
+
+def beam_key_rows(rows: int, max_length: int, device) -> torch.Tensor:
+    """the ping-pong key-row tables [2, rows, max_length] int32 of a fresh call: every key in the row's own cache batch"""
+    return torch.arange(rows, dtype=torch.int32, device=device).view(1, rows, 1).expand(2, rows, max_length).contiguous()
+
+
+def beam_step(logits: torch.Tensor, vocab: int, st: BeamState, pos: int, *, eos_token_id: int, pad_token_id: int,
+              min_length: int = 0, no_repeat_ngram_size: int = 0, length_penalty: float = 1.0, early_stopping: bool = False,
+              force_eos: bool = False, slices: Optional[int] = None) -> None:
+    """One step after the decoder: ``logits`` [B*K, >= vocab] of position ``pos``; reads ``st.ids[pos % 2]`` / ``st.key_rows[pos % 2]``
+    and writes the other halves, the beam scores, ``st.tokens`` and ``st.counters[pos]`` (items not done).  Nothing is synchronised."""
+    rows, K = logits.shape[0], st.K
+    src, dst = pos & 1, (pos + 1) & 1
+    kr = st.key_rows
+    ok = (not EAGER and logits.is_cuda and logits.dtype in (torch.bfloat16, torch.float32) and logits.dim() == 2
+          and _rows_ok(logits) and logits.shape[1] >= (vocab + 7) // 8 * 8 and vocab <= MAX_VOCAB and 2 <= K <= MAX_BEAMS
+          and rows == st.B * K and 0 <= eos_token_id < vocab and st.ids.is_cuda
+          and (kr is None or (kr.is_cuda and kr.dtype == torch.int32 and kr.is_contiguous())))
+    if not ok:
+        return _torch_beam_step(logits, vocab, st, pos, eos_token_id, pad_token_id, min_length, no_repeat_ngram_size,
+                                length_penalty, early_stopping, force_eos)
+    S = _beam_slices(rows, vocab) if slices is None else int(slices)
+    T = 2 * K
+    ws = getattr(st, "_ws", None)
+    if ws is None or ws[0].shape[0] != rows * S * 2:
+        ws = (torch.empty(rows * S * 2, dtype=torch.float32, device=logits.device),
+              torch.empty(rows * S * T, dtype=torch.float32, device=logits.device),
+              torch.empty(rows * S * T, dtype=torch.int32, device=logits.device))
+        st._ws = ws
+    stats, val, tok = ws
+    ids_in, ids_out = st.ids[src], st.ids[dst]
+    lib = _lib.load()
+    code = lib.vlpet_beam_rows(logits.data_ptr(), logits.stride(0), vocab, ids_in.data_ptr(), ids_in.stride(0), pos, rows, K, S,
+                               int(eos_token_id), int(min_length), int(no_repeat_ngram_size), int(bool(force_eos)),
+                               stats.data_ptr(), val.data_ptr(), tok.data_ptr(), _io_dtype(logits), _stream())
+    _lib.check(code, "vlpet_beam_rows")
+    LAUNCHES["beam_rows"] += 1
+    code = lib.vlpet_beam_advance(stats.data_ptr(), val.data_ptr(), tok.data_ptr(), S, vocab, st.B, K, st.scores.data_ptr(),
+                                  ids_in.data_ptr(), ids_out.data_ptr(), ids_in.stride(0),
+                                  None if kr is None else kr[src].data_ptr(), None if kr is None else kr[dst].data_ptr(),
+                                  0 if kr is None else kr.stride(1), st.tokens.data_ptr(), st.hyp_score.data_ptr(),
+                                  st.hyp_meta.data_ptr(), st.hyp_tokens.data_ptr(), st.hyp_tokens.stride(0), st.worst.data_ptr(),
+                                  st.state.data_ptr(), st.counters.data_ptr() + 4 * pos, pos, int(eos_token_id),
+                                  int(pad_token_id), float(length_penalty), int(bool(early_stopping)), _stream())
+    _lib.check(code, "vlpet_beam_advance")
+    LAUNCHES["beam_advance"] += 1
+
+
+def _torch_beam_rows(logits, vocab, ids, pos, eos, min_length, ngram, force_eos):
+    """the processed fp32 log-probs [rows, vocab]: BART's forced eos, log_softmax, then the bans (no renormalisation)"""
+    x = logits[:, :vocab].float()
+    if force_eos:
+        keep = x[:, eos].clone()
+        x = torch.full_like(x, float("-inf"))
+        x[:, eos] = keep
+    x = torch.log_softmax(x, -1)
+    cur_len = pos + 1
+    if ngram > 0 and cur_len + 1 >= ngram:
+        for r, prefix in enumerate(ids[:, :cur_len].tolist()):
+            banned = _banned_ngram_tokens(prefix, ngram)
+            if banned:
+                x[r, torch.tensor(banned, device=x.device)] = float("-inf")
+    if cur_len < min_length:
+        x[:, eos] = float("-inf")
+    return x
+
+
+class _Hyps:
+    """an item's hypothesis table on the host (the torch forms and finalize): K slots of (score, insertion, tokens)"""
+
+    def __init__(self, K, lp, early, beams, worst, n_added):
+        self.K, self.lp, self.early = K, lp, early
+        self.beams, self.worst, self.n_added = beams, worst, n_added
+
+    def add(self, tokens, sum_logprobs):
+        score = sum_logprobs / (len(tokens) ** self.lp)
+        if len(self.beams) < self.K or score > self.worst:
+            if len(self.beams) < self.K:
+                self.beams.append([score, self.n_added, list(tokens)])
+                self.worst = min(score, self.worst)
+            else:
+                at = min(range(self.K), key=lambda j: (self.beams[j][0], self.beams[j][1]))
+                self.beams[at] = [score, self.n_added, list(tokens)]
+                self.worst = min(b[0] for b in self.beams)
+            self.n_added += 1
+
+    def is_done(self, best, cur_len):
+        return len(self.beams) >= self.K and (self.early or self.worst >= best / cur_len ** self.lp)
+
+
+def _load_hyps(st, lp, early):
+    """the hypothesis tables of ``st`` as host objects (slot order kept)"""
+    hs, hm = st.hyp_score.tolist(), st.hyp_meta.tolist()
+    ht, worst, state = st.hyp_tokens.tolist(), st.worst.tolist(), st.state.tolist()
+    K = st.K
+    out = []
+    for b in range(st.B):
+        cnt, nadd, _ = state[b]
+        beams = [[hs[b * K + j], hm[b * K + j][1], ht[b * K + j][:hm[b * K + j][0]]] for j in range(cnt)]
+        out.append(_Hyps(K, lp, early, beams, worst[b], nadd))
+    return out
+
+
+def _store_hyps(st, hyps, done):
+    K = st.K
+    for b, h in enumerate(hyps):
+        for j, (score, order, toks) in enumerate(h.beams):
+            r = b * K + j
+            st.hyp_score[r] = score
+            st.hyp_meta[r, 0] = len(toks)
+            st.hyp_meta[r, 1] = order
+            st.hyp_tokens[r, :len(toks)] = torch.tensor(toks, dtype=torch.int64)
+        st.worst[b] = h.worst
+        st.state[b, 0] = len(h.beams)
+        st.state[b, 1] = h.n_added
+        st.state[b, 2] = int(done[b])
+
+
+def _torch_beam_step(logits, vocab, st, pos, eos, pad, min_length, ngram, lp, early, force_eos):
+    """The torch form of beam_step: the same state, BeamSearchScorer.process in a host loop over the items"""
+    B, K = st.B, st.K
+    src, dst = pos & 1, (pos + 1) & 1
+    cur_len = pos + 1
+    ids_in = st.ids[src]
+    x = _torch_beam_rows(logits, vocab, ids_in, pos, eos, min_length, ngram, force_eos)
+    scores = (x + st.scores[:, None]).view(B, K * vocab)
+    top_v, top_i = torch.sort(scores, dim=-1, descending=True, stable=True)
+    top_v, top_i = top_v[:, :2 * K].tolist(), top_i[:, :2 * K].tolist()
+    hyps = _load_hyps(st, lp, early)
+    done = [bool(d) for d in st.state[:, 2].tolist()]
+    prefixes = ids_in[:, :cur_len].tolist()
+    nscore, ntok, nsrc = st.scores.tolist(), [pad] * (B * K), list(range(B * K))
+    for b in range(B):
+        if done[b]:
+            continue
+        slot = 0
+        for rank in range(2 * K):
+            s, flat = top_v[b][rank], top_i[b][rank]
+            beam, tok = flat // vocab, flat % vocab
+            if tok == eos:
+                if rank >= K:
+                    continue
+                hyps[b].add(prefixes[b * K + beam], s)
+            else:
+                nscore[b * K + slot], ntok[b * K + slot], nsrc[b * K + slot] = s, tok, b * K + beam
+                slot += 1
+            if slot == K:
+                break
+        done[b] = hyps[b].is_done(top_v[b][0], cur_len)
+    dev = st.ids.device
+    idx = torch.tensor(nsrc, device=dev)
+    tok = torch.tensor(ntok, dtype=torch.int64, device=dev)
+    st.ids[dst, :, :cur_len] = ids_in[idx, :cur_len]
+    st.ids[dst, :, cur_len] = tok
+    if st.key_rows is not None:
+        st.key_rows[dst, :, :cur_len] = st.key_rows[src][idx, :cur_len]
+        st.key_rows[dst, :, cur_len] = torch.arange(B * K, dtype=torch.int32, device=dev)
+    st.scores.copy_(torch.tensor(nscore, dtype=torch.float32))
+    st.tokens.copy_(tok)
+    _store_hyps(st, hyps, done)
+    st.counters[pos] += sum(1 for d in done if not d)
+
+
+def beam_finalize(st: BeamState, cur_len: int, vocab: int, eos_token_id: int, pad_token_id: int, length_penalty: float,
+                  early_stopping: bool):
+    """BeamSearchScorer.finalize (num_beam_hyps_to_keep = 1): the open beams of items not done are added, each item's best
+    hypothesis (ties: the one added last) becomes its output.  Returns (ids [B, min(max len + 1, max_length)], scores [B] fp32)."""
+    hyps = _load_hyps(st, length_penalty, early_stopping)
+    done = st.state[:, 2].tolist()
+    final = st.ids[(cur_len - 1) & 1][:, :cur_len].tolist()
+    bs = st.scores.tolist()
+    K = st.K
+    best = []
+    for b, h in enumerate(hyps):
+        if not done[b]:
+            for k in range(K):
+                h.add(final[b * K + k], bs[b * K + k])
+        best.append(max(h.beams, key=lambda x: (x[0], x[1])))
+    lens = [len(t) for _, _, t in best]
+    width = min(max(lens) + 1, st.L)
+    out = torch.full((st.B, width), int(pad_token_id), dtype=torch.int64)
+    for b, (_, _, t) in enumerate(best):
+        out[b, :len(t)] = torch.tensor(t, dtype=torch.int64)
+        if len(t) < st.L:
+            out[b, len(t)] = int(eos_token_id)
+    dev = st.ids.device
+    return out.to(dev), torch.tensor([s for s, _, _ in best], dtype=torch.float32, device=dev)
+
+
+def beam_generate(step: Callable[[torch.Tensor, int], torch.Tensor], vocab: int, B: int, num_beams: int, device, max_length: int,
+                  start_token_id: int, eos_token_id: int, pad_token_id: int, min_length: int = 0, no_repeat_ngram_size: int = 0,
+                  length_penalty: float = 1.0, early_stopping: bool = False, force_eos: bool = False,
+                  key_rows: Optional[torch.Tensor] = None):
+    """The loop of HF 4.2.1 beam_search.  ``step(tokens [B*K], pos)`` runs the decoder on the rows' tokens at ``pos`` and returns
+    their logits [B*K, >= vocab]; it follows ``key_rows[pos % 2]`` (``beam_key_rows``) when the caches use them.  ``force_eos``:
+    BART's adjust_logits_during_generation (every column but eos at -inf when cur_len == max_length - 1).  One host
+    synchronisation per step: the count of items not done.  Returns (ids [B, <= max_length], sequence scores [B])."""
+    if eos_token_id is None:
+        raise ValueError("beam search needs an eos token")
+    st = BeamState(B, num_beams, max_length, device, start_token_id, pad_token_id, key_rows)
+    cur_len = 1
+    for pos in range(max_length - 1):
+        logits = step(st.tokens, pos)
+        beam_step(logits, vocab, st, pos, eos_token_id=int(eos_token_id), pad_token_id=int(pad_token_id), min_length=min_length,
+                  no_repeat_ngram_size=no_repeat_ngram_size, length_penalty=length_penalty, early_stopping=early_stopping,
+                  force_eos=force_eos and pos + 1 == max_length - 1)
+        cur_len = pos + 2
+        if int(st.counters[pos]) == 0:
+            break
+    return beam_finalize(st, cur_len, vocab, eos_token_id, pad_token_id, length_penalty, early_stopping)

@@ -354,11 +354,13 @@ class BartAttention(nn.Module):
             return qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
         return _linear(self.q_proj, x)[:, 0], _linear(self.k_proj, x)[:, 0], _linear(self.v_proj, x)[:, 0]
 
-    def step_self(self, x, k_cache, v_cache, pos, task=None):
-        """causal self-attention of the token at ``pos``: its key / value rows go into cache row ``pos`` inside the attention launch"""
+    def step_self(self, x, k_cache, v_cache, pos, task=None, key_rows=None):
+        """causal self-attention of the token at ``pos``: its key / value rows go into cache row ``pos`` inside the attention launch
+        (beam search: earlier keys are looked up through ``key_rows``)"""
         from ..decode import decode_attention
         q, k, v = self._step_qkv(x, task)
-        out = decode_attention(q, k_cache, v_cache, self.num_heads, pos=pos, k_new=k, v_new=v, scale=self.head_dim ** -0.5)
+        out = decode_attention(q, k_cache, v_cache, self.num_heads, pos=pos, k_new=k, v_new=v, scale=self.head_dim ** -0.5,
+                               key_rows=key_rows)
         return _linear(self.out_proj, out[:, None])
 
     def cross_values(self, enc, task=None):
@@ -369,10 +371,11 @@ class BartAttention(nn.Module):
             v = self.attn_value_parallel_adapter(enc, task, y=v)
         return v
 
-    def step_cross(self, x, k_cache, v_cache, key_mask, task=None):
+    def step_cross(self, x, k_cache, v_cache, key_mask, task=None, group=1):
         from ..decode import decode_attention
         q = self.q_proj(x, task) if self.use_lora else _linear(self.q_proj, x)
-        out = decode_attention(q[:, 0], k_cache, v_cache, self.num_heads, key_mask=key_mask, scale=self.head_dim ** -0.5)
+        out = decode_attention(q[:, 0], k_cache, v_cache, self.num_heads, key_mask=key_mask, scale=self.head_dim ** -0.5,
+                               group=group)
         return _linear(self.out_proj, out[:, None])
 
 
@@ -447,11 +450,13 @@ class BartDecoderLayer(nn.Module):
 
 
     def step(self, x, cache, pos, task=None):
-        """generate(): the token x [B, 1, d] at position ``pos``; ``cache`` = (self k, self v, cross k, cross v, cross key mask)"""
-        ks, vs, kx, vx, km = cache
-        h = self.self_attn.step_self(x, ks, vs, pos, task)
+        """generate(): the token x [B, 1, d] at position ``pos``; ``cache`` = (self k, self v, cross k, cross v, cross key mask[,
+        beams per item, ping-pong key-row tables]) -- beam search adds the last two (decode.beam_key_rows)"""
+        ks, vs, kx, vx, km = cache[:5]
+        group, kr = cache[5:] if len(cache) > 5 else (1, None)
+        h = self.self_attn.step_self(x, ks, vs, pos, task, key_rows=None if kr is None else kr[pos & 1])
         x = sublayer_tail(x, h, self.self_attn_layer_norm, self.dropout, self.training)                     # K5
-        h = self.encoder_attn.step_cross(x, kx, vx, km, task)
+        h = self.encoder_attn.step_cross(x, kx, vx, km, task, group=group)
         x = sublayer_tail(x, h, self.encoder_attn_layer_norm, self.dropout, self.training)                  # K5
         h = ffn_activation(_linear(self.fc1, x), "gelu", self.activation_dropout, self.training)
         return sublayer_tail(x, _linear(self.fc2, h), self.final_layer_norm, self.dropout, self.training)   # K5
@@ -570,17 +575,23 @@ class BartDecoder(nn.Module):
         return VF.cross_key_blocks(enc, c[1], c[2], len(mods))
 
 
-    def init_cache(self, enc, key_mask, task, max_length):
+    def init_cache(self, enc, key_mask, task, max_length, num_beams=1):
         """generate(): per layer a self-attention key / value cache [B, max_length, E] (one allocation) and the cross-attention
-        caches of ``enc``: keys as column blocks of ONE fused projection where the layers allow it, values through K2 / K3 once"""
+        caches of ``enc``: keys as column blocks of ONE fused projection where the layers allow it, values through K2 / K3 once.
+        ``num_beams`` K > 1: the self-attention caches have B * K rows, the cross-attention ones stay per item, and every layer's
+        tuple ends with (K, the shared ping-pong key-row tables)."""
+        from ..decode import beam_key_rows
         B, _, E = enc.shape
         n = len(self.layers)
-        selfc = enc.new_empty(n, 2, B, max_length, E)
+        selfc = enc.new_empty(n, 2, B * num_beams, max_length, E)
         if FUSE_CROSS_KEYS and not EAGER_ATTENTION and n >= 2 and enc.is_cuda:
             ks = self._cross_keys(enc)[0]
         else:
             ks = [_linear(l.encoder_attn.k_proj, enc) for l in self.layers]
         vs = [l.encoder_attn.cross_values(enc, task) for l in self.layers]
+        if num_beams > 1:
+            kr = beam_key_rows(B * num_beams, max_length, enc.device)
+            return [(selfc[i, 0], selfc[i, 1], ks[i], vs[i], key_mask, num_beams, kr) for i in range(n)]
         return [(selfc[i, 0], selfc[i, 1], ks[i], vs[i], key_mask) for i in range(n)]
 
     def step(self, tok, pos, caches, task=None):
@@ -652,12 +663,15 @@ class VLBart(nn.Module):
         return lm_loss(h, self.model.shared.weight, labels, self._logits_bias())
 
     def generate(self, input_ids, vis_inputs, task, attention_mask=None, max_length=20, min_length=0, no_repeat_ngram_size=0,
-                 eos_token_id=None, pad_token_id=None, no_padding=False):
+                 eos_token_id=None, pad_token_id=None, no_padding=False, num_beams=1, length_penalty=1.0, early_stopping=False):
         """Greedy search with HF 4.2.1 semantics (num_beams = 1; the reference's evaluation, src/multitask.py test_step) on a per-layer
         key / value cache: the encoder runs once, every step feeds one token (vlpet_amd.decode).  Returns the token ids
         [B, <= max_length], starting with decoder_start_token_id; finished rows are padded.  eos / pad default to the config's
-        (BART: 2 / 1).  Pass the checkpoint's own generation settings (min_length, no_repeat_ngram_size) explicitly."""
-        from ..decode import greedy_generate
+        (BART: 2 / 1).  Pass the checkpoint's own generation settings (min_length, no_repeat_ngram_size) explicitly.
+        ``num_beams`` > 1: HF 4.2.1 beam search (one sequence per item; the video captioning evaluation, src/multitask_video.py)
+        with ``length_penalty`` / ``early_stopping``, BART's forced eos at the last step, and the cross-attention caches kept per
+        item (decode.beam_generate, which also returns each sequence's score)."""
+        from ..decode import beam_generate, greedy_generate
         from ..lmloss import _padded_head
         cfg = self.config
         eos = getattr(cfg, "eos_token_id", 2) if eos_token_id is None else eos_token_id
@@ -669,7 +683,8 @@ class VLBart(nn.Module):
                 enc, mask = self.model.encoder(input_ids, vis_inputs, attention_mask, task, no_padding)
                 key_mask = None if mask is None else mask[:, 0, 0, :].contiguous()
                 dec = self.model.decoder
-                caches = dec.init_cache(enc, key_mask, task, max_length)
+                K = int(num_beams)
+                caches = dec.init_cache(enc, key_mask, task, max_length, num_beams=K)
                 V = self.model.shared.weight.shape[0]
                 head = _padded_head(self.model.shared.weight, enc.dtype)
                 bias = self._logits_bias()
@@ -679,6 +694,10 @@ class VLBart(nn.Module):
                     if bias is not None:
                         logits[:, :V] += bias[0].to(logits.dtype)
                     return logits
+                if K > 1:
+                    return beam_generate(step, V, enc.shape[0], K, enc.device, max_length, cfg.decoder_start_token_id, eos, pad,
+                                         min_length, no_repeat_ngram_size, length_penalty, early_stopping, force_eos=True,
+                                         key_rows=caches[0][6])[0]
                 return greedy_generate(step, V, enc.shape[0], enc.device, max_length, cfg.decoder_start_token_id, eos, pad,
                                        min_length, no_repeat_ngram_size)
         finally:

@@ -329,7 +329,7 @@ class T5Attention(nn.Module):
 
 
     # ---- generate(): one decoder token against the caches (decode.decode_attention, scale 1: T5 has no 1/sqrt(d))
-    def step_self(self, n, k_cache, v_cache, pos, bias_row):
+    def step_self(self, n, k_cache, v_cache, pos, bias_row, key_rows=None):
         """causal self-attention of the normed token n [B, 1, d] at ``pos``; ``bias_row`` [H, >= pos + 1]: row ``pos`` of the
         decoder's relative position bias"""
         from ..decode import decode_attention
@@ -339,7 +339,8 @@ class T5Attention(nn.Module):
             q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
         else:
             q, k, v = _linear(self.q, n)[:, 0], _linear(self.k, n)[:, 0], _linear(self.v, n)[:, 0]
-        out = decode_attention(q, k_cache, v_cache, self.n_heads, pos=pos, k_new=k, v_new=v, bias=bias_row, scale=1.0)
+        out = decode_attention(q, k_cache, v_cache, self.n_heads, pos=pos, k_new=k, v_new=v, bias=bias_row, scale=1.0,
+                               key_rows=key_rows)
         return _linear(self.o, out[:, None])
 
     def cross_values(self, enc, task=None):
@@ -349,9 +350,9 @@ class T5Attention(nn.Module):
             v = self.attn_value_parallel_adapter(enc, task, y=v)
         return v
 
-    def step_cross(self, n, k_cache, v_cache, key_mask):
+    def step_cross(self, n, k_cache, v_cache, key_mask, group=1):
         from ..decode import decode_attention
-        out = decode_attention(_linear(self.q, n)[:, 0], k_cache, v_cache, self.n_heads, key_mask=key_mask, scale=1.0)
+        out = decode_attention(_linear(self.q, n)[:, 0], k_cache, v_cache, self.n_heads, key_mask=key_mask, scale=1.0, group=group)
         return _linear(self.o, out[:, None])
 
 
@@ -433,13 +434,15 @@ class T5Block(nn.Module):
 
 
 def _block_step(blk, x, cache, pos, bias_row):
-    """generate(): one decoder block on the token x [B, 1, d]; ``cache`` = (self k, self v, cross k, cross v, cross key mask).  The
-    tails are forward's (_tail_linked: on the GPU each fused with the next sublayer's norm)."""
+    """generate(): one decoder block on the token x [B, 1, d]; ``cache`` = (self k, self v, cross k, cross v, cross key mask[, beams
+    per item, ping-pong key-row tables]).  The tails are forward's (_tail_linked: on the GPU each fused with the next sublayer's
+    norm)."""
     sa, ca, ff = blk.layer[0], blk.layer[1], blk.layer[-1]
-    ks, vs, kx, vx, km = cache
-    y = sa.SelfAttention.step_self(sa.layer_norm(x), ks, vs, pos, bias_row)
+    ks, vs, kx, vx, km = cache[:5]
+    group, kr = cache[5:] if len(cache) > 5 else (1, None)
+    y = sa.SelfAttention.step_self(sa.layer_norm(x), ks, vs, pos, bias_row, key_rows=None if kr is None else kr[pos & 1])
     x = _tail_linked(x, y, sa.p, sa.training, None, layer=sa)
-    y = ca.EncDecAttention.step_cross(ca.layer_norm(x), kx, vx, km)
+    y = ca.EncDecAttention.step_cross(ca.layer_norm(x), kx, vx, km, group=group)
     x = _tail_linked(x, y, ca.p, ca.training, None, layer=ca)
     y = ff.DenseReluDense(ff.layer_norm(x))
     return _tail_linked(x, y, ff.p, ff.training, None, layer=ff)
@@ -544,14 +547,16 @@ class T5Decoder(nn.Module):
         return F.dropout(self.final_layer_norm(x), p=self.p, training=self.training)
 
 
-    def init_cache(self, enc, key_mask, task, max_length):
+    def init_cache(self, enc, key_mask, task, max_length, num_beams=1):
         """generate(): self-attention caches [B, max_length, inner] per block (one allocation), cross-attention caches of ``enc`` (keys
         as column blocks of ONE fused projection on the GPU), and the relative position bias of every query position as a
-        [max_length, H, max_length] fp32 table (row ``pos`` = compute_bias(max_length, max_length)[0, :, pos])"""
+        [max_length, H, max_length] fp32 table (row ``pos`` = compute_bias(max_length, max_length)[0, :, pos]).  ``num_beams`` > 1:
+        as host/bart.py BartDecoder.init_cache (self-attention caches of B * K rows, (K, key-row tables) ending every tuple)"""
+        from ..decode import beam_key_rows
         B, _, _ = enc.shape
         n = len(self.block)
         inner = self.block[0].layer[0].SelfAttention.inner
-        selfc = enc.new_empty(n, 2, B, max_length, inner)
+        selfc = enc.new_empty(n, 2, B * num_beams, max_length, inner)
         atts = [blk.layer[1].EncDecAttention for blk in self.block]
         if FUSE_CROSS_KEYS and not EAGER_ATTENTION and n >= 2 and enc.is_cuda:
             ks = self._cross_keys(enc)[0]
@@ -560,6 +565,9 @@ class T5Decoder(nn.Module):
         vs = [a.cross_values(enc, task) for a in atts]
         rel = self.block[0].layer[0].SelfAttention.compute_bias(max_length, max_length)[0]        # [H, q, k]
         table = rel.permute(1, 0, 2).float().contiguous()
+        if num_beams > 1:
+            kr = beam_key_rows(B * num_beams, max_length, enc.device)
+            return [(selfc[i, 0], selfc[i, 1], ks[i], vs[i], key_mask, num_beams, kr) for i in range(n)], table
         return [(selfc[i, 0], selfc[i, 1], ks[i], vs[i], key_mask) for i in range(n)], table
 
     def step(self, tok, pos, state):
@@ -619,10 +627,11 @@ class VLT5(nn.Module):
         return lm_loss(h, self.shared.weight, labels)
 
     def generate(self, input_ids, vis_inputs, task, attention_mask=None, max_length=20, min_length=0, no_repeat_ngram_size=0,
-                 eos_token_id=None, pad_token_id=None, no_padding=False):
+                 eos_token_id=None, pad_token_id=None, no_padding=False, num_beams=1, length_penalty=1.0, early_stopping=False):
         """Greedy search with HF 4.2.1 semantics on per-block key / value caches (see host/bart.py VLBart.generate).  eos / pad
-        default to T5's 1 / 0; the output starts with decoder_start_token_id (0)."""
-        from ..decode import greedy_generate
+        default to T5's 1 / 0; the output starts with decoder_start_token_id (0).  ``num_beams`` > 1: HF 4.2.1 beam search as in
+        VLBart.generate (T5 forces no eos)."""
+        from ..decode import beam_generate, greedy_generate
         from ..lmloss import _padded_head
         cfg = self.config
         eos = getattr(cfg, "eos_token_id", 1) if eos_token_id is None else eos_token_id
@@ -633,13 +642,18 @@ class VLT5(nn.Module):
             with torch.no_grad():
                 enc, keep = self.encoder(input_ids, vis_inputs, attention_mask, task)
                 key_mask = (keep > 0.5).contiguous()
-                state = self.decoder.init_cache(enc, key_mask, task, max_length)
+                K = int(num_beams)
+                state = self.decoder.init_cache(enc, key_mask, task, max_length, num_beams=K)
                 V = self.shared.weight.shape[0]
                 head = _padded_head(self.shared.weight, enc.dtype)
                 scale = cfg.d_model ** -0.5
 
                 def step(tok, pos):
                     return F.linear(self.decoder.step(tok, pos, state) * scale, head)
+                if K > 1:
+                    return beam_generate(step, V, enc.shape[0], K, enc.device, max_length, cfg.decoder_start_token_id, eos, pad,
+                                         min_length, no_repeat_ngram_size, length_penalty, early_stopping,
+                                         key_rows=state[0][0][6])[0]
                 return greedy_generate(step, V, enc.shape[0], enc.device, max_length, cfg.decoder_start_token_id, eos, pad,
                                        min_length, no_repeat_ngram_size)
         finally:
