@@ -14,7 +14,7 @@ fallback; ``EAGER = True`` forces them, the "torch cached" leg of tools/genbench
 ``host.bart.attention_core`` so that the CPU parity harness of the test suite, which swaps that attribute, covers it."""
 from __future__ import annotations
 
-from typing import Callable, Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -87,29 +87,19 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     km = None
     if key_mask is not None:
         km = key_mask.view(torch.uint8) if key_mask.dtype == torch.bool else key_mask
+    args = (q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1), k_cache.stride(0),
+            v_cache.stride(1), v_cache.stride(0), k_new.data_ptr() if append else None, v_new.data_ptr() if append else None,
+            k_new.stride(0) if append else 0, pos if append else 0, None if km is None else km.data_ptr(),
+            0 if km is None else km.stride(0), None if bias is None else bias.data_ptr(), 0 if bias is None else bias.stride(0),
+            out.data_ptr(), out.stride(0), B, num_heads, D, n_keys, scale)
     lib = _lib.load()
-    if group != 1 or key_rows is not None:
-        code = lib.vlpet_attn_decode_beam(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1),
-                                          k_cache.stride(0), v_cache.stride(1), v_cache.stride(0),
-                                          k_new.data_ptr() if append else None, v_new.data_ptr() if append else None,
-                                          k_new.stride(0) if append else 0, pos if append else 0,
-                                          None if km is None else km.data_ptr(), 0 if km is None else km.stride(0),
-                                          None if bias is None else bias.data_ptr(), 0 if bias is None else bias.stride(0),
-                                          out.data_ptr(), out.stride(0), B, num_heads, D, n_keys, scale, int(group),
-                                          None if key_rows is None else key_rows.data_ptr(),
+    if group != 1 or key_rows is not None:        # the beam entry point: the same arguments, then the group and the key-row table
+        code = lib.vlpet_attn_decode_beam(*args, int(group), None if key_rows is None else key_rows.data_ptr(),
                                           0 if key_rows is None else key_rows.stride(0), _io_dtype(q), _stream())
         _lib.check(code, "vlpet_attn_decode_beam")
-        LAUNCHES["attn_decode"] += 1
-        return out
-    code = lib.vlpet_attn_decode(q.data_ptr(), q.stride(0), k_cache.data_ptr(), v_cache.data_ptr(), k_cache.stride(1),
-                                 k_cache.stride(0), v_cache.stride(1), v_cache.stride(0),
-                                 k_new.data_ptr() if append else None, v_new.data_ptr() if append else None,
-                                 k_new.stride(0) if append else 0, pos if append else 0,
-                                 None if km is None else km.data_ptr(), 0 if km is None else km.stride(0),
-                                 None if bias is None else bias.data_ptr(), 0 if bias is None else bias.stride(0),
-                                 out.data_ptr(), out.stride(0), B, num_heads, D, pos + 1 if append else k_cache.shape[1],
-                                 scale, _io_dtype(q), _stream())
-    _lib.check(code, "vlpet_attn_decode")
+    else:
+        code = lib.vlpet_attn_decode(*args, _io_dtype(q), _stream())
+        _lib.check(code, "vlpet_attn_decode")
     LAUNCHES["attn_decode"] += 1
     return out
 
@@ -258,6 +248,30 @@ class BeamState:
 def beam_key_rows(rows: int, max_length: int, device) -> torch.Tensor:
     """the ping-pong key-row tables [2, rows, max_length] int32 of a fresh call: every key in the row's own cache batch"""
     return torch.arange(rows, dtype=torch.int32, device=device).view(1, rows, 1).expand(2, rows, max_length).contiguous()
+
+
+class DecodeState(NamedTuple):
+    """The caches of one generate() call.  ``layers``: per decoder layer ``(self_k, self_v, cross_k, cross_v)`` -- self-attention
+    caches [B * group, max_length, E] filled row by row, cross-attention caches [B, Lk, E] of the encoder output, kept per item.
+    Once per call: ``key_mask`` [B, Lk] of the encoder output (or None), ``group`` (beams per item; 1 = greedy), ``key_rows`` (the
+    ping-pong key-row tables of beam search, ``beam_key_rows``; None = greedy) and ``bias_table`` (T5: fp32 [max_length, H,
+    max_length], row ``pos`` = the relative position bias of query position ``pos``; else None)."""
+    layers: list
+    key_mask: Optional[torch.Tensor]
+    group: int
+    key_rows: Optional[torch.Tensor]
+    bias_table: Optional[torch.Tensor]
+
+
+def new_decode_state(enc: torch.Tensor, width: int, max_length: int, cross_k, cross_v, key_mask, num_beams: int = 1,
+                     bias_table: Optional[torch.Tensor] = None) -> DecodeState:
+    """The state of a fresh call over the encoder output ``enc`` [B, Lk, d]: ONE allocation [n, 2, B * num_beams, max_length, width]
+    holds every layer's self-attention caches; ``cross_k`` / ``cross_v`` are the layers' projected cross-attention keys / values."""
+    B, n = enc.shape[0], len(cross_v)
+    selfc = enc.new_empty(n, 2, B * num_beams, max_length, width)
+    key_rows = beam_key_rows(B * num_beams, max_length, enc.device) if num_beams > 1 else None
+    return DecodeState([(selfc[i, 0], selfc[i, 1], cross_k[i], cross_v[i]) for i in range(n)], key_mask, num_beams, key_rows,
+                       bias_table)
 
 
 def beam_step(logits: torch.Tensor, vocab: int, st: BeamState, pos: int, *, eos_token_id: int, pad_token_id: int,
@@ -464,3 +478,16 @@ def beam_generate(step: Callable[[torch.Tensor, int], torch.Tensor], vocab: int,
         if int(st.counters[pos]) == 0:
             break
     return beam_finalize(st, cur_len, vocab, eos_token_id, pad_token_id, length_penalty, early_stopping)
+
+
+def generate(step: Callable[[torch.Tensor, int], torch.Tensor], vocab: int, B: int, device, key_rows: Optional[torch.Tensor],
+             start_token_id: int, eos_token_id: Optional[int], pad_token_id: int, max_length: int, min_length: int = 0,
+             no_repeat_ngram_size: int = 0, num_beams: int = 1, length_penalty: float = 1.0, early_stopping: bool = False,
+             force_eos: bool = False) -> torch.Tensor:
+    """The driver behind ``VLBart.generate`` / ``VLT5.generate``: beam search for ``num_beams`` > 1 (over ``key_rows``, the state's
+    tables), else greedy search.  Returns the ids [B, <= max_length].  (Both loops are looked up in this module when called.)"""
+    if num_beams > 1:
+        return beam_generate(step, vocab, B, num_beams, device, max_length, start_token_id, eos_token_id, pad_token_id, min_length,
+                             no_repeat_ngram_size, length_penalty, early_stopping, force_eos=force_eos, key_rows=key_rows)[0]
+    return greedy_generate(step, vocab, B, device, max_length, start_token_id, eos_token_id, pad_token_id, min_length,
+                           no_repeat_ngram_size)

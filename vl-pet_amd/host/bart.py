@@ -22,17 +22,19 @@ from __future__ import annotations
 import copy
 import math
 from types import SimpleNamespace
-from typing import Optional
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import attention as A
+from .. import decode as D
 from .. import functional as VF
-from ..adapters import AdapterConfig, AdapterController
+from ..adapters import AdapterConfig
 from ..encoder_pet import apply_pet, build_pet, has_pet
 from ..lora import LoRALinearController, LoraConfig
 from ..visual import Downsample, LowRankVisualEmbedding, VisualEmbedding
+from .common import derived_weights, eval_no_grad, is_key_mask, shift_right, unpack_vis_inputs, value_parallel_adapter
 
 TASKS = ["vqa", "gqa", "nlvr", "caption"]
 
@@ -111,8 +113,7 @@ def _pet_then_tail(layer, which, residual, h, norm, p, training, config, gemm_li
     projection armed (_first_linear): K1's d/dresidual (which already holds the tail's) goes out through it."""
     if not FUSE_RESIDUAL_GRAD:
         return sublayer_tail(residual, apply_pet(layer, which, residual, h, config), norm, p, training)
-    from ..functional import ResidualLink
-    link = ResidualLink()
+    link = VF.ResidualLink()
     y = apply_pet(layer, which, residual, h, config, link=link, out_link=gemm_link)
     return sublayer_tail(residual, y, norm, p, training, link=link)
 
@@ -133,22 +134,19 @@ def _new_gemm_link(x):
     """A link for the first projection of a sublayer whose input is ``x``, or None when nothing would use it."""
     if not (FUSE_RESIDUAL_GRAD and FUSE_GEMM_GRAD) or not x.requires_grad or not torch.is_grad_enabled():
         return None
-    from ..functional import ResidualLink
-    return ResidualLink()
+    return VF.ResidualLink()
 
 
 def _first_linear(mod, x, link):
     """``mod(x)`` for the first projection of a sublayer; with a link and a frozen ``nn.Linear``: functional.linear_acc."""
     if link is not None and _frozen(mod):
-        from ..functional import linear_acc
-        return linear_acc(x, link, mod)
+        return VF.linear_acc(x, link, mod)
     if (link is not None and FUSE_BIAS_GRAD and isinstance(mod, nn.Linear) and not mod.weight.requires_grad and mod.bias is not None
             and mod.bias.requires_grad):
         # frozen weight, trainable bias (the LoRA runs): the same hand-over through the bias-gradient form of the projection
-        from ..functional import linear_train_bias, linear_train_bias_ok
         w = mod.weight if mod.weight.dtype == x.dtype else mod.weight.to(x.dtype)
-        if linear_train_bias_ok(x, w, mod.bias):
-            return linear_train_bias(x, w, mod.bias, link)
+        if VF.linear_train_bias_ok(x, w, mod.bias):
+            return VF.linear_train_bias(x, w, mod.bias, link)
     return _linear(mod, x)
 
 
@@ -200,9 +198,8 @@ def _linear(mod: nn.Linear, x):
     if w.dtype != x.dtype:
         w = w.to(x.dtype)
     if FUSE_BIAS_GRAD and b is not None and b.requires_grad:
-        from ..functional import linear_train_bias, linear_train_bias_ok
-        if linear_train_bias_ok(x, w, b):
-            return linear_train_bias(x, w, b)             # bias gradient = column sums of dy on the HIP path
+        if VF.linear_train_bias_ok(x, w, b):
+            return VF.linear_train_bias(x, w, b)             # bias gradient = column sums of dy on the HIP path
     if b is not None and b.dtype != x.dtype:
         b = b.to(x.dtype)
     return F.linear(x, w, b)
@@ -225,11 +222,8 @@ def attention_core(q, k, v, num_heads, attn_mask, causal, p, training, k_slot=No
     128 tokens in bf16 with head dim 64 (every image-text shape) run on vlpet_amd.attention's on-chip kernels; anything
     else (fp32 parity runs, the 664-token video encoder, non-boolean masks) on torch's SDPA.  The parity / CPU-baseline
     harnesses swap this module attribute for the eager chain."""
-    from .. import attention as A
     B, Lq, E = q.shape
-    boolean_key_mask = attn_mask is None or (attn_mask.dtype == torch.bool and attn_mask.dim() == 4
-                                             and attn_mask.shape[1] == 1 and attn_mask.shape[2] == 1)
-    if not EAGER_ATTENTION and boolean_key_mask and A.supported(q, k, num_heads):
+    if not EAGER_ATTENTION and (attn_mask is None or is_key_mask(attn_mask)) and A.supported(q, k, num_heads):
         km = None if attn_mask is None else attn_mask[:, 0, 0, :]
         return A.short_attention(q, k, v, num_heads, km, causal and attn_mask is None, p, training, k_slot=k_slot)
     sh = lambda t: t.reshape(B, -1, num_heads, E // num_heads).transpose(1, 2)
@@ -265,31 +259,14 @@ class BartAttention(nn.Module):
         self.out_proj = nn.Linear(embed_dim, embed_dim)
         self.attn_value_parallel_adapter = None
         if value_adapter:
-            ac = copy.deepcopy(config.adapter_config)
-            ac.use_adapter_down_dim = True
-            ac.adapter_down_dim = config.decoder_enc_attn_value_parallel_adapter_down_dim
-            ac.use_parallel_adapter = True
-            if config.use_decoder_enc_attn_value_parallel_adapter_scaling:
-                ac.use_scaling_factor = True
-                ac.scaling_factor = config.decoder_enc_attn_value_parallel_adapter_scaling_factor
-            self.attn_value_parallel_adapter = AdapterController(ac)
+            self.attn_value_parallel_adapter = value_parallel_adapter(config)
 
     def _shape(self, t, B):
         return t.view(B, -1, self.num_heads, self.head_dim).transpose(1, 2)
 
     def _fused_qkv(self, dtype):
-        """The frozen q | k | v projections of a self-attention as one [3E, E] weight (a derived cache keyed on the three
-        modules' tensors: rebuilt when any of them changes; never a parameter, the state dict keeps q_proj / k_proj / v_proj)."""
-        mods = (self.q_proj, self.k_proj, self.v_proj)
-        key = tuple((m.weight.data_ptr(), m.weight._version, m.bias.data_ptr(), m.bias._version) for m in mods) + (dtype, VF.FROZEN_EPOCH)
-        c = getattr(self, "_qkv_cache", None)
-        if c is None or c[0] != key:
-            with torch.no_grad():
-                w = torch.cat([m.weight.to(dtype) for m in mods], 0).contiguous()
-                b = torch.cat([m.bias.to(dtype) for m in mods], 0).contiguous()
-            c = (key, w, b)
-            self._qkv_cache = c
-        return c[1], c[2]
+        """The frozen q | k | v projections of a self-attention as one [3E, E] weight and [3E] bias (common.derived_weights)"""
+        return derived_weights(self, "_qkv_cache", (self.q_proj, self.k_proj, self.v_proj), dtype)
 
     def forward(self, hidden, kv=None, attn_mask=None, causal=False, task=None, in_link=None, k_pre=None):
         """``in_link``: see _first_linear -- armed by the projection of ``hidden`` (q|k|v or q_proj) when that is frozen.
@@ -300,16 +277,12 @@ class BartAttention(nn.Module):
         if kv is None and FUSE_QKV and not self.use_lora and not EAGER_ATTENTION:
             # self-attention with frozen projections: one [E -> 3E] GEMM each way, the attention kernels read / write the
             # q | k | v column blocks in place (one input gradient instead of three that autograd would have to sum)
-            from .. import attention as A
             frozen = not any(t.requires_grad for m in (self.q_proj, self.k_proj, self.v_proj) for t in (m.weight, m.bias))
-            boolean_key_mask = attn_mask is None or (attn_mask.dtype == torch.bool and attn_mask.dim() == 4
-                                                     and attn_mask.shape[1] == 1 and attn_mask.shape[2] == 1)
-            if (frozen and boolean_key_mask and hidden.is_cuda and hidden.dtype == torch.bfloat16 and L <= A.MAX_LEN
-                    and self.head_dim == A.HEAD_DIM):
+            if (frozen and (attn_mask is None or is_key_mask(attn_mask)) and hidden.is_cuda and hidden.dtype == torch.bfloat16
+                    and L <= A.MAX_LEN and self.head_dim == A.HEAD_DIM):
                 w, b = self._fused_qkv(hidden.dtype)
                 if in_link is not None:
-                    from ..functional import linear_acc
-                    qkv = linear_acc(hidden, in_link, (w, b))
+                    qkv = VF.linear_acc(hidden, in_link, (w, b))
                 else:
                     qkv = F.linear(hidden, w, b)
                 km = None if attn_mask is None else attn_mask[:, 0, 0, :]
@@ -324,12 +297,11 @@ class BartAttention(nn.Module):
             q = _first_linear(self.q_proj, hidden, in_link)
             kv_link = _new_gemm_link(src) if (kv is not None and _frozen(self.k_proj, self.v_proj)) else None
             if kv_link is not None:
-                from ..functional import linear_acc
                 k_slot = None
                 if k_pre is not None:
-                    (k, k_slot), v = k_pre, linear_acc(src, kv_link, self.v_proj)
+                    (k, k_slot), v = k_pre, VF.linear_acc(src, kv_link, self.v_proj)
                 else:
-                    k, v = linear_acc(src, kv_link, self.k_proj, self.v_proj)      # one gradient for the encoder output, K2's included
+                    k, v = VF.linear_acc(src, kv_link, self.k_proj, self.v_proj)      # one gradient for the encoder output, K2's included
                 if self.attn_value_parallel_adapter is not None:
                     v = self.attn_value_parallel_adapter(src, task, y=v, link=kv_link)
                 out = attention_core(q, k, v, self.num_heads, attn_mask, causal, self.dropout, self.training, k_slot=k_slot)
@@ -357,10 +329,9 @@ class BartAttention(nn.Module):
     def step_self(self, x, k_cache, v_cache, pos, task=None, key_rows=None):
         """causal self-attention of the token at ``pos``: its key / value rows go into cache row ``pos`` inside the attention launch
         (beam search: earlier keys are looked up through ``key_rows``)"""
-        from ..decode import decode_attention
         q, k, v = self._step_qkv(x, task)
-        out = decode_attention(q, k_cache, v_cache, self.num_heads, pos=pos, k_new=k, v_new=v, scale=self.head_dim ** -0.5,
-                               key_rows=key_rows)
+        out = D.decode_attention(q, k_cache, v_cache, self.num_heads, pos=pos, k_new=k, v_new=v, scale=self.head_dim ** -0.5,
+                                 key_rows=key_rows)
         return _linear(self.out_proj, out[:, None])
 
     def cross_values(self, enc, task=None):
@@ -372,10 +343,9 @@ class BartAttention(nn.Module):
         return v
 
     def step_cross(self, x, k_cache, v_cache, key_mask, task=None, group=1):
-        from ..decode import decode_attention
         q = self.q_proj(x, task) if self.use_lora else _linear(self.q_proj, x)
-        out = decode_attention(q[:, 0], k_cache, v_cache, self.num_heads, key_mask=key_mask, scale=self.head_dim ** -0.5,
-                               group=group)
+        out = D.decode_attention(q[:, 0], k_cache, v_cache, self.num_heads, key_mask=key_mask, scale=self.head_dim ** -0.5,
+                                 group=group)
         return _linear(self.out_proj, out[:, None])
 
 
@@ -449,14 +419,14 @@ class BartDecoderLayer(nn.Module):
         return _tail_linked(residual, h, self.final_layer_norm, self.dropout, self.training, gl)             # K5
 
 
-    def step(self, x, cache, pos, task=None):
-        """generate(): the token x [B, 1, d] at position ``pos``; ``cache`` = (self k, self v, cross k, cross v, cross key mask[,
-        beams per item, ping-pong key-row tables]) -- beam search adds the last two (decode.beam_key_rows)"""
-        ks, vs, kx, vx, km = cache[:5]
-        group, kr = cache[5:] if len(cache) > 5 else (1, None)
+    def step(self, x, cache, pos, state, task=None):
+        """generate(): the token x [B, 1, d] at position ``pos``; ``cache`` = this layer's (self k, self v, cross k, cross v) of
+        ``state`` (decode.DecodeState)"""
+        ks, vs, kx, vx = cache
+        kr = state.key_rows
         h = self.self_attn.step_self(x, ks, vs, pos, task, key_rows=None if kr is None else kr[pos & 1])
         x = sublayer_tail(x, h, self.self_attn_layer_norm, self.dropout, self.training)                     # K5
-        h = self.encoder_attn.step_cross(x, kx, vx, km, task, group=group)
+        h = self.encoder_attn.step_cross(x, kx, vx, state.key_mask, task, group=state.group)
         x = sublayer_tail(x, h, self.encoder_attn_layer_norm, self.dropout, self.training)                  # K5
         h = ffn_activation(_linear(self.fc1, x), "gelu", self.activation_dropout, self.training)
         return sublayer_tail(x, _linear(self.fc2, h), self.final_layer_norm, self.dropout, self.training)   # K5
@@ -499,16 +469,7 @@ class JointEncoder(nn.Module):
             # row has the full length -- true for the synthetic batches), which keeps attention on the unmasked path
             attention_mask = input_ids.ne(self.config.pad_token_id)
         x = self.embed_tokens(input_ids) * self.embed_scale + self.embed_positions(L, input_ids.device)
-        if self.downsample is not None:
-            # fp32 CLIP features -> compute dtype inside the pooling kernel (rounding is monotone:
-            # pool(round(f)) == round(pool(f)))
-            vis_inputs = self.downsample(vis_inputs, out_dtype=x.dtype)
-        elif vis_inputs[0].dtype != x.dtype:
-            vis_inputs = (vis_inputs[0].to(x.dtype),) + tuple(vis_inputs[1:])
-        feats, boxes = vis_inputs[0], vis_inputs[1]
-        img_ids = vis_inputs[2] if len(vis_inputs) >= 3 else None
-        obj_ids = vis_inputs[3] if len(vis_inputs) == 4 else None
-        vis = self.visual_embedding(feats, boxes, img_ids, obj_ids).to(x.dtype)   # K4
+        vis = self.visual_embedding(*unpack_vis_inputs(vis_inputs, self.downsample, x.dtype)).to(x.dtype)   # K4
         if self.config.share_vis_lang_layer_norm:
             x = self.layernorm_embedding(torch.cat([x, vis], dim=1))
             x = F.dropout(x, p=self.dropout, training=self.training)
@@ -540,10 +501,9 @@ class BartDecoder(nn.Module):
         B, L = input_ids.shape
         x = self.embed_tokens(input_ids) * self.embed_scale + self.embed_positions(L, input_ids.device)
         x = F.dropout(self.layernorm_embedding(x), p=self.dropout, training=self.training)
-        from ..functional import fanout
         n = len(self.layers)
         fused_keys = self._cross_keys_ok(enc, enc_mask)
-        encs = fanout(enc, n + (1 if fused_keys else 0))        # one gradient sum for the encoder output instead of autograd's pairwise adds
+        encs = VF.fanout(enc, n + (1 if fused_keys else 0))        # one gradient sum for the encoder output instead of autograd's pairwise adds
         ks = self._cross_keys(encs[n]) if fused_keys else None
         for i, (layer, e) in enumerate(zip(self.layers, encs)):
             x = layer(x, e, enc_mask, task, k_pre=None if ks is None else (ks[0][i], None if ks[1] is None else (ks[1], i)))
@@ -552,54 +512,37 @@ class BartDecoder(nn.Module):
     def _cross_keys_ok(self, enc, enc_mask) -> bool:
         """The layers' cross-attention key projections as ONE GEMM (functional.cross_key_blocks): frozen plain projections, bf16 on the
         GPU, a shape the short-sequence attention kernels take (they read a layer's keys as a column block in place)."""
-        from .. import attention as A
         if not FUSE_CROSS_KEYS or EAGER_ATTENTION or len(self.layers) < 2 or not enc.is_cuda or enc.dtype != torch.bfloat16:
             return False
         a0 = self.layers[0].encoder_attn
         if enc.shape[1] > A.MAX_LEN or a0.head_dim != A.HEAD_DIM:
             return False
-        if enc_mask is not None and not (enc_mask.dtype == torch.bool and enc_mask.dim() == 4 and enc_mask.shape[1] == 1 and enc_mask.shape[2] == 1):
+        if enc_mask is not None and not is_key_mask(enc_mask):
             return False
         return all((not l.encoder_attn.use_lora) and _frozen(l.encoder_attn.k_proj, l.encoder_attn.v_proj) for l in self.layers)
 
     def _cross_keys(self, enc):
-        from .. import functional as VF
-        mods = [l.encoder_attn.k_proj for l in self.layers]
-        key = (enc.dtype, VF.FROZEN_EPOCH) + tuple((m.weight.data_ptr(), m.weight._version, m.bias.data_ptr(), m.bias._version) for m in mods)
-        c = getattr(self, "_ck_cache", None)
-        if c is None or c[0] != key:
-            with torch.no_grad():
-                w = torch.cat([m.weight.to(enc.dtype) for m in mods], 0).contiguous()
-                b = torch.cat([m.bias.to(enc.dtype) for m in mods], 0).contiguous()
-            c = self._ck_cache = (key, w, b)
-        return VF.cross_key_blocks(enc, c[1], c[2], len(mods))
+        w, b = derived_weights(self, "_ck_cache", [l.encoder_attn.k_proj for l in self.layers], enc.dtype)
+        return VF.cross_key_blocks(enc, w, b, len(self.layers))
 
 
     def init_cache(self, enc, key_mask, task, max_length, num_beams=1):
-        """generate(): per layer a self-attention key / value cache [B, max_length, E] (one allocation) and the cross-attention
-        caches of ``enc``: keys as column blocks of ONE fused projection where the layers allow it, values through K2 / K3 once.
-        ``num_beams`` K > 1: the self-attention caches have B * K rows, the cross-attention ones stay per item, and every layer's
-        tuple ends with (K, the shared ping-pong key-row tables)."""
-        from ..decode import beam_key_rows
-        B, _, E = enc.shape
-        n = len(self.layers)
-        selfc = enc.new_empty(n, 2, B * num_beams, max_length, E)
-        if FUSE_CROSS_KEYS and not EAGER_ATTENTION and n >= 2 and enc.is_cuda:
+        """generate(): the decode.DecodeState of a call over ``enc``: the cross-attention keys as column blocks of ONE fused
+        projection where the layers allow it, the values through K2 / K3 once; ``num_beams`` K > 1: self-attention caches of B * K
+        rows, the cross-attention ones stay per item."""
+        if FUSE_CROSS_KEYS and not EAGER_ATTENTION and len(self.layers) >= 2 and enc.is_cuda:
             ks = self._cross_keys(enc)[0]
         else:
             ks = [_linear(l.encoder_attn.k_proj, enc) for l in self.layers]
         vs = [l.encoder_attn.cross_values(enc, task) for l in self.layers]
-        if num_beams > 1:
-            kr = beam_key_rows(B * num_beams, max_length, enc.device)
-            return [(selfc[i, 0], selfc[i, 1], ks[i], vs[i], key_mask, num_beams, kr) for i in range(n)]
-        return [(selfc[i, 0], selfc[i, 1], ks[i], vs[i], key_mask) for i in range(n)]
+        return D.new_decode_state(enc, enc.shape[2], max_length, ks, vs, key_mask, num_beams)
 
-    def step(self, tok, pos, caches, task=None):
+    def step(self, tok, pos, state, task=None):
         """generate(): hidden state [B, d] of the tokens ``tok`` [B] at position ``pos`` (learned position pos + 2)"""
         x = self.embed_tokens(tok)[:, None] * self.embed_scale + self.embed_positions.weight[pos + 2]
         x = F.dropout(self.layernorm_embedding(x), p=self.dropout, training=self.training)
-        for layer, c in zip(self.layers, caches):
-            x = layer.step(x, c, pos, task)
+        for layer, c in zip(self.layers, state.layers):
+            x = layer.step(x, c, pos, state, task)
         return x[:, 0]
 
 
@@ -611,11 +554,7 @@ class VLBartModel(nn.Module):
         self.decoder = BartDecoder(config, self.shared)
 
 
-def shift_tokens_right(labels, pad_id, start_id):
-    out = labels.new_zeros(labels.shape)
-    out[:, 1:] = labels[:, :-1]
-    out[:, 0] = start_id
-    return out.masked_fill(out == -100, pad_id)
+shift_tokens_right = shift_right
 
 
 class VLBart(nn.Module):
@@ -671,34 +610,23 @@ class VLBart(nn.Module):
         ``num_beams`` > 1: HF 4.2.1 beam search (one sequence per item; the video captioning evaluation, src/multitask_video.py)
         with ``length_penalty`` / ``early_stopping``, BART's forced eos at the last step, and the cross-attention caches kept per
         item (decode.beam_generate, which also returns each sequence's score)."""
-        from ..decode import beam_generate, greedy_generate
         from ..lmloss import _padded_head
         cfg = self.config
         eos = getattr(cfg, "eos_token_id", 2) if eos_token_id is None else eos_token_id
         pad = cfg.pad_token_id if pad_token_id is None else pad_token_id
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                enc, mask = self.model.encoder(input_ids, vis_inputs, attention_mask, task, no_padding)
-                key_mask = None if mask is None else mask[:, 0, 0, :].contiguous()
-                dec = self.model.decoder
-                K = int(num_beams)
-                caches = dec.init_cache(enc, key_mask, task, max_length, num_beams=K)
-                V = self.model.shared.weight.shape[0]
-                head = _padded_head(self.model.shared.weight, enc.dtype)
-                bias = self._logits_bias()
+        with eval_no_grad(self):
+            enc, mask = self.model.encoder(input_ids, vis_inputs, attention_mask, task, no_padding)
+            key_mask = None if mask is None else mask[:, 0, 0, :].contiguous()
+            dec = self.model.decoder
+            state = dec.init_cache(enc, key_mask, task, max_length, num_beams=int(num_beams))
+            V = self.model.shared.weight.shape[0]
+            head = _padded_head(self.model.shared.weight, enc.dtype)
+            bias = self._logits_bias()
 
-                def step(tok, pos):
-                    logits = F.linear(dec.step(tok, pos, caches, task), head)
-                    if bias is not None:
-                        logits[:, :V] += bias[0].to(logits.dtype)
-                    return logits
-                if K > 1:
-                    return beam_generate(step, V, enc.shape[0], K, enc.device, max_length, cfg.decoder_start_token_id, eos, pad,
-                                         min_length, no_repeat_ngram_size, length_penalty, early_stopping, force_eos=True,
-                                         key_rows=caches[0][6])[0]
-                return greedy_generate(step, V, enc.shape[0], enc.device, max_length, cfg.decoder_start_token_id, eos, pad,
-                                       min_length, no_repeat_ngram_size)
-        finally:
-            self.train(was_training)
+            def step(tok, pos):
+                logits = F.linear(dec.step(tok, pos, state, task), head)
+                if bias is not None:
+                    logits[:, :V] += bias[0].to(logits.dtype)
+                return logits
+            return D.generate(step, V, enc.shape[0], enc.device, state.key_rows, cfg.decoder_start_token_id, eos, pad, max_length,
+                              min_length, no_repeat_ngram_size, int(num_beams), length_penalty, early_stopping, force_eos=True)

@@ -20,11 +20,14 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from .. import attention as A
+from .. import decode as D
 from .. import functional as VF
-from ..adapters import AdapterConfig, AdapterController
+from ..adapters import AdapterConfig
 from ..encoder_pet import apply_pet, build_pet, has_pet
 from ..visual import Downsample, T5LayerNorm, VisualEmbedding
 from .bart import TASKS, _linear
+from .common import derived_weights, eval_no_grad, shift_right, unpack_vis_inputs, value_parallel_adapter
 
 
 # K1's gate and the sublayer tail both read the sublayer input; with a link the tail's backward hands its d/dx1 to K1's
@@ -38,8 +41,7 @@ def _pet_then_tail(layer, which, residual, h, norm, p, training, config, norm_li
     (which read ``residual`` first): K1's d/dresidual -- the tail's included -- goes out through it."""
     if not FUSE_RESIDUAL_GRAD:
         return sublayer_tail(residual, apply_pet(layer, which, residual, h, config), norm, p, training)
-    from ..functional import ResidualLink
-    link = ResidualLink()
+    link = VF.ResidualLink()
     y = apply_pet(layer, which, residual, h, config, link=link, out_link=norm_link)
     nxt = _fused_tail_ok(layer, y) if norm is None else None
     if nxt is not None:
@@ -60,8 +62,7 @@ def _new_norm_link(x):
         return fused.link
     if not (FUSE_RESIDUAL_GRAD and FUSE_NORM_GRAD) or not x.is_cuda or not x.requires_grad or not torch.is_grad_enabled():
         return None
-    from ..functional import ResidualLink
-    return ResidualLink()
+    return VF.ResidualLink()
 
 
 def _normed(norm, hidden, link):
@@ -213,7 +214,6 @@ class AttnSpec:
         if self.rel_trainable:
             return None
         if self._fast is None:
-            from .. import attention as A
             bias = A.AttnBias(self.rel) if self.rel is not None else None
             km = None if self.keep is None else (self.keep > 0.5).to(torch.uint8).contiguous()
             self._fast = (bias, km)
@@ -238,14 +238,7 @@ class T5Attention(nn.Module):
         self.o = nn.Linear(self.inner, d, bias=False)
         self.attn_value_parallel_adapter = None
         if value_adapter:
-            ac = copy.deepcopy(config.adapter_config)
-            ac.use_adapter_down_dim = True
-            ac.adapter_down_dim = config.decoder_enc_attn_value_parallel_adapter_down_dim
-            ac.use_parallel_adapter = True
-            if config.use_decoder_enc_attn_value_parallel_adapter_scaling:
-                ac.use_scaling_factor = True
-                ac.scaling_factor = config.decoder_enc_attn_value_parallel_adapter_scaling_factor
-            self.attn_value_parallel_adapter = AdapterController(ac)
+            self.attn_value_parallel_adapter = value_parallel_adapter(config)
         self.has_relative_attention_bias = has_relative_attention_bias
         if has_relative_attention_bias:
             self.relative_attention_bias = nn.Embedding(self.num_buckets, self.n_heads)
@@ -261,23 +254,13 @@ class T5Attention(nn.Module):
         return t.view(B, -1, self.n_heads, self.d_kv).transpose(1, 2)
 
     def _fused_qkv(self, dtype):
-        """The frozen q | k | v projections of a self-attention as one [3 inner, d] weight (as host/bart.py: a derived cache keyed on the
-        three modules' tensors, never a parameter -- the state dict keeps q / k / v)."""
-        mods = (self.q, self.k, self.v)
-        key = tuple((m.weight.data_ptr(), m.weight._version) for m in mods) + (dtype, VF.FROZEN_EPOCH)
-        c = getattr(self, "_qkv_cache", None)
-        if c is None or c[0] != key:
-            with torch.no_grad():
-                w = torch.cat([m.weight.to(dtype) for m in mods], 0).contiguous()
-            c = (key, w)
-            self._qkv_cache = c
-        return c[1]
+        """The frozen q | k | v projections of a self-attention as one [3 inner, d] weight (common.derived_weights; T5 has no biases)"""
+        return derived_weights(self, "_qkv_cache", (self.q, self.k, self.v), dtype)[0]
 
     def forward(self, hidden, bias, kv=None, task=None, k_pre=None):
-        """``k_pre`` = (k, k_slot): this block's cross-attention keys, a column block of the decoder's fused key projection (T5Stack._cross_keys)"""
+        """``k_pre`` = (k, k_slot): this block's cross-attention keys, a column block of the decoder's fused key projection (T5Decoder._cross_keys)"""
         B, Lq, _ = hidden.shape
         src = hidden if kv is None else kv
-        from .. import attention as A
         k_slot = None
         spec = bias if isinstance(bias, AttnSpec) else None
         if (kv is None and FUSE_QKV and spec is not None and not EAGER_ATTENTION and hidden.is_cuda and hidden.dtype == torch.bfloat16
@@ -289,8 +272,7 @@ class T5Attention(nn.Module):
                 # input gradient instead of three (at the per-rank batch of an 8-GPU run each of those GEMMs is a ~9 us launch)
                 w = self._fused_qkv(hidden.dtype)
                 if FUSE_RESIDUAL_GRAD and FUSE_NORM_GRAD and torch.is_grad_enabled() and hidden.requires_grad:
-                    from ..functional import linear_acc
-                    qkv = linear_acc(hidden, None, (w, None))
+                    qkv = VF.linear_acc(hidden, None, (w, None))
                 else:
                     qkv = F.linear(hidden, w)
                 out = A.short_self_attention(qkv, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0, bias=fast[0])
@@ -300,16 +282,15 @@ class T5Attention(nn.Module):
         if fused:
             # the projections that read one tensor are ONE autograd node whose dgrad GEMMs accumulate into one gradient
             # (functional.linear_acc): q | k | v of a self-attention; k | v of a cross-attention, onto K2's parked d/dsrc
-            from ..functional import ResidualLink, linear_acc
             if kv is None:
-                q, k, v = linear_acc(hidden, None, self.q, self.k, self.v)
+                q, k, v = VF.linear_acc(hidden, None, self.q, self.k, self.v)
             else:
                 q = _linear(self.q, hidden)
-                kv_link = ResidualLink() if self.attn_value_parallel_adapter is not None else None
+                kv_link = VF.ResidualLink() if self.attn_value_parallel_adapter is not None else None
                 if k_pre is not None:
-                    (k, k_slot), v = k_pre, linear_acc(src, kv_link, self.v)
+                    (k, k_slot), v = k_pre, VF.linear_acc(src, kv_link, self.v)
                 else:
-                    k, v = linear_acc(src, kv_link, self.k, self.v)
+                    k, v = VF.linear_acc(src, kv_link, self.k, self.v)
                 if self.attn_value_parallel_adapter is not None:
                     v = self.attn_value_parallel_adapter(src, task, y=v, link=kv_link)    # K2
         else:
@@ -332,15 +313,14 @@ class T5Attention(nn.Module):
     def step_self(self, n, k_cache, v_cache, pos, bias_row, key_rows=None):
         """causal self-attention of the normed token n [B, 1, d] at ``pos``; ``bias_row`` [H, >= pos + 1]: row ``pos`` of the
         decoder's relative position bias"""
-        from ..decode import decode_attention
         E = self.inner
         if FUSE_QKV:
             qkv = F.linear(n[:, 0], self._fused_qkv(n.dtype))
             q, k, v = qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
         else:
             q, k, v = _linear(self.q, n)[:, 0], _linear(self.k, n)[:, 0], _linear(self.v, n)[:, 0]
-        out = decode_attention(q, k_cache, v_cache, self.n_heads, pos=pos, k_new=k, v_new=v, bias=bias_row, scale=1.0,
-                               key_rows=key_rows)
+        out = D.decode_attention(q, k_cache, v_cache, self.n_heads, pos=pos, k_new=k, v_new=v, bias=bias_row, scale=1.0,
+                                 key_rows=key_rows)
         return _linear(self.o, out[:, None])
 
     def cross_values(self, enc, task=None):
@@ -351,8 +331,7 @@ class T5Attention(nn.Module):
         return v
 
     def step_cross(self, n, k_cache, v_cache, key_mask, group=1):
-        from ..decode import decode_attention
-        out = decode_attention(_linear(self.q, n)[:, 0], k_cache, v_cache, self.n_heads, key_mask=key_mask, scale=1.0, group=group)
+        out = D.decode_attention(_linear(self.q, n)[:, 0], k_cache, v_cache, self.n_heads, key_mask=key_mask, scale=1.0, group=group)
         return _linear(self.o, out[:, None])
 
 
@@ -433,16 +412,16 @@ class T5Block(nn.Module):
         return self.layer[-1](hidden, task)
 
 
-def _block_step(blk, x, cache, pos, bias_row):
-    """generate(): one decoder block on the token x [B, 1, d]; ``cache`` = (self k, self v, cross k, cross v, cross key mask[, beams
-    per item, ping-pong key-row tables]).  The tails are forward's (_tail_linked: on the GPU each fused with the next sublayer's
-    norm)."""
+def _block_step(blk, x, cache, pos, state, bias_row):
+    """generate(): one decoder block on the token x [B, 1, d]; ``cache`` = this block's (self k, self v, cross k, cross v) of ``state``
+    (decode.DecodeState), ``bias_row`` = row ``pos`` of its bias table.  The tails are forward's (_tail_linked: on the GPU each fused
+    with the next sublayer's norm)."""
     sa, ca, ff = blk.layer[0], blk.layer[1], blk.layer[-1]
-    ks, vs, kx, vx, km = cache[:5]
-    group, kr = cache[5:] if len(cache) > 5 else (1, None)
+    ks, vs, kx, vx = cache
+    kr = state.key_rows
     y = sa.SelfAttention.step_self(sa.layer_norm(x), ks, vs, pos, bias_row, key_rows=None if kr is None else kr[pos & 1])
     x = _tail_linked(x, y, sa.p, sa.training, None, layer=sa)
-    y = ca.EncDecAttention.step_cross(ca.layer_norm(x), kx, vx, km, group=group)
+    y = ca.EncDecAttention.step_cross(ca.layer_norm(x), kx, vx, state.key_mask, group=state.group)
     x = _tail_linked(x, y, ca.p, ca.training, None, layer=ca)
     y = ff.DenseReluDense(ff.layer_norm(x))
     return _tail_linked(x, y, ff.p, ff.training, None, layer=ff)
@@ -472,14 +451,7 @@ class JointEncoder(nn.Module):
     def forward(self, input_ids, vis_inputs, attention_mask=None, task=None):
         B, L = input_ids.shape
         x = self.embed_tokens(input_ids)
-        if self.downsample is not None:
-            vis_inputs = self.downsample(vis_inputs, out_dtype=x.dtype)
-        elif vis_inputs[0].dtype != x.dtype:
-            vis_inputs = (vis_inputs[0].to(x.dtype),) + tuple(vis_inputs[1:])
-        feats, boxes = vis_inputs[0], vis_inputs[1]
-        img_ids = vis_inputs[2] if len(vis_inputs) >= 3 else None
-        obj_ids = vis_inputs[3] if len(vis_inputs) == 4 else None
-        vis = self.visual_embedding(feats, boxes, img_ids, obj_ids).to(x.dtype)             # K4
+        vis = self.visual_embedding(*unpack_vis_inputs(vis_inputs, self.downsample, x.dtype)).to(x.dtype)             # K4
         V = vis.shape[1]
         from ..act import concat_dropout
         x = concat_dropout(x, vis, self.p, self.training)      # cat + dropout (src/modeling_t5.py:263, 300): one pass each way
@@ -510,7 +482,6 @@ class T5Decoder(nn.Module):
 
     def _cross_keys_ok(self, enc, cross_bias) -> bool:
         """The blocks' cross-attention key projections as ONE GEMM (functional.cross_key_blocks; host/bart.py BartDecoder._cross_keys_ok)"""
-        from .. import attention as A
         if not FUSE_CROSS_KEYS or EAGER_ATTENTION or len(self.block) < 2 or not enc.is_cuda or enc.dtype != torch.bfloat16:
             return False
         if not (FUSE_RESIDUAL_GRAD and FUSE_NORM_GRAD and torch.is_grad_enabled() and enc.requires_grad):
@@ -521,14 +492,8 @@ class T5Decoder(nn.Module):
         return not any(m.weight.requires_grad or m.bias is not None for a in atts for m in (a.q, a.k, a.v))
 
     def _cross_keys(self, enc):
-        mods = [blk.layer[1].EncDecAttention.k for blk in self.block]
-        key = (enc.dtype, VF.FROZEN_EPOCH) + tuple((m.weight.data_ptr(), m.weight._version) for m in mods)
-        c = getattr(self, "_ck_cache", None)
-        if c is None or c[0] != key:
-            with torch.no_grad():
-                w = torch.cat([m.weight.to(enc.dtype) for m in mods], 0).contiguous()
-            c = self._ck_cache = (key, w)
-        return VF.cross_key_blocks(enc, c[1], None, len(mods))
+        w, _ = derived_weights(self, "_ck_cache", [blk.layer[1].EncDecAttention.k for blk in self.block], enc.dtype)
+        return VF.cross_key_blocks(enc, w, None, len(self.block))
 
     def forward(self, input_ids, enc, enc_keep, task=None):
         B, L = input_ids.shape
@@ -537,10 +502,9 @@ class T5Decoder(nn.Module):
         self_bias = AttnSpec(sa0.compute_bias(L, L), None, causal=True,
                              rel_trainable=sa0.relative_attention_bias.weight.requires_grad and torch.is_grad_enabled())
         cross_bias = AttnSpec(None, enc_keep, causal=False)      # (dense form: invert_attention_mask, (1 - keep) * -1e9 in fp32)
-        from ..functional import fanout
         n = len(self.block)
         fused_keys = self._cross_keys_ok(enc, cross_bias)
-        encs = fanout(enc, n + (1 if fused_keys else 0))         # one gradient sum for the encoder output instead of autograd's pairwise adds
+        encs = VF.fanout(enc, n + (1 if fused_keys else 0))         # one gradient sum for the encoder output instead of autograd's pairwise adds
         ks = self._cross_keys(encs[n]) if fused_keys else None
         for i, (blk, e) in enumerate(zip(self.block, encs)):
             x = blk(x, self_bias, e, cross_bias, task, k_pre=None if ks is None else (ks[0][i], None if ks[1] is None else (ks[1], i)))
@@ -548,42 +512,25 @@ class T5Decoder(nn.Module):
 
 
     def init_cache(self, enc, key_mask, task, max_length, num_beams=1):
-        """generate(): self-attention caches [B, max_length, inner] per block (one allocation), cross-attention caches of ``enc`` (keys
-        as column blocks of ONE fused projection on the GPU), and the relative position bias of every query position as a
-        [max_length, H, max_length] fp32 table (row ``pos`` = compute_bias(max_length, max_length)[0, :, pos]).  ``num_beams`` > 1:
-        as host/bart.py BartDecoder.init_cache (self-attention caches of B * K rows, (K, key-row tables) ending every tuple)"""
-        from ..decode import beam_key_rows
-        B, _, _ = enc.shape
-        n = len(self.block)
-        inner = self.block[0].layer[0].SelfAttention.inner
-        selfc = enc.new_empty(n, 2, B * num_beams, max_length, inner)
+        """generate(): the decode.DecodeState of a call over ``enc`` (as host/bart.py BartDecoder.init_cache: the cross-attention keys
+        as column blocks of ONE fused projection on the GPU), with the relative position bias of every query position as its
+        [max_length, H, max_length] fp32 table (row ``pos`` = compute_bias(max_length, max_length)[0, :, pos])."""
         atts = [blk.layer[1].EncDecAttention for blk in self.block]
-        if FUSE_CROSS_KEYS and not EAGER_ATTENTION and n >= 2 and enc.is_cuda:
+        if FUSE_CROSS_KEYS and not EAGER_ATTENTION and len(atts) >= 2 and enc.is_cuda:
             ks = self._cross_keys(enc)[0]
         else:
             ks = [_linear(a.k, enc) for a in atts]
         vs = [a.cross_values(enc, task) for a in atts]
-        rel = self.block[0].layer[0].SelfAttention.compute_bias(max_length, max_length)[0]        # [H, q, k]
-        table = rel.permute(1, 0, 2).float().contiguous()
-        if num_beams > 1:
-            kr = beam_key_rows(B * num_beams, max_length, enc.device)
-            return [(selfc[i, 0], selfc[i, 1], ks[i], vs[i], key_mask, num_beams, kr) for i in range(n)], table
-        return [(selfc[i, 0], selfc[i, 1], ks[i], vs[i], key_mask) for i in range(n)], table
+        sa0 = self.block[0].layer[0].SelfAttention
+        table = sa0.compute_bias(max_length, max_length)[0].permute(1, 0, 2).float().contiguous()        # [H, q, k] -> [q, H, k]
+        return D.new_decode_state(enc, sa0.inner, max_length, ks, vs, key_mask, num_beams, bias_table=table)
 
     def step(self, tok, pos, state):
-        caches, table = state
         x = F.dropout(self.embed_tokens(tok)[:, None], p=self.p, training=self.training)
-        for blk, c in zip(self.block, caches):
-            x = _block_step(blk, x, c, pos, table[pos])
+        bias_row = state.bias_table[pos]
+        for blk, c in zip(self.block, state.layers):
+            x = _block_step(blk, x, c, pos, state, bias_row)
         return F.dropout(self.final_layer_norm(x), p=self.p, training=self.training)[:, 0]
-
-
-def shift_right(labels, pad_id, start_id):
-    """T5PreTrainedModel._shift_right (my_transformers/modeling_t5.py:1068-1087)."""
-    out = labels.new_zeros(labels.shape)
-    out[:, 1:] = labels[:, :-1]
-    out[:, 0] = start_id
-    return out.masked_fill(out == -100, pad_id)
 
 
 class VLT5(nn.Module):
@@ -631,30 +578,18 @@ class VLT5(nn.Module):
         """Greedy search with HF 4.2.1 semantics on per-block key / value caches (see host/bart.py VLBart.generate).  eos / pad
         default to T5's 1 / 0; the output starts with decoder_start_token_id (0).  ``num_beams`` > 1: HF 4.2.1 beam search as in
         VLBart.generate (T5 forces no eos)."""
-        from ..decode import beam_generate, greedy_generate
         from ..lmloss import _padded_head
         cfg = self.config
         eos = getattr(cfg, "eos_token_id", 1) if eos_token_id is None else eos_token_id
         pad = cfg.pad_token_id if pad_token_id is None else pad_token_id
-        was_training = self.training
-        self.eval()
-        try:
-            with torch.no_grad():
-                enc, keep = self.encoder(input_ids, vis_inputs, attention_mask, task)
-                key_mask = (keep > 0.5).contiguous()
-                K = int(num_beams)
-                state = self.decoder.init_cache(enc, key_mask, task, max_length, num_beams=K)
-                V = self.shared.weight.shape[0]
-                head = _padded_head(self.shared.weight, enc.dtype)
-                scale = cfg.d_model ** -0.5
+        with eval_no_grad(self):
+            enc, keep = self.encoder(input_ids, vis_inputs, attention_mask, task)
+            state = self.decoder.init_cache(enc, (keep > 0.5).contiguous(), task, max_length, num_beams=int(num_beams))
+            V = self.shared.weight.shape[0]
+            head = _padded_head(self.shared.weight, enc.dtype)
+            scale = cfg.d_model ** -0.5
 
-                def step(tok, pos):
-                    return F.linear(self.decoder.step(tok, pos, state) * scale, head)
-                if K > 1:
-                    return beam_generate(step, V, enc.shape[0], K, enc.device, max_length, cfg.decoder_start_token_id, eos, pad,
-                                         min_length, no_repeat_ngram_size, length_penalty, early_stopping,
-                                         key_rows=state[0][0][6])[0]
-                return greedy_generate(step, V, enc.shape[0], enc.device, max_length, cfg.decoder_start_token_id, eos, pad,
-                                       min_length, no_repeat_ngram_size)
-        finally:
-            self.train(was_training)
+            def step(tok, pos):
+                return F.linear(self.decoder.step(tok, pos, state) * scale, head)
+            return D.generate(step, V, enc.shape[0], enc.device, state.key_rows, cfg.decoder_start_token_id, eos, pad, max_length,
+                              min_length, no_repeat_ngram_size, int(num_beams), length_penalty, early_stopping, force_eos=False)
