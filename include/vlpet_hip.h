@@ -630,8 +630,9 @@ int vlpet_adamw_step_sliced(float* p, float* g, float* m, float* v, const uint8_
  *   projection [B, Lk, n_layers * H*D]), o [B, H*D] (ld_o).  k_new / v_new [B, H*D] (row stride ld_new) given: written into cache
  *   row `pos` (0 <= pos < Lk), keys 0..pos attended (self-attention step); NULL: keys 0..Lk-1.  key_mask [B, Lk] u8 (row stride
  *   ld_mask, 0 = masked) and bias [H, Lk] fp32 (head stride ld_bias: T5's relative position bias row of the query position) are
- *   optional.  D = 16 or 64, Lk <= 1024, io_dtype bf16 / fp32, softmax in fp32.  Tensor pointers 16-byte aligned, strides
- *   multiples of 8 elements.
+ *   optional.  A -inf bias entry means "excluded", exactly like a masked key; a row whose keys are all excluded (by the mask, the
+ *   bias or both) gets zeros.  D = 16 or 64, Lk <= 1024, io_dtype bf16 / fp32, softmax in fp32.  Tensor pointers 16-byte aligned,
+ *   strides multiples of 8 elements.
  * vlpet_greedy_pick: per row b of logits [B, ld] (columns >= V ignored; ld >= V rounded up to 8, V <= 65536): ban eos while
  *   pos + 1 < min_length, ban the tokens that would repeat an n-gram of ids[b, 0..pos] (n = no_repeat_ngram_size, 0 = off), take
  *   the argmax (lowest index on ties), emit pad instead when unfinished[b] == 0, write ids[b, pos + 1] (int64, row stride ld_ids),

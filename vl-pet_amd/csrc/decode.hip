@@ -122,9 +122,10 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(DecodeAttnA
             for (int d = 0; d < 8; ++d) s = fmaf(qf[d], kr[u].get(d), s);
 #pragma unroll
             for (int o = 1; o < LPK; o <<= 1) s += __shfl_xor(s, o);
-            const bool ok = j < n && (mrow == nullptr || mrow[j] != 0);
-            if (ok) {
-                if (brow != nullptr) s += brow[j];
+            bool ok = j < n && (mrow == nullptr || mrow[j] != 0);
+            if (ok && brow != nullptr) s += brow[j];
+            ok = ok && s != -INFINITY;                           // (a -inf bias entry excludes the key, like the mask:
+            if (ok) {                                            //  with m = -inf it would make exp(m - mn) a NaN)
                 const float mn = fmaxf(m, s);
                 const float c = __expf(m - mn);                  // (m = -inf before the first key: c = 0)
                 const float p = __expf(s - mn);

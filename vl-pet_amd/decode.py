@@ -63,6 +63,8 @@ def decode_attention(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tens
     ``[B, H*D]`` and ``pos``: they are written into cache row ``pos`` and keys ``0..pos`` are attended (self-attention step); else
     all ``Lmax`` keys.  ``key_mask`` ``[B, Lk]`` (bool / u8, False = masked), ``bias`` ``[H, >= Lk]`` fp32 (T5's relative position
     bias row of the query position).  ``scale`` defaults to ``D**-0.5`` (BART); T5 passes 1.0.  Returns ``[B, H*D]``.
+    A ``-inf`` entry of ``bias`` means "excluded", exactly like a masked key; a (row, head) whose keys are all excluded, by the
+    mask, the bias or both, gets zeros -- in the kernel and in the torch form alike.
 
     Beam search (``beam_generate``): ``group`` -- query row r reads cache batch ``r // group`` and key-mask row ``r // group`` (the
     cross-attention caches of an item serve its ``group`` beams, never expanded); ``key_rows`` int32 ``[B, >= n_keys]`` -- key j of
@@ -317,13 +319,16 @@ def beam_step(logits: torch.Tensor, vocab: int, st: BeamState, pos: int, *, eos_
 
 
 def _torch_beam_rows(logits, vocab, ids, pos, eos, min_length, ngram, force_eos):
-    """the processed fp32 log-probs [rows, vocab]: BART's forced eos, log_softmax, then the bans (no renormalisation)"""
-    x = logits[:, :vocab].float()
+    """the processed fp32 log-probs [rows, vocab]: BART's forced eos, log_softmax, then the bans (no renormalisation).
+    The softmax runs on rows padded with -inf columns to a multiple of 8 (exp(-inf) = 0: the sum is the same): torch's device
+    kernel orders a row's sum by the row's alignment, and with an odd vocab (50265) two bitwise identical rows would otherwise get
+    log-probs one ulp apart -- an exact cross-beam tie must stay one, to be ordered by index as the kernels and HF's CPU form do."""
+    x = logits.new_full((logits.shape[0], (vocab + 7) // 8 * 8), float("-inf"), dtype=torch.float32)
     if force_eos:
-        keep = x[:, eos].clone()
-        x = torch.full_like(x, float("-inf"))
-        x[:, eos] = keep
-    x = torch.log_softmax(x, -1)
+        x[:, eos] = logits[:, eos]
+    else:
+        x[:, :vocab] = logits[:, :vocab]
+    x = torch.log_softmax(x, -1)[:, :vocab]
     cur_len = pos + 1
     if ngram > 0 and cur_len + 1 >= ngram:
         for r, prefix in enumerate(ids[:, :cur_len].tolist()):
