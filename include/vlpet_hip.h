@@ -684,6 +684,45 @@ int vlpet_beam_advance(const float* part_stats, const float* part_val, const int
                        int64_t* hyp_tokens, int64_t ld_hyp, float* item_worst, int* item_state, int* counter, int pos,
                        int eos_token_id, int pad_token_id, float length_penalty, int early_stopping, vlpet_stream_t stream);
 
+/* ---- position-on-device forms of the four decode kernels (csrc/decode.hip): one captured launch serves every step -----------
+ * Each takes `const int* pos_dev` (device, 4-byte aligned; NULL: -1) where its sibling takes `int pos`, and `int pos_limit`.  The
+ * kernel reads pos = *pos_dev once (uniform) and derives in the kernel everything the host derives from an int position; the
+ * arithmetic is the sibling's (the two forms are instantiations of one kernel body: results are bitwise the sibling's).
+ * Guard: a launch with pos < 0 or pos >= pos_limit writes NOTHING and returns 0.  pos_limit must not exceed the capacity of any
+ * buffer indexed by the position: the entry points check it against the strides they are given (-1), the caller answers for the
+ * buffers whose size the ABI does not see (the counters: pos_limit slots; the bias table: pos_limit rows; both ping-pong halves).
+ * Every other argument check is the sibling's, evaluated at pos = pos_limit - 1.
+ *
+ * vlpet_attn_decode_at: the append (self-attention) form of vlpet_attn_decode_beam, group = 1: k_new / v_new (required) go to
+ *   cache row pos, keys 0..pos are attended; pos_limit <= Lk, the caches' row capacity.  bias: base of a [positions, H, >= pos_limit]
+ *   fp32 table (position stride pos_stride_bias, head stride ld_bias), row pos is used; NULL: no bias.  key_rows: base of the
+ *   [2, B, ld_key_rows] ping-pong tables (half stride parity_stride_key_rows), half pos & 1 is read; NULL: every key in batch r.
+ * vlpet_greedy_pick_at: ids[b, pos + 1], the ban scan over ids[b, 0..pos], the min_length test and the counter slot counters[pos]
+ *   (`counters` is the base) come from the device word; next_tokens[b] (int64 [B], required) also gets the token written to ids.
+ *   pos_limit < ld_ids.
+ * vlpet_beam_rows_at: `ids` is the base of the [2, rows, ld_ids] ping-pong buffers (half stride parity_stride_ids), half pos & 1 is
+ *   read; the forced-eos step is the one with pos == force_eos_pos (-1: never).
+ * vlpet_beam_advance_at: `ids` / `key_rows` are the ping-pong bases: half pos & 1 is read, the other half written; `counters` is the
+ *   base (slot pos).  pos_limit < ld_ids, <= ld_hyp, < ld_key_rows. */
+int vlpet_attn_decode_at(const void* q, int64_t ld_q, void* k_cache, void* v_cache, int64_t ld_k, int64_t bs_k, int64_t ld_v,
+                         int64_t bs_v, const void* k_new, const void* v_new, int64_t ld_new, const int* pos_dev, int pos_limit,
+                         const uint8_t* key_mask, int64_t ld_mask, const float* bias, int64_t ld_bias, int64_t pos_stride_bias,
+                         void* o, int64_t ld_o, int B, int H, int D, int Lk, float scale, const int* key_rows,
+                         int64_t ld_key_rows, int64_t parity_stride_key_rows, int io_dtype, vlpet_stream_t stream);
+int vlpet_greedy_pick_at(const void* logits, int64_t ld, int V, int64_t* ids, int64_t ld_ids, const int* pos_dev, int pos_limit,
+                         int* unfinished, int* counters, int64_t* next_tokens, int B, int eos_token_id, int pad_token_id,
+                         int min_length, int no_repeat_ngram_size, int io_dtype, vlpet_stream_t stream);
+int vlpet_beam_rows_at(const void* logits, int64_t ld, int V, const int64_t* ids, int64_t ld_ids, int64_t parity_stride_ids,
+                       const int* pos_dev, int pos_limit, int rows, int num_beams, int slices, int eos_token_id, int min_length,
+                       int no_repeat_ngram_size, int force_eos_pos, float* part_stats, float* part_val, int* part_tok,
+                       int io_dtype, vlpet_stream_t stream);
+int vlpet_beam_advance_at(const float* part_stats, const float* part_val, const int* part_tok, int slices, int V, int B,
+                          int num_beams, float* beam_scores, int64_t* ids, int64_t ld_ids, int64_t parity_stride_ids,
+                          int* key_rows, int64_t ld_key_rows, int64_t parity_stride_key_rows, int64_t* next_tokens,
+                          float* hyp_score, int* hyp_meta, int64_t* hyp_tokens, int64_t ld_hyp, float* item_worst, int* item_state,
+                          int* counters, const int* pos_dev, int pos_limit, int eos_token_id, int pad_token_id,
+                          float length_penalty, int early_stopping, vlpet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

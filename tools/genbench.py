@@ -4,6 +4,11 @@
   hip      VLBart.generate: per-layer caches, decode.decode_attention / decode.greedy_pick on csrc/decode.hip
   torch    the same cached loop on the torch forms (decode.EAGER, host.bart.EAGER_ATTENTION: SDPA, eager argmax + processors)
   nocache  what a user writes without generate(): the training-path decoder re-run on the whole prefix at every step
+  graph    generate(graph=True): the hip step captured once and replayed (decode.graph_generate).  Its first call (eager warm-up) and
+           second call (capture + replays) are timed on their own and never enter the timed calls.  With hip and graph both asked
+           for, ``--ab-rounds N`` rounds of alternating hip / graph calls follow (same process, same inputs): the spread of each
+           leg and the ratio; ``--launches`` counts the kernel launches of one decode step of each leg with the torch profiler
+           (a run of its own: tracing slows the host).
 
 Every path runs max_length - 1 steps (min_length = max_length bans eos throughout).  Shapes: VQA (B = 500, S_enc = 20 + 36 = 56,
 max_length 20), caption (B = 416, S_enc = 40 + 36 = 76, max_length 40).
@@ -90,6 +95,76 @@ def nocache_generate(model, ids, vis, task, max_length, eos, start):
         return out
 
 
+def timed_legs(args, path, call):
+    """(ms per call over args.reps calls after the warm-up, the last output, extras): the graph leg's first two calls -- eager
+    warm-up, capture -- are timed separately, from an empty graph cache, so they are what a fresh process pays"""
+    import torch
+    import vlpet_amd.decode as D
+    extra = {}
+    if path == "graph":
+        D.clear_graphs()
+        s0 = dict(D.GRAPH_STATS)
+        for name in ("first_call_ms", "capture_call_ms"):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            call()
+            torch.cuda.synchronize()
+            extra[name] = round((time.perf_counter() - t) * 1e3, 2)
+    for _ in range(args.warmup):
+        call()
+    torch.cuda.synchronize()
+    t = time.perf_counter()
+    for _ in range(args.reps):
+        out = call()
+    torch.cuda.synchronize()
+    ms = (time.perf_counter() - t) * 1e3 / args.reps
+    if path == "graph":
+        d = {k: D.GRAPH_STATS[k] - s0[k] for k in s0}
+        assert d["captures"] == 1 and d["eager"] == 0 and d["replays"] > 0, d      # the timed calls replayed; nothing fell back
+        extra["replays_per_call"] = d["replays"] // (1 + args.warmup + args.reps)
+    return ms, out, extra
+
+
+def ab_rounds(args, calls, steps, tag):
+    """alternating hip / graph calls: per leg the ms per call of every round, and graph / hip of the means"""
+    import torch
+    per = {p: [] for p in calls}
+    for _ in range(args.ab_rounds):
+        for p, call in calls.items():
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            for _ in range(args.reps):
+                call()
+            torch.cuda.synchronize()
+            per[p].append((time.perf_counter() - t) * 1e3 / args.reps)
+    mean = {p: sum(v) / len(v) for p, v in per.items()}
+    row = dict(tag, ab_rounds=args.ab_rounds, reps=args.reps,
+               **{f"{p}_ms": [round(x, 2) for x in v] for p, v in per.items()},
+               **{f"{p}_mean_ms": round(m, 2) for p, m in mean.items()},
+               **{f"{p}_step_ms": round(m / steps, 3) for p, m in mean.items()},
+               graph_over_hip=round(mean["graph"] / mean["hip"], 3))
+    print(json.dumps(row), flush=True)
+    return row
+
+
+def launches_per_step(make_call):
+    """kernel launches of ONE decode step: a call of three tokens minus a call of two, counted by the torch profiler.
+    ``make_call(max_length)`` returns the call."""
+    import torch
+    from torch.profiler import ProfilerActivity, profile
+    counts = []
+    for ml in (2, 3):
+        call = make_call(ml)
+        call()
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            call()
+            torch.cuda.synchronize()
+        counts.append(sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA
+                          and "memcpy" not in e.name.lower() and "memset" not in e.name.lower()))
+    return counts[1] - counts[0]
+
+
 def run(args):
     import torch
     import vlpet_amd.decode as D
@@ -113,32 +188,34 @@ def run(args):
                 model.model.encoder(ids, vis, None, sh["task"], False)
             torch.cuda.synchronize()
             enc_ms = (time.perf_counter() - t) * 1e3 / args.reps
-        outs = {}
+        outs, calls = {}, {}
         for path in args.paths:
-            def call():
+            def call(path=path, ml=ml):
                 if path == "nocache":
                     return nocache_generate(model, ids, vis, sh["task"], ml, 2, cfg.decoder_start_token_id)
-                return model.generate(ids, vis, sh["task"], max_length=ml, min_length=ml)
+                return model.generate(ids, vis, sh["task"], max_length=ml, min_length=ml, graph=path == "graph")
+            calls[path] = call
+            if args.launches:
+                if path in ("hip", "graph"):     # (graph: its first call of a key issues the launches a capture records)
+                    def make_call(n, path=path, call=call):
+                        return lambda: (D.clear_graphs(), call(path, n))
+                    print(json.dumps(dict(shape=shape, path=path, launches_per_step=launches_per_step(make_call))), flush=True)
+                continue
             saved = (D.EAGER, HB.EAGER_ATTENTION)
             D.EAGER = HB.EAGER_ATTENTION = path == "torch"
             try:
-                for _ in range(args.warmup):
-                    call()
-                torch.cuda.synchronize()
-                t = time.perf_counter()
-                for _ in range(args.reps):
-                    out = call()
-                torch.cuda.synchronize()
-                ms = (time.perf_counter() - t) * 1e3 / args.reps
+                ms, out, extra = timed_legs(args, path, call)
             finally:
                 D.EAGER, HB.EAGER_ATTENTION = saved
             outs[path] = out
             assert out.shape == (sh["B"], ml), out.shape
             row = dict(shape=shape, path=path, B=sh["B"], S_enc=sh["S_enc"], max_length=ml, total_ms=round(ms, 2),
                        encoder_ms=round(enc_ms, 2), step_ms=round((ms - enc_ms) / steps, 3),
-                       tokens_per_s=round(sh["B"] * steps / (ms / 1e3), 1))
+                       tokens_per_s=round(sh["B"] * steps / (ms / 1e3), 1), **extra)
             rows.append(row)
             print(json.dumps(row), flush=True)
+        if "hip" in outs and "graph" in outs and args.ab_rounds > 0:
+            ab_rounds(args, {p: calls[p] for p in ("hip", "graph")}, steps, dict(shape=shape, encoder_ms=round(enc_ms, 2)))
         if "hip" in outs:
             for p, o in outs.items():       # bf16 paths may part ways where two logits are within rounding: report, do not fail
                 agree = float((o == outs["hip"]).float().mean())
@@ -160,30 +237,36 @@ def run_beams(args):
         b = TR.synthetic_batch(sh["task"], sh["B"], cfg, dev, gen, no_padding=False)
         ids, vis, ml = b["input_ids"], b["vis_inputs"], sh["max_length"]
         enc_len = ids.shape[1] + vis[0].shape[1]
-        outs = {}
+        outs, calls = {}, {}
         for path in args.paths:
             if path == "nocache":
                 continue
-            def call():
-                return model.generate(ids, vis, sh["task"], max_length=ml, min_length=ml, num_beams=args.num_beams)
+            def call(path=path, ml=ml):
+                return model.generate(ids, vis, sh["task"], max_length=ml, min_length=ml, num_beams=args.num_beams,
+                                      graph=path == "graph")
+            calls[path] = call
+            if args.launches:
+                if path in ("hip", "graph"):
+                    def make_call(n, path=path, call=call):
+                        return lambda: (D.clear_graphs(), call(path, n))
+                    print(json.dumps(dict(model=kind, path=path, launches_per_step=launches_per_step(make_call))), flush=True)
+                continue
             saved = (D.EAGER, HB.EAGER_ATTENTION)
             D.EAGER = HB.EAGER_ATTENTION = path == "torch"
             try:
-                for _ in range(args.warmup):
-                    call()
-                torch.cuda.synchronize()
-                t = time.perf_counter()
-                for _ in range(args.reps):
-                    out = call()
-                torch.cuda.synchronize()
-                ms = (time.perf_counter() - t) * 1e3 / args.reps
+                ms, out, extra = timed_legs(args, path, call)
             finally:
                 D.EAGER, HB.EAGER_ATTENTION = saved
             outs[path] = out
             row = dict(model=kind, path=path, num_beams=args.num_beams, B=sh["B"], enc_len=enc_len, max_length=ml,
-                       total_ms=round(ms, 2), step_ms=round(ms / (ml - 1), 3))
+                       total_ms=round(ms, 2), step_ms=round(ms / (ml - 1), 3), **extra)
             rows.append(row)
             print(json.dumps(row), flush=True)
+        if "hip" in outs and "graph" in outs:
+            agree = float((outs["graph"] == outs["hip"]).float().mean()) if outs["graph"].shape == outs["hip"].shape else 0.0
+            print(json.dumps(dict(model=kind, tokens_equal_to_hip="graph", fraction=round(agree, 4))), flush=True)
+            if args.ab_rounds > 0:
+                ab_rounds(args, {p: calls[p] for p in ("hip", "graph")}, ml - 1, dict(model=kind, num_beams=args.num_beams))
         if "hip" in outs and "torch" in outs:
             o, h = outs["torch"], outs["hip"]
             agree = float((o == h).float().mean()) if o.shape == h.shape else 0.0
@@ -266,7 +349,9 @@ def stats(path, shape="vqa"):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--shapes", nargs="+", default=["vqa", "caption"], choices=list(SHAPES))
-    ap.add_argument("--paths", nargs="+", default=["hip", "torch", "nocache"], choices=["hip", "torch", "nocache"])
+    ap.add_argument("--paths", nargs="+", default=["hip", "torch", "nocache"], choices=["hip", "torch", "nocache", "graph"])
+    ap.add_argument("--ab-rounds", type=int, default=3, help="alternating hip / graph rounds after the legs (0: none)")
+    ap.add_argument("--launches", action="store_true", help="count one decode step's kernel launches (hip, graph) instead of timing")
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--out", default=None)
@@ -284,6 +369,8 @@ def main():
     else:
         rows = run(args)
         text = table(rows)
+    if args.launches:
+        return
     print(text)
     if args.out:
         with open(args.out, "w") as f:

@@ -15,6 +15,12 @@
 // blocks of the same rows.  Inside a wave, D / 8 lanes hold one key (16-byte loads of 8 elements), so a wave step covers
 // 64 / (D / 8) keys; every lane keeps an online softmax (max, sum, 8 accumulators) over the keys of its lane group and the groups
 // are merged with cross-lane shuffles at the end.  The loads of U steps are issued before any of them is consumed.
+//
+// Every kernel has a second instantiation (AT = true: the vlpet_*_at entry points) that reads the step position from device memory
+// instead of its argument block, so that one captured launch serves every step of a replayed generate().  The position is resolved
+// at the top of the kernel (device_pos: one uniform 4-byte read, and a launch whose position lies outside 0..pos_limit-1 writes
+// nothing); everything the host derives from an int position -- key count, bias row, ping-pong halves, counter slot, forced step --
+// is derived there, and the body below is the same code for both forms.
 #include "common.h"
 #include "../../include/vlpet_hip.h"
 
@@ -40,6 +46,13 @@ template <typename IO> __device__ __forceinline__ IO to_io(float f);
 template <> __device__ __forceinline__ __bf16 to_io<__bf16>(float f) { return (__bf16)f; }
 template <> __device__ __forceinline__ float to_io<float>(float f) { return f; }
 
+// The step position of an _at launch.  The pointer is a kernel argument and nothing in the launch writes the word, so the read is a
+// scalar load; readfirstlane makes the uniformity provable where the compiler cannot see it.  False: outside 0..limit-1.
+__device__ __forceinline__ bool device_pos(const int* pos_dev, int limit, int& pos) {
+    pos = __builtin_amdgcn_readfirstlane(*pos_dev);
+    return pos >= 0 && pos < limit;
+}
+
 struct DecodeAttnArgs {
     const void* q; int64_t ld_q;
     void* k; void* v; int64_t ld_k, bs_k, ld_v, bs_v;
@@ -51,12 +64,23 @@ struct DecodeAttnArgs {
     float scale;
     int group;                                  // cross caches / key mask: batch (query row) / group
     const int* key_rows; int64_t ld_kr;         // KR: key j of query row b lives in cache batch key_rows[b, j]
+    const int* pos_dev; int pos_limit;          // AT: the position word; bias / key_rows are table bases with these strides
+    int64_t ps_bias, ps_kr;                     //     (bias row `pos`, key-row half `pos & 1`)
 };
 
 #define DEC_WAVES 4
 
-template <typename IO, int D, bool KR = false>
+template <typename IO, int D, bool KR = false, bool AT = false>
 __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(DecodeAttnArgs a) {
+    int pos = a.pos, n = a.n_keys;
+    const float* bias = a.bias;
+    const int* key_rows = a.key_rows;
+    if constexpr (AT) {                         // (append form only: cache row = pos, keys 0..pos)
+        if (!device_pos(a.pos_dev, a.pos_limit, pos)) return;
+        n = pos + 1;
+        if (bias != nullptr) bias += (int64_t)pos * a.ps_bias;
+        if constexpr (KR) key_rows += (int64_t)(pos & 1) * a.ps_kr;
+    }
     constexpr int LPK = D / 8;                  // lanes per key
     constexpr int KPS = 64 / LPK;               // keys per wave step
     constexpr int U = D == 64 ? 4 : 2;          // steps whose loads are in flight together
@@ -83,14 +107,13 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(DecodeAttnA
         kn.load(reinterpret_cast<const IO*>(a.k_new) + b * a.ld_new + col);
         vn.load(reinterpret_cast<const IO*>(a.v_new) + b * a.ld_new + col);
         if (kj == 0) {
-            kn.store(kc + (int64_t)a.pos * a.ld_k);
-            vn.store(vc + (int64_t)a.pos * a.ld_v);
+            kn.store(kc + (int64_t)pos * a.ld_k);
+            vn.store(vc + (int64_t)pos * a.ld_v);
         }
     }
-    const int n = a.n_keys;
     const uint8_t* mrow = a.mask != nullptr ? a.mask + (b / a.group) * a.ld_mask : nullptr;
-    const int* krow = KR ? a.key_rows + b * a.ld_kr : nullptr;
-    const float* brow = a.bias != nullptr ? a.bias + (int64_t)h * a.ld_bias : nullptr;
+    const int* krow = KR ? key_rows + b * a.ld_kr : nullptr;
+    const float* brow = bias != nullptr ? bias + (int64_t)h * a.ld_bias : nullptr;
 
     float m = -INFINITY, l = 0.f, acc[8];
 #pragma unroll
@@ -101,7 +124,7 @@ __global__ __launch_bounds__(DEC_WAVES * 64) void attn_decode_kernel(DecodeAttnA
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int j = min(j0 + u * KPS + kj, n - 1);        // (clamped: a key past the end is loaded but not counted)
-            if (append && j == a.pos) {                          // the appended row comes from registers, not back from memory
+            if (append && j == pos) {                          // the appended row comes from registers, not back from memory
                 kr[u] = kn;
                 vr[u] = vn;
             } else if constexpr (KR) {                           // (a batch outside 0..B-1 reads the row's own)
@@ -174,6 +197,8 @@ struct GreedyArgs {
     int64_t* ids; int64_t ld_ids; int pos;
     int* unfinished; int* counter;
     int eos, pad, min_length, ngram;
+    const int* pos_dev; int pos_limit;          // AT: the position word; `counter` is the counters' base (slot `pos`)
+    int64_t* next_tokens;                       // AT: [B], the token just written to ids[b, pos + 1]
 };
 
 #define GP_THREADS 512
@@ -215,15 +240,21 @@ __device__ __forceinline__ bool build_bans(uint32_t* ban, const int64_t* ids, in
 // One workgroup per row.  The banned tokens of the row (eos below min_length, the continuations of every earlier occurrence of the
 // last n - 1 tokens) are set in an LDS bitmap before the scan; the scan reads the row once, 16 bytes per lane per load, GP_U loads
 // in flight per lane, and skips banned columns with one LDS word per 8 columns.
-template <typename IO>
+template <typename IO, bool AT = false>
 __global__ __launch_bounds__(GP_THREADS) void greedy_pick_kernel(GreedyArgs a) {
     __shared__ uint32_t ban[GP_MAX_V / 32];
     __shared__ float wv[GP_THREADS / 64];
     __shared__ int wi[GP_THREADS / 64];
+    int pos = a.pos;
+    int* counter = a.counter;
+    if constexpr (AT) {                         // (before any barrier: the whole workgroup leaves)
+        if (!device_pos(a.pos_dev, a.pos_limit, pos)) return;
+        counter += pos;
+    }
     const int tid = threadIdx.x;
     const int64_t b = blockIdx.x;
-    const bool any_ban = build_bans(ban, a.ids + b * a.ld_ids, a.pos + 1, a.V, a.eos, a.min_length, a.ngram, tid, GP_THREADS);
-    const int cur_len = a.pos + 1;
+    const bool any_ban = build_bans(ban, a.ids + b * a.ld_ids, pos + 1, a.V, a.eos, a.min_length, a.ngram, tid, GP_THREADS);
+    const int cur_len = pos + 1;
     const IO* row = reinterpret_cast<const IO*>(a.logits) + b * a.ld;
     const int groups = (a.V + 7) >> 3;
     float best = -INFINITY;
@@ -261,7 +292,8 @@ __global__ __launch_bounds__(GP_THREADS) void greedy_pick_kernel(GreedyArgs a) {
             else if (tok == a.eos) { unf = 0; a.unfinished[b] = 0; }
         }
         a.ids[b * a.ld_ids + cur_len] = tok;
-        atomicAdd(a.counter, unf);
+        if constexpr (AT) a.next_tokens[b] = tok;
+        atomicAdd(counter, unf);
     }
 }
 
@@ -319,13 +351,23 @@ struct BeamRowsArgs {
     int eos, min_length, ngram, force_eos;
     int slices, slice_cols;
     float* stats; float* val; int* tok;         // per (row, slice): (max, sum of exp(x - max)); the top T (value, token)
+    const int* pos_dev; int pos_limit;          // AT: the position word; `ids` is the ping-pong base (half `pos & 1`, stride ps_ids),
+    int64_t ps_ids; int force_eos_pos;          //     the forced step is the one at force_eos_pos (-1: never)
 };
 
 #define BR_THREADS 256
 
 // grid (slices, rows).  The slice's columns are read once, 16 bytes per lane per load, GP_U loads in flight per lane.
-template <typename IO, int T>
+template <typename IO, int T, bool AT = false>
 __global__ __launch_bounds__(BR_THREADS) void beam_rows_kernel(BeamRowsArgs a) {
+    int pos = a.pos;
+    const int64_t* ids = a.ids;
+    bool force_eos = a.force_eos != 0;
+    if constexpr (AT) {                         // (before any barrier: the whole workgroup leaves)
+        if (!device_pos(a.pos_dev, a.pos_limit, pos)) return;
+        ids += (int64_t)(pos & 1) * a.ps_ids;
+        force_eos = pos == a.force_eos_pos;
+    }
     __shared__ uint32_t ban[GP_MAX_V / 32];
     __shared__ float wm[BR_THREADS / 64], ws[BR_THREADS / 64];
     __shared__ float lv[BR_THREADS / 64][T];
@@ -333,7 +375,7 @@ __global__ __launch_bounds__(BR_THREADS) void beam_rows_kernel(BeamRowsArgs a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int s = blockIdx.x;
     const int64_t r = blockIdx.y;
-    const bool any_ban = build_bans(ban, a.ids + r * a.ld_ids, a.pos + 1, a.V, a.eos, a.min_length, a.ngram, tid, BR_THREADS);
+    const bool any_ban = build_bans(ban, ids + r * a.ld_ids, pos + 1, a.V, a.eos, a.min_length, a.ngram, tid, BR_THREADS);
     const IO* row = reinterpret_cast<const IO*>(a.logits) + r * a.ld;
     const int c0 = s * a.slice_cols, c1 = min(a.V, c0 + a.slice_cols);
     const int g_lo = c0 >> 3, g_hi = (c1 + 7) >> 3;             // (slice_cols is a multiple of 8)
@@ -353,7 +395,7 @@ __global__ __launch_bounds__(BR_THREADS) void beam_rows_kernel(BeamRowsArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 const int c = 8 * g + j;
-                const bool in = c < c1 && (!a.force_eos || c == a.eos);
+                const bool in = c < c1 && (!force_eos || c == a.eos);
                 xv[j] = in ? x[u].get(j) : -INFINITY;
                 mx = fmaxf(mx, xv[j]);
             }
@@ -413,13 +455,30 @@ struct BeamAdvanceArgs {
     float* worst; int* state; int* counter;
     int pos, eos, pad;
     float length_penalty; int early;
+    const int* pos_dev; int pos_limit;          // AT: the position word; ids_in / kr_in are the ping-pong bases (read half `pos & 1`,
+    int64_t ps_ids, ps_kr;                      //     written half the other one), `counter` the counters' base (slot `pos`)
 };
 
 // One wave (= one workgroup) per item.  Every lane runs the scorer's walk on the same values (held in registers alike), so no lane
 // waits on another's memory writes; the copies (ids, key rows, a new hypothesis' tokens) are spread over the lanes.
-template <int K>
+template <int K, bool AT = false>
 __global__ __launch_bounds__(64) void beam_advance_kernel(BeamAdvanceArgs a) {
     constexpr int T = 2 * K;
+    if constexpr (AT) {                         // resolved into the argument block's own copy: the body reads `a` as in the int form
+        int pos;
+        if (!device_pos(a.pos_dev, a.pos_limit, pos)) return;
+        const int64_t src = pos & 1, dst = src ^ 1;
+        int64_t* ids = a.ids_out;               // (the base of both halves)
+        a.pos = pos;
+        a.ids_in = ids + src * a.ps_ids;
+        a.ids_out = ids + dst * a.ps_ids;
+        if (a.kr_in) {
+            int* kr = a.kr_out;
+            a.kr_in = kr + src * a.ps_kr;
+            a.kr_out = kr + dst * a.ps_kr;
+        }
+        a.counter += pos;
+    }
     __shared__ float s_lse[K], s_bs[K];
     const int lane = threadIdx.x;
     const int b = blockIdx.x;
@@ -548,97 +607,66 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(BeamAdvanceArgs a) {
 inline bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int herr(hipError_t e) { return e == hipSuccess ? 0 : (int)e; }
 
-}  // namespace
+inline bool al4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
 
-extern "C" int vlpet_attn_decode(const void* q, int64_t ld_q, void* k_cache, void* v_cache, int64_t ld_k, int64_t bs_k,
-                                 int64_t ld_v, int64_t bs_v, const void* k_new, const void* v_new, int64_t ld_new, int pos,
-                                 const uint8_t* key_mask, int64_t ld_mask, const float* bias, int64_t ld_bias, void* o,
-                                 int64_t ld_o, int B, int H, int D, int Lk, float scale, int io_dtype, vlpet_stream_t stream) {
-    if (!q || !k_cache || !v_cache || !o) return VLPET_E_NULL;
-    if ((k_new == nullptr) != (v_new == nullptr)) return VLPET_E_NULL;
-    if (io_dtype != VLPET_F32 && io_dtype != VLPET_BF16) return VLPET_E_DTYPE;
-    if (B <= 0 || H <= 0 || (D != 16 && D != 64) || Lk <= 0 || Lk > 1024) return VLPET_E_SHAPE;
-    const bool append = k_new != nullptr;
-    if (append && (pos < 0 || pos >= Lk)) return VLPET_E_SHAPE;
-    const int64_t E = (int64_t)H * D;
-    if (ld_q < E || ld_k < E || ld_v < E || ld_o < E || (append && ld_new < E)) return VLPET_E_SHAPE;
-    if (bs_k < 0 || bs_v < 0 || (key_mask && ld_mask < Lk) || (bias && ld_bias < Lk)) return VLPET_E_SHAPE;
-    if (!al16(q) || !al16(k_cache) || !al16(v_cache) || !al16(o) || (append && (!al16(k_new) || !al16(v_new))))
-        return VLPET_E_ALIGN;
-    if ((ld_q | ld_k | ld_v | bs_k | bs_v | ld_o | (append ? ld_new : 0)) & 7) return VLPET_E_ALIGN;
-    if (bias && (reinterpret_cast<uintptr_t>(bias) & 3)) return VLPET_E_ALIGN;
-    DecodeAttnArgs a{};
-    a.q = q; a.ld_q = ld_q; a.k = k_cache; a.v = v_cache; a.ld_k = ld_k; a.bs_k = bs_k; a.ld_v = ld_v; a.bs_v = bs_v;
-    a.k_new = k_new; a.v_new = v_new; a.ld_new = ld_new; a.pos = pos; a.mask = key_mask; a.ld_mask = ld_mask;
-    a.bias = bias; a.ld_bias = ld_bias; a.o = o; a.ld_o = ld_o; a.B = B; a.H = H; a.n_keys = append ? pos + 1 : Lk;
-    a.scale = scale; a.group = 1;
-    const int64_t pairs = (int64_t)B * H;
-    dim3 grid((unsigned)((pairs + DEC_WAVES - 1) / DEC_WAVES)), block(DEC_WAVES * 64);
-    hipStream_t s = (hipStream_t)stream;
-    if (io_dtype == VLPET_BF16) {
-        if (D == 64) hipLaunchKernelGGL((attn_decode_kernel<__bf16, 64>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((attn_decode_kernel<__bf16, 16>), grid, block, 0, s, a);
-    } else {
-        if (D == 64) hipLaunchKernelGGL((attn_decode_kernel<float, 64>), grid, block, 0, s, a);
-        else hipLaunchKernelGGL((attn_decode_kernel<float, 16>), grid, block, 0, s, a);
-    }
-    return herr(hipGetLastError());
+// An _at entry point's position arguments: no position word or a limit outside 1..capacity (of what `pos` indexes) -> -1.
+inline int check_pos_dev(const int* pos_dev, int pos_limit, int64_t capacity) {
+    if (!pos_dev) return VLPET_E_SHAPE;
+    if (!al4(pos_dev)) return VLPET_E_ALIGN;
+    if (pos_limit < 1 || pos_limit > capacity) return VLPET_E_SHAPE;
+    return 0;
 }
 
-extern "C" int vlpet_greedy_pick(const void* logits, int64_t ld, int V, int64_t* ids, int64_t ld_ids, int pos, int* unfinished,
-                                 int* counter, int B, int eos_token_id, int pad_token_id, int min_length, int no_repeat_ngram_size,
-                                 int io_dtype, vlpet_stream_t stream) {
-    if (!logits || !ids || !unfinished || !counter) return VLPET_E_NULL;
-    if (io_dtype != VLPET_F32 && io_dtype != VLPET_BF16) return VLPET_E_DTYPE;
-    if (B <= 0 || V <= 0 || V > GP_MAX_V || ld < (int64_t)((V + 7) / 8 * 8) || pos < 0 || (int64_t)pos + 1 >= ld_ids)
-        return VLPET_E_SHAPE;
-    if (eos_token_id >= V || no_repeat_ngram_size < 0) return VLPET_E_SHAPE;
-    if (!al16(logits) || (ld & 7) || (reinterpret_cast<uintptr_t>(ids) & 7) || (reinterpret_cast<uintptr_t>(unfinished) & 3)
-        || (reinterpret_cast<uintptr_t>(counter) & 3))
-        return VLPET_E_ALIGN;
-    GreedyArgs a{};
-    a.logits = logits; a.ld = ld; a.V = V; a.ids = ids; a.ld_ids = ld_ids; a.pos = pos; a.unfinished = unfinished;
-    a.counter = counter; a.eos = eos_token_id < 0 ? -1 : eos_token_id; a.pad = pad_token_id; a.min_length = min_length;
-    a.ngram = no_repeat_ngram_size;
-    hipStream_t s = (hipStream_t)stream;
-    if (io_dtype == VLPET_BF16) hipLaunchKernelGGL(greedy_pick_kernel<__bf16>, dim3(B), dim3(GP_THREADS), 0, s, a);
-    else hipLaunchKernelGGL(greedy_pick_kernel<float>, dim3(B), dim3(GP_THREADS), 0, s, a);
-    return herr(hipGetLastError());
-}
+// Checks + launch of the four entry points' two forms.  `at`: the position-dependent checks of the int form run at pos_limit - 1,
+// the largest position the kernel's guard lets through, and the launch takes the AT instantiation.
 
-extern "C" int vlpet_attn_decode_beam(const void* q, int64_t ld_q, void* k_cache, void* v_cache, int64_t ld_k, int64_t bs_k,
-                                      int64_t ld_v, int64_t bs_v, const void* k_new, const void* v_new, int64_t ld_new, int pos,
-                                      const uint8_t* key_mask, int64_t ld_mask, const float* bias, int64_t ld_bias, void* o,
-                                      int64_t ld_o, int B, int H, int D, int Lk, float scale, int group, const int* key_rows,
-                                      int64_t ld_key_rows, int io_dtype, vlpet_stream_t stream) {
+int attn_decode_run(const void* q, int64_t ld_q, void* k_cache, void* v_cache, int64_t ld_k, int64_t bs_k, int64_t ld_v,
+                    int64_t bs_v, const void* k_new, const void* v_new, int64_t ld_new, int pos, const uint8_t* key_mask,
+                    int64_t ld_mask, const float* bias, int64_t ld_bias, void* o, int64_t ld_o, int B, int H, int D, int Lk,
+                    float scale, int group, const int* key_rows, int64_t ld_key_rows, int io_dtype, vlpet_stream_t stream, bool at,
+                    const int* pos_dev, int pos_limit, int64_t ps_bias, int64_t ps_kr) {
     if (!q || !k_cache || !v_cache || !o) return VLPET_E_NULL;
     if ((k_new == nullptr) != (v_new == nullptr)) return VLPET_E_NULL;
+    if (at && !k_new) return VLPET_E_NULL;                        // (the _at form is the append form)
     if (io_dtype != VLPET_F32 && io_dtype != VLPET_BF16) return VLPET_E_DTYPE;
     if (B <= 0 || H <= 0 || (D != 16 && D != 64) || Lk <= 0 || Lk > 1024 || group <= 0) return VLPET_E_SHAPE;
+    int keys = Lk;                                                // what a mask / bias / key-row row must cover
+    if (at) {
+        const int e = check_pos_dev(pos_dev, pos_limit, Lk);
+        if (e) return e;
+        if (ps_bias < 0 || ps_kr < 0) return VLPET_E_SHAPE;
+        pos = pos_limit - 1;
+        keys = pos_limit;
+    }
     const bool append = k_new != nullptr;
     if (append && (pos < 0 || pos >= Lk)) return VLPET_E_SHAPE;
     if (append && group != 1) return VLPET_E_SHAPE;               // the appended row goes to batch r: one cache batch per row
     if (key_rows && ld_key_rows < (append ? pos + 1 : Lk)) return VLPET_E_SHAPE;
     const int64_t E = (int64_t)H * D;
     if (ld_q < E || ld_k < E || ld_v < E || ld_o < E || (append && ld_new < E)) return VLPET_E_SHAPE;
-    if (bs_k < 0 || bs_v < 0 || (key_mask && ld_mask < Lk) || (bias && ld_bias < Lk)) return VLPET_E_SHAPE;
+    if (bs_k < 0 || bs_v < 0 || (key_mask && ld_mask < keys) || (bias && ld_bias < keys)) return VLPET_E_SHAPE;
     if (!al16(q) || !al16(k_cache) || !al16(v_cache) || !al16(o) || (append && (!al16(k_new) || !al16(v_new))))
         return VLPET_E_ALIGN;
     if ((ld_q | ld_k | ld_v | bs_k | bs_v | ld_o | (append ? ld_new : 0)) & 7) return VLPET_E_ALIGN;
-    if ((bias && (reinterpret_cast<uintptr_t>(bias) & 3)) || (key_rows && (reinterpret_cast<uintptr_t>(key_rows) & 3)))
-        return VLPET_E_ALIGN;
+    if ((bias && !al4(bias)) || (key_rows && !al4(key_rows))) return VLPET_E_ALIGN;
     DecodeAttnArgs a{};
     a.q = q; a.ld_q = ld_q; a.k = k_cache; a.v = v_cache; a.ld_k = ld_k; a.bs_k = bs_k; a.ld_v = ld_v; a.bs_v = bs_v;
     a.k_new = k_new; a.v_new = v_new; a.ld_new = ld_new; a.pos = pos; a.mask = key_mask; a.ld_mask = ld_mask;
     a.bias = bias; a.ld_bias = ld_bias; a.o = o; a.ld_o = ld_o; a.B = B; a.H = H; a.n_keys = append ? pos + 1 : Lk;
     a.scale = scale; a.group = group; a.key_rows = key_rows; a.ld_kr = ld_key_rows;
+    a.pos_dev = pos_dev; a.pos_limit = pos_limit; a.ps_bias = ps_bias; a.ps_kr = ps_kr;
     const int64_t pairs = (int64_t)B * H;
     dim3 grid((unsigned)((pairs + DEC_WAVES - 1) / DEC_WAVES)), block(DEC_WAVES * 64);
     hipStream_t s = (hipStream_t)stream;
+#define DEC_LAUNCH_KR(IO, DD, KR)                                                                                                  \
+    do {                                                                                                                           \
+        if (at) hipLaunchKernelGGL((attn_decode_kernel<IO, DD, KR, true>), grid, block, 0, s, a);                                 \
+        else hipLaunchKernelGGL((attn_decode_kernel<IO, DD, KR, false>), grid, block, 0, s, a);                                   \
+    } while (0)
 #define DEC_LAUNCH(IO, DD)                                                                                                         \
     do {                                                                                                                           \
-        if (key_rows) hipLaunchKernelGGL((attn_decode_kernel<IO, DD, true>), grid, block, 0, s, a);                               \
-        else hipLaunchKernelGGL((attn_decode_kernel<IO, DD, false>), grid, block, 0, s, a);                                       \
+        if (key_rows) DEC_LAUNCH_KR(IO, DD, true);                                                                                 \
+        else DEC_LAUNCH_KR(IO, DD, false);                                                                                         \
     } while (0)
     if (io_dtype == VLPET_BF16) {
         if (D == 64) DEC_LAUNCH(__bf16, 64);
@@ -648,48 +676,101 @@ extern "C" int vlpet_attn_decode_beam(const void* q, int64_t ld_q, void* k_cache
         else DEC_LAUNCH(float, 16);
     }
 #undef DEC_LAUNCH
+#undef DEC_LAUNCH_KR
     return herr(hipGetLastError());
 }
 
-extern "C" int vlpet_beam_rows(const void* logits, int64_t ld, int V, const int64_t* ids, int64_t ld_ids, int pos, int rows,
-                               int num_beams, int slices, int eos_token_id, int min_length, int no_repeat_ngram_size, int force_eos,
-                               float* part_stats, float* part_val, int* part_tok, int io_dtype, vlpet_stream_t stream) {
+int greedy_pick_run(const void* logits, int64_t ld, int V, int64_t* ids, int64_t ld_ids, int pos, int* unfinished, int* counter,
+                    int B, int eos_token_id, int pad_token_id, int min_length, int no_repeat_ngram_size, int io_dtype,
+                    vlpet_stream_t stream, bool at, const int* pos_dev, int pos_limit, int64_t* next_tokens) {
+    if (!logits || !ids || !unfinished || !counter || (at && !next_tokens)) return VLPET_E_NULL;
+    if (io_dtype != VLPET_F32 && io_dtype != VLPET_BF16) return VLPET_E_DTYPE;
+    if (at) {
+        const int e = check_pos_dev(pos_dev, pos_limit, INT_MAX);
+        if (e) return e;
+        pos = pos_limit - 1;
+    }
+    if (B <= 0 || V <= 0 || V > GP_MAX_V || ld < (int64_t)((V + 7) / 8 * 8) || pos < 0 || (int64_t)pos + 1 >= ld_ids)
+        return VLPET_E_SHAPE;
+    if (eos_token_id >= V || no_repeat_ngram_size < 0) return VLPET_E_SHAPE;
+    if (!al16(logits) || (ld & 7) || (reinterpret_cast<uintptr_t>(ids) & 7) || !al4(unfinished) || !al4(counter)
+        || (reinterpret_cast<uintptr_t>(next_tokens) & 7))
+        return VLPET_E_ALIGN;
+    GreedyArgs a{};
+    a.logits = logits; a.ld = ld; a.V = V; a.ids = ids; a.ld_ids = ld_ids; a.pos = pos; a.unfinished = unfinished;
+    a.counter = counter; a.eos = eos_token_id < 0 ? -1 : eos_token_id; a.pad = pad_token_id; a.min_length = min_length;
+    a.ngram = no_repeat_ngram_size; a.pos_dev = pos_dev; a.pos_limit = pos_limit; a.next_tokens = next_tokens;
+    hipStream_t s = (hipStream_t)stream;
+#define GP_LAUNCH(IO)                                                                                                              \
+    do {                                                                                                                           \
+        if (at) hipLaunchKernelGGL((greedy_pick_kernel<IO, true>), dim3(B), dim3(GP_THREADS), 0, s, a);                           \
+        else hipLaunchKernelGGL((greedy_pick_kernel<IO, false>), dim3(B), dim3(GP_THREADS), 0, s, a);                             \
+    } while (0)
+    if (io_dtype == VLPET_BF16) GP_LAUNCH(__bf16);
+    else GP_LAUNCH(float);
+#undef GP_LAUNCH
+    return herr(hipGetLastError());
+}
+
+int beam_rows_run(const void* logits, int64_t ld, int V, const int64_t* ids, int64_t ld_ids, int pos, int rows, int num_beams,
+                  int slices, int eos_token_id, int min_length, int no_repeat_ngram_size, int force_eos, float* part_stats,
+                  float* part_val, int* part_tok, int io_dtype, vlpet_stream_t stream, bool at, const int* pos_dev, int pos_limit,
+                  int64_t ps_ids, int force_eos_pos) {
     if (!logits || !ids || !part_stats || !part_val || !part_tok) return VLPET_E_NULL;
     if (io_dtype != VLPET_F32 && io_dtype != VLPET_BF16) return VLPET_E_DTYPE;
+    if (at) {
+        const int e = check_pos_dev(pos_dev, pos_limit, INT_MAX);
+        if (e) return e;
+        if (ps_ids < 0) return VLPET_E_SHAPE;
+        pos = pos_limit - 1;
+    }
     if (rows <= 0 || V <= 0 || V > GP_MAX_V || ld < (int64_t)((V + 7) / 8 * 8) || pos < 0 || (int64_t)pos + 1 > ld_ids)
         return VLPET_E_SHAPE;
     if (num_beams < 2 || num_beams > 8 || slices < 1 || slices > 64 || rows > 65535) return VLPET_E_SHAPE;
     if (eos_token_id < 0 || eos_token_id >= V || no_repeat_ngram_size < 0) return VLPET_E_SHAPE;
     if (!al16(logits) || (ld & 7) || (reinterpret_cast<uintptr_t>(ids) & 7) || (reinterpret_cast<uintptr_t>(part_stats) & 7)
-        || (reinterpret_cast<uintptr_t>(part_val) & 3) || (reinterpret_cast<uintptr_t>(part_tok) & 3))
+        || !al4(part_val) || !al4(part_tok))
         return VLPET_E_ALIGN;
     BeamRowsArgs a{};
     a.logits = logits; a.ld = ld; a.V = V; a.ids = ids; a.ld_ids = ld_ids; a.pos = pos; a.eos = eos_token_id;
     a.min_length = min_length; a.ngram = no_repeat_ngram_size; a.force_eos = force_eos ? 1 : 0;
     a.slices = slices; a.slice_cols = ((V + slices - 1) / slices + 7) / 8 * 8;
     a.stats = part_stats; a.val = part_val; a.tok = part_tok;
+    a.pos_dev = pos_dev; a.pos_limit = pos_limit; a.ps_ids = ps_ids; a.force_eos_pos = force_eos_pos;
     dim3 grid(slices, rows), block(BR_THREADS);
     hipStream_t s = (hipStream_t)stream;
+#define BR_LAUNCH_AT(IO, KK)                                                                                                       \
+    do {                                                                                                                           \
+        if (at) hipLaunchKernelGGL((beam_rows_kernel<IO, 2 * KK, true>), grid, block, 0, s, a);                                   \
+        else hipLaunchKernelGGL((beam_rows_kernel<IO, 2 * KK, false>), grid, block, 0, s, a);                                     \
+    } while (0)
 #define BR_LAUNCH(KK)                                                                                                              \
     case KK:                                                                                                                       \
-        if (io_dtype == VLPET_BF16) hipLaunchKernelGGL((beam_rows_kernel<__bf16, 2 * KK>), grid, block, 0, s, a);                 \
-        else hipLaunchKernelGGL((beam_rows_kernel<float, 2 * KK>), grid, block, 0, s, a);                                         \
+        if (io_dtype == VLPET_BF16) BR_LAUNCH_AT(__bf16, KK);                                                                      \
+        else BR_LAUNCH_AT(float, KK);                                                                                              \
         break;
     switch (num_beams) { BR_LAUNCH(2) BR_LAUNCH(3) BR_LAUNCH(4) BR_LAUNCH(5) BR_LAUNCH(6) BR_LAUNCH(7) BR_LAUNCH(8) }
 #undef BR_LAUNCH
+#undef BR_LAUNCH_AT
     return herr(hipGetLastError());
 }
 
-extern "C" int vlpet_beam_advance(const float* part_stats, const float* part_val, const int* part_tok, int slices, int V, int B,
-                                  int num_beams, float* beam_scores, const int64_t* ids_in, int64_t* ids_out, int64_t ld_ids,
-                                  const int* key_rows_in, int* key_rows_out, int64_t ld_key_rows, int64_t* next_tokens,
-                                  float* hyp_score, int* hyp_meta, int64_t* hyp_tokens, int64_t ld_hyp, float* item_worst,
-                                  int* item_state, int* counter, int pos, int eos_token_id, int pad_token_id, float length_penalty,
-                                  int early_stopping, vlpet_stream_t stream) {
+int beam_advance_run(const float* part_stats, const float* part_val, const int* part_tok, int slices, int V, int B, int num_beams,
+                     float* beam_scores, const int64_t* ids_in, int64_t* ids_out, int64_t ld_ids, const int* key_rows_in,
+                     int* key_rows_out, int64_t ld_key_rows, int64_t* next_tokens, float* hyp_score, int* hyp_meta,
+                     int64_t* hyp_tokens, int64_t ld_hyp, float* item_worst, int* item_state, int* counter, int pos,
+                     int eos_token_id, int pad_token_id, float length_penalty, int early_stopping, vlpet_stream_t stream, bool at,
+                     const int* pos_dev, int pos_limit, int64_t ps_ids, int64_t ps_kr) {
     if (!part_stats || !part_val || !part_tok || !beam_scores || !ids_in || !ids_out || !next_tokens || !hyp_score || !hyp_meta
         || !hyp_tokens || !item_worst || !item_state || !counter)
         return VLPET_E_NULL;
     if ((key_rows_in == nullptr) != (key_rows_out == nullptr)) return VLPET_E_NULL;
+    if (at) {
+        const int e = check_pos_dev(pos_dev, pos_limit, INT_MAX);
+        if (e) return e;
+        if (ps_ids < 0 || ps_kr < 0) return VLPET_E_SHAPE;
+        pos = pos_limit - 1;
+    }
     if (B <= 0 || V <= 0 || V > GP_MAX_V || num_beams < 2 || num_beams > 8 || slices < 1 || slices > 64) return VLPET_E_SHAPE;
     if (pos < 0 || (int64_t)pos + 1 >= ld_ids || (int64_t)pos + 1 > ld_hyp || (key_rows_in && (int64_t)pos + 1 >= ld_key_rows))
         return VLPET_E_SHAPE;
@@ -709,10 +790,100 @@ extern "C" int vlpet_beam_advance(const float* part_stats, const float* part_val
     a.ld_kr = ld_key_rows; a.next_tokens = next_tokens; a.hyp_score = hyp_score; a.hyp_meta = hyp_meta;
     a.hyp_tokens = hyp_tokens; a.ld_hyp = ld_hyp; a.worst = item_worst; a.state = item_state; a.counter = counter; a.pos = pos;
     a.eos = eos_token_id; a.pad = pad_token_id; a.length_penalty = length_penalty; a.early = early_stopping ? 1 : 0;
+    a.pos_dev = pos_dev; a.pos_limit = pos_limit; a.ps_ids = ps_ids; a.ps_kr = ps_kr;
     hipStream_t s = (hipStream_t)stream;
 #define BA_LAUNCH(KK)                                                                                                              \
-    case KK: hipLaunchKernelGGL((beam_advance_kernel<KK>), dim3(B), dim3(64), 0, s, a); break;
+    case KK:                                                                                                                       \
+        if (at) hipLaunchKernelGGL((beam_advance_kernel<KK, true>), dim3(B), dim3(64), 0, s, a);                                  \
+        else hipLaunchKernelGGL((beam_advance_kernel<KK, false>), dim3(B), dim3(64), 0, s, a);                                    \
+        break;
     switch (num_beams) { BA_LAUNCH(2) BA_LAUNCH(3) BA_LAUNCH(4) BA_LAUNCH(5) BA_LAUNCH(6) BA_LAUNCH(7) BA_LAUNCH(8) }
 #undef BA_LAUNCH
     return herr(hipGetLastError());
+}
+
+}  // namespace
+
+extern "C" int vlpet_attn_decode(const void* q, int64_t ld_q, void* k_cache, void* v_cache, int64_t ld_k, int64_t bs_k,
+                                 int64_t ld_v, int64_t bs_v, const void* k_new, const void* v_new, int64_t ld_new, int pos,
+                                 const uint8_t* key_mask, int64_t ld_mask, const float* bias, int64_t ld_bias, void* o,
+                                 int64_t ld_o, int B, int H, int D, int Lk, float scale, int io_dtype, vlpet_stream_t stream) {
+    return attn_decode_run(q, ld_q, k_cache, v_cache, ld_k, bs_k, ld_v, bs_v, k_new, v_new, ld_new, pos, key_mask, ld_mask, bias,
+                           ld_bias, o, ld_o, B, H, D, Lk, scale, 1, nullptr, 0, io_dtype, stream, false, nullptr, 0, 0, 0);
+}
+
+extern "C" int vlpet_attn_decode_beam(const void* q, int64_t ld_q, void* k_cache, void* v_cache, int64_t ld_k, int64_t bs_k,
+                                      int64_t ld_v, int64_t bs_v, const void* k_new, const void* v_new, int64_t ld_new, int pos,
+                                      const uint8_t* key_mask, int64_t ld_mask, const float* bias, int64_t ld_bias, void* o,
+                                      int64_t ld_o, int B, int H, int D, int Lk, float scale, int group, const int* key_rows,
+                                      int64_t ld_key_rows, int io_dtype, vlpet_stream_t stream) {
+    return attn_decode_run(q, ld_q, k_cache, v_cache, ld_k, bs_k, ld_v, bs_v, k_new, v_new, ld_new, pos, key_mask, ld_mask, bias,
+                           ld_bias, o, ld_o, B, H, D, Lk, scale, group, key_rows, ld_key_rows, io_dtype, stream, false, nullptr, 0,
+                           0, 0);
+}
+
+extern "C" int vlpet_attn_decode_at(const void* q, int64_t ld_q, void* k_cache, void* v_cache, int64_t ld_k, int64_t bs_k,
+                                    int64_t ld_v, int64_t bs_v, const void* k_new, const void* v_new, int64_t ld_new,
+                                    const int* pos_dev, int pos_limit, const uint8_t* key_mask, int64_t ld_mask, const float* bias,
+                                    int64_t ld_bias, int64_t pos_stride_bias, void* o, int64_t ld_o, int B, int H, int D, int Lk,
+                                    float scale, const int* key_rows, int64_t ld_key_rows, int64_t parity_stride_key_rows,
+                                    int io_dtype, vlpet_stream_t stream) {
+    return attn_decode_run(q, ld_q, k_cache, v_cache, ld_k, bs_k, ld_v, bs_v, k_new, v_new, ld_new, 0, key_mask, ld_mask, bias,
+                           ld_bias, o, ld_o, B, H, D, Lk, scale, 1, key_rows, ld_key_rows, io_dtype, stream, true, pos_dev,
+                           pos_limit, pos_stride_bias, parity_stride_key_rows);
+}
+
+extern "C" int vlpet_greedy_pick(const void* logits, int64_t ld, int V, int64_t* ids, int64_t ld_ids, int pos, int* unfinished,
+                                 int* counter, int B, int eos_token_id, int pad_token_id, int min_length, int no_repeat_ngram_size,
+                                 int io_dtype, vlpet_stream_t stream) {
+    return greedy_pick_run(logits, ld, V, ids, ld_ids, pos, unfinished, counter, B, eos_token_id, pad_token_id, min_length,
+                           no_repeat_ngram_size, io_dtype, stream, false, nullptr, 0, nullptr);
+}
+
+extern "C" int vlpet_greedy_pick_at(const void* logits, int64_t ld, int V, int64_t* ids, int64_t ld_ids, const int* pos_dev,
+                                    int pos_limit, int* unfinished, int* counters, int64_t* next_tokens, int B, int eos_token_id,
+                                    int pad_token_id, int min_length, int no_repeat_ngram_size, int io_dtype,
+                                    vlpet_stream_t stream) {
+    return greedy_pick_run(logits, ld, V, ids, ld_ids, 0, unfinished, counters, B, eos_token_id, pad_token_id, min_length,
+                           no_repeat_ngram_size, io_dtype, stream, true, pos_dev, pos_limit, next_tokens);
+}
+
+extern "C" int vlpet_beam_rows(const void* logits, int64_t ld, int V, const int64_t* ids, int64_t ld_ids, int pos, int rows,
+                               int num_beams, int slices, int eos_token_id, int min_length, int no_repeat_ngram_size, int force_eos,
+                               float* part_stats, float* part_val, int* part_tok, int io_dtype, vlpet_stream_t stream) {
+    return beam_rows_run(logits, ld, V, ids, ld_ids, pos, rows, num_beams, slices, eos_token_id, min_length, no_repeat_ngram_size,
+                         force_eos, part_stats, part_val, part_tok, io_dtype, stream, false, nullptr, 0, 0, -1);
+}
+
+extern "C" int vlpet_beam_rows_at(const void* logits, int64_t ld, int V, const int64_t* ids, int64_t ld_ids,
+                                  int64_t parity_stride_ids, const int* pos_dev, int pos_limit, int rows, int num_beams, int slices,
+                                  int eos_token_id, int min_length, int no_repeat_ngram_size, int force_eos_pos, float* part_stats,
+                                  float* part_val, int* part_tok, int io_dtype, vlpet_stream_t stream) {
+    return beam_rows_run(logits, ld, V, ids, ld_ids, 0, rows, num_beams, slices, eos_token_id, min_length, no_repeat_ngram_size, 0,
+                         part_stats, part_val, part_tok, io_dtype, stream, true, pos_dev, pos_limit, parity_stride_ids,
+                         force_eos_pos);
+}
+
+extern "C" int vlpet_beam_advance(const float* part_stats, const float* part_val, const int* part_tok, int slices, int V, int B,
+                                  int num_beams, float* beam_scores, const int64_t* ids_in, int64_t* ids_out, int64_t ld_ids,
+                                  const int* key_rows_in, int* key_rows_out, int64_t ld_key_rows, int64_t* next_tokens,
+                                  float* hyp_score, int* hyp_meta, int64_t* hyp_tokens, int64_t ld_hyp, float* item_worst,
+                                  int* item_state, int* counter, int pos, int eos_token_id, int pad_token_id, float length_penalty,
+                                  int early_stopping, vlpet_stream_t stream) {
+    return beam_advance_run(part_stats, part_val, part_tok, slices, V, B, num_beams, beam_scores, ids_in, ids_out, ld_ids,
+                            key_rows_in, key_rows_out, ld_key_rows, next_tokens, hyp_score, hyp_meta, hyp_tokens, ld_hyp,
+                            item_worst, item_state, counter, pos, eos_token_id, pad_token_id, length_penalty, early_stopping,
+                            stream, false, nullptr, 0, 0, 0);
+}
+
+extern "C" int vlpet_beam_advance_at(const float* part_stats, const float* part_val, const int* part_tok, int slices, int V, int B,
+                                     int num_beams, float* beam_scores, int64_t* ids, int64_t ld_ids, int64_t parity_stride_ids,
+                                     int* key_rows, int64_t ld_key_rows, int64_t parity_stride_key_rows, int64_t* next_tokens,
+                                     float* hyp_score, int* hyp_meta, int64_t* hyp_tokens, int64_t ld_hyp, float* item_worst,
+                                     int* item_state, int* counters, const int* pos_dev, int pos_limit, int eos_token_id,
+                                     int pad_token_id, float length_penalty, int early_stopping, vlpet_stream_t stream) {
+    return beam_advance_run(part_stats, part_val, part_tok, slices, V, B, num_beams, beam_scores, ids, ids, ld_ids, key_rows,
+                            key_rows, ld_key_rows, next_tokens, hyp_score, hyp_meta, hyp_tokens, ld_hyp, item_worst, item_state,
+                            counters, 0, eos_token_id, pad_token_id, length_penalty, early_stopping, stream, true, pos_dev,
+                            pos_limit, parity_stride_ids, parity_stride_key_rows);
 }

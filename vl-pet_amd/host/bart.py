@@ -326,12 +326,13 @@ class BartAttention(nn.Module):
             return qkv[:, :E], qkv[:, E:2 * E], qkv[:, 2 * E:]
         return _linear(self.q_proj, x)[:, 0], _linear(self.k_proj, x)[:, 0], _linear(self.v_proj, x)[:, 0]
 
-    def step_self(self, x, k_cache, v_cache, pos, task=None, key_rows=None):
+    def step_self(self, x, k_cache, v_cache, pos, task=None, key_rows=None, pos_dev=None):
         """causal self-attention of the token at ``pos``: its key / value rows go into cache row ``pos`` inside the attention launch
-        (beam search: earlier keys are looked up through ``key_rows``)"""
+        (beam search: earlier keys are looked up through ``key_rows``).  ``pos_dev``: the position word instead of ``pos``,
+        ``key_rows`` then both ping-pong halves (decode.decode_attention)"""
         q, k, v = self._step_qkv(x, task)
         out = D.decode_attention(q, k_cache, v_cache, self.num_heads, pos=pos, k_new=k, v_new=v, scale=self.head_dim ** -0.5,
-                                 key_rows=key_rows)
+                                 key_rows=key_rows, pos_dev=pos_dev)
         return _linear(self.out_proj, out[:, None])
 
     def cross_values(self, enc, task=None):
@@ -423,8 +424,8 @@ class BartDecoderLayer(nn.Module):
         """generate(): the token x [B, 1, d] at position ``pos``; ``cache`` = this layer's (self k, self v, cross k, cross v) of
         ``state`` (decode.DecodeState)"""
         ks, vs, kx, vx = cache
-        kr = state.key_rows
-        h = self.self_attn.step_self(x, ks, vs, pos, task, key_rows=None if kr is None else kr[pos & 1])
+        kr, pd = state.key_rows, state.pos_dev
+        h = self.self_attn.step_self(x, ks, vs, pos, task, key_rows=kr if kr is None or pd is not None else kr[pos & 1], pos_dev=pd)
         x = sublayer_tail(x, h, self.self_attn_layer_norm, self.dropout, self.training)                     # K5
         h = self.encoder_attn.step_cross(x, kx, vx, state.key_mask, task, group=state.group)
         x = sublayer_tail(x, h, self.encoder_attn_layer_norm, self.dropout, self.training)                  # K5
@@ -538,8 +539,13 @@ class BartDecoder(nn.Module):
         return D.new_decode_state(enc, enc.shape[2], max_length, ks, vs, key_mask, num_beams)
 
     def step(self, tok, pos, state, task=None):
-        """generate(): hidden state [B, d] of the tokens ``tok`` [B] at position ``pos`` (learned position pos + 2)"""
-        x = self.embed_tokens(tok)[:, None] * self.embed_scale + self.embed_positions.weight[pos + 2]
+        """generate(): hidden state [B, d] of the tokens ``tok`` [B] at position ``pos`` (learned position pos + 2); with
+        ``state.pos_dev`` the position is the device word's (a gather) and ``pos`` is not read"""
+        if state.pos_dev is not None:
+            p = self.embed_positions.weight[2:].index_select(0, state.pos_dev)
+        else:
+            p = self.embed_positions.weight[pos + 2]
+        x = self.embed_tokens(tok)[:, None] * self.embed_scale + p
         x = F.dropout(self.layernorm_embedding(x), p=self.dropout, training=self.training)
         for layer, c in zip(self.layers, state.layers):
             x = layer.step(x, c, pos, state, task)
@@ -602,14 +608,17 @@ class VLBart(nn.Module):
         return lm_loss(h, self.model.shared.weight, labels, self._logits_bias())
 
     def generate(self, input_ids, vis_inputs, task, attention_mask=None, max_length=20, min_length=0, no_repeat_ngram_size=0,
-                 eos_token_id=None, pad_token_id=None, no_padding=False, num_beams=1, length_penalty=1.0, early_stopping=False):
+                 eos_token_id=None, pad_token_id=None, no_padding=False, num_beams=1, length_penalty=1.0, early_stopping=False,
+                 graph=False):
         """Greedy search with HF 4.2.1 semantics (num_beams = 1; the reference's evaluation, src/multitask.py test_step) on a per-layer
         key / value cache: the encoder runs once, every step feeds one token (vlpet_amd.decode).  Returns the token ids
         [B, <= max_length], starting with decoder_start_token_id; finished rows are padded.  eos / pad default to the config's
         (BART: 2 / 1).  Pass the checkpoint's own generation settings (min_length, no_repeat_ngram_size) explicitly.
         ``num_beams`` > 1: HF 4.2.1 beam search (one sequence per item; the video captioning evaluation, src/multitask_video.py)
         with ``length_penalty`` / ``early_stopping``, BART's forced eos at the last step, and the cross-attention caches kept per
-        item (decode.beam_generate, which also returns each sequence's score)."""
+        item (decode.beam_generate, which also returns each sequence's score).
+        ``graph=True``: the decode step is captured once per shape and replayed (decode.graph_generate: the first call of a shape
+        runs eagerly, the second captures); CPU tensors and inputs the decode kernels do not take run the plain loop."""
         from ..lmloss import _padded_head
         cfg = self.config
         eos = getattr(cfg, "eos_token_id", 2) if eos_token_id is None else eos_token_id
@@ -623,10 +632,17 @@ class VLBart(nn.Module):
             head = _padded_head(self.model.shared.weight, enc.dtype)
             bias = self._logits_bias()
 
-            def step(tok, pos):
-                logits = F.linear(dec.step(tok, pos, state, task), head)
-                if bias is not None:
-                    logits[:, :V] += bias[0].to(logits.dtype)
-                return logits
-            return D.generate(step, V, enc.shape[0], enc.device, state.key_rows, cfg.decoder_start_token_id, eos, pad, max_length,
-                              min_length, no_repeat_ngram_size, int(num_beams), length_penalty, early_stopping, force_eos=True)
+            def make_step(st):
+                def step(tok, pos):
+                    logits = F.linear(dec.step(tok, pos, st, task), head)
+                    if bias is not None:
+                        logits[:, :V] += bias[0].to(logits.dtype)
+                    return logits
+                return step
+            if graph:
+                gs = D.GenSettings(cfg.decoder_start_token_id, eos, int(pad), int(max_length), int(min_length),
+                                   int(no_repeat_ngram_size), int(num_beams), float(length_penalty), bool(early_stopping), True)
+                return D.graph_generate(self, state, make_step, V, cfg.decoder_attention_heads, head, gs, key_extra=(task,))[0]
+            return D.generate(make_step(state), V, enc.shape[0], enc.device, state.key_rows, cfg.decoder_start_token_id, eos, pad,
+                              max_length, min_length, no_repeat_ngram_size, int(num_beams), length_penalty, early_stopping,
+                              force_eos=True)

@@ -310,9 +310,10 @@ class T5Attention(nn.Module):
 
 
     # ---- generate(): one decoder token against the caches (decode.decode_attention, scale 1: T5 has no 1/sqrt(d))
-    def step_self(self, n, k_cache, v_cache, pos, bias_row, key_rows=None):
+    def step_self(self, n, k_cache, v_cache, pos, bias_row, key_rows=None, pos_dev=None):
         """causal self-attention of the normed token n [B, 1, d] at ``pos``; ``bias_row`` [H, >= pos + 1]: row ``pos`` of the
-        decoder's relative position bias"""
+        decoder's relative position bias.  ``pos_dev``: the position word instead of ``pos``; ``bias_row`` is then the whole bias
+        table and ``key_rows`` both ping-pong halves (decode.decode_attention)"""
         E = self.inner
         if FUSE_QKV:
             qkv = F.linear(n[:, 0], self._fused_qkv(n.dtype))
@@ -320,7 +321,7 @@ class T5Attention(nn.Module):
         else:
             q, k, v = _linear(self.q, n)[:, 0], _linear(self.k, n)[:, 0], _linear(self.v, n)[:, 0]
         out = D.decode_attention(q, k_cache, v_cache, self.n_heads, pos=pos, k_new=k, v_new=v, bias=bias_row, scale=1.0,
-                                 key_rows=key_rows)
+                                 key_rows=key_rows, pos_dev=pos_dev)
         return _linear(self.o, out[:, None])
 
     def cross_values(self, enc, task=None):
@@ -418,8 +419,9 @@ def _block_step(blk, x, cache, pos, state, bias_row):
     with the next sublayer's norm)."""
     sa, ca, ff = blk.layer[0], blk.layer[1], blk.layer[-1]
     ks, vs, kx, vx = cache
-    kr = state.key_rows
-    y = sa.SelfAttention.step_self(sa.layer_norm(x), ks, vs, pos, bias_row, key_rows=None if kr is None else kr[pos & 1])
+    kr, pd = state.key_rows, state.pos_dev
+    y = sa.SelfAttention.step_self(sa.layer_norm(x), ks, vs, pos, bias_row,
+                                   key_rows=kr if kr is None or pd is not None else kr[pos & 1], pos_dev=pd)
     x = _tail_linked(x, y, sa.p, sa.training, None, layer=sa)
     y = ca.EncDecAttention.step_cross(ca.layer_norm(x), kx, vx, state.key_mask, group=state.group)
     x = _tail_linked(x, y, ca.p, ca.training, None, layer=ca)
@@ -527,7 +529,7 @@ class T5Decoder(nn.Module):
 
     def step(self, tok, pos, state):
         x = F.dropout(self.embed_tokens(tok)[:, None], p=self.p, training=self.training)
-        bias_row = state.bias_table[pos]
+        bias_row = state.bias_table if state.pos_dev is not None else state.bias_table[pos]    # (the kernel takes row *pos_dev)
         for blk, c in zip(self.block, state.layers):
             x = _block_step(blk, x, c, pos, state, bias_row)
         return F.dropout(self.final_layer_norm(x), p=self.p, training=self.training)[:, 0]
@@ -574,10 +576,11 @@ class VLT5(nn.Module):
         return lm_loss(h, self.shared.weight, labels)
 
     def generate(self, input_ids, vis_inputs, task, attention_mask=None, max_length=20, min_length=0, no_repeat_ngram_size=0,
-                 eos_token_id=None, pad_token_id=None, no_padding=False, num_beams=1, length_penalty=1.0, early_stopping=False):
+                 eos_token_id=None, pad_token_id=None, no_padding=False, num_beams=1, length_penalty=1.0, early_stopping=False,
+                 graph=False):
         """Greedy search with HF 4.2.1 semantics on per-block key / value caches (see host/bart.py VLBart.generate).  eos / pad
         default to T5's 1 / 0; the output starts with decoder_start_token_id (0).  ``num_beams`` > 1: HF 4.2.1 beam search as in
-        VLBart.generate (T5 forces no eos)."""
+        VLBart.generate (T5 forces no eos).  ``graph=True``: the captured, replayed decode step, as there."""
         from ..lmloss import _padded_head
         cfg = self.config
         eos = getattr(cfg, "eos_token_id", 1) if eos_token_id is None else eos_token_id
@@ -589,7 +592,12 @@ class VLT5(nn.Module):
             head = _padded_head(self.shared.weight, enc.dtype)
             scale = cfg.d_model ** -0.5
 
-            def step(tok, pos):
-                return F.linear(self.decoder.step(tok, pos, state) * scale, head)
-            return D.generate(step, V, enc.shape[0], enc.device, state.key_rows, cfg.decoder_start_token_id, eos, pad, max_length,
-                              min_length, no_repeat_ngram_size, int(num_beams), length_penalty, early_stopping, force_eos=False)
+            def make_step(st):
+                return lambda tok, pos: F.linear(self.decoder.step(tok, pos, st) * scale, head)
+            if graph:
+                gs = D.GenSettings(cfg.decoder_start_token_id, eos, int(pad), int(max_length), int(min_length),
+                                   int(no_repeat_ngram_size), int(num_beams), float(length_penalty), bool(early_stopping), False)
+                return D.graph_generate(self, state, make_step, V, cfg.num_heads, head, gs, key_extra=(task,))[0]
+            return D.generate(make_step(state), V, enc.shape[0], enc.device, state.key_rows, cfg.decoder_start_token_id, eos, pad,
+                              max_length, min_length, no_repeat_ngram_size, int(num_beams), length_penalty, early_stopping,
+                              force_eos=False)
