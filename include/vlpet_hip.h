@@ -553,6 +553,16 @@ int vlpet_attn_bwd_kv(const void* q, const void* k, const void* v, const void* o
                       const uint8_t* key_mask, const float* bias, const float* bias_t, void* dq, void* dk, void* dv,
                       int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, int causal, float scale, float p, uint64_t seed,
                       vlpet_stream_t stream);
+/* Attention forward for up to VLPET_ATTN_LONG_MAX_LEN keys and queries: o = softmax(scale * q k^T + bias[h] + masks) v, the same
+ * layouts, masks (key_mask [B, Lk] bytes, causal: key j visible to query i iff j <= i + Lk - Lq), bias table and lse convention
+ * (log2 units, +inf for a row with no visible key, which gets an all-zero output row) as vlpet_attn_fwd_kv, without dropout and
+ * without a backward: the inference form for the video configuration's 664-token encoder.  Keys are streamed in chunks with an
+ * online softmax whose summation order depends on (Lq, Lk) only: the result is bitwise reproducible and does not depend on B or
+ * on the other items of the batch.  Allocates nothing, enqueues on `stream`, does not synchronise. */
+#define VLPET_ATTN_LONG_MAX_LEN 1024
+int vlpet_attn_long_fwd(const void* q, const void* k, const void* v, const uint8_t* key_mask, const float* bias, void* o,
+                        float* lse, int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, int causal, float scale,
+                        vlpet_stream_t stream);
 
 /* ---- Downsample (the step before K4) -------------------------------------------------------
  * AdaptiveMaxPool2d(s_in x s_in -> s_out x s_out) over the token grid of x [n_images, s_in*s_in, dim]

@@ -1,11 +1,77 @@
 #!/usr/bin/env python3
-"""Short-sequence attention kernels vs torch SDPA at the configs[1] encoder shapes (HIP events on the launch stream)."""
+"""Short-sequence attention kernels vs torch SDPA at the configs[1] encoder shapes (HIP events on the launch stream).
+
+    python tools/attnbench.py                  # the short kernels, forward and backward, ATTNBENCH_P = dropout
+    python tools/attnbench.py long [rounds]    # the long forward (csrc/attn_long.hip) against the SDPA forward the hosts otherwise call,
+                                               # at the video encoder's shapes, no_grad, key mask present, alternating legs; every
+                                               # timed call starts cold (ATTNBENCH_WARM=1: back-to-back calls instead)
+"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch
 import torch.nn.functional as F
 from vlpet_amd.attention import short_attention
+
+MFMA_PEAK = 2.5e15      # bf16 dense MFMA FLOP/s of the chip (the roofline figure of DESIGN.md)
+
+
+def long_bench(rounds):
+    """us per call (median over the rounds' calls) of long_attention and of F.scaled_dot_product_attention on the same inputs; as in
+    tools/k1bench.py's K1BENCH_COLD a read-modify-write over 1 GiB runs before every timed call, so that neither leg reads its
+    inputs from the Infinity Cache the previous call filled"""
+    import statistics
+    from vlpet_amd.attention import AttnBias, long_attention
+    H, S = 12, 664
+    cold = not os.environ.get("ATTNBENCH_WARM")
+    evict = torch.zeros(1 << 28, dtype=torch.float32, device="cuda") if cold else None
+
+    def one(fn):
+        if cold:
+            evict.add_(1.0)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(); fn(); e1.record(); torch.cuda.synchronize()
+        return e0.elapsed_time(e1) * 1e3
+
+    with torch.no_grad():
+        for name, B, biased in [("bart", 50, False), ("t5", 30, True)]:
+            g = torch.Generator(device="cuda").manual_seed(1)
+            amp = 0.4 if biased else 1.5
+            q, k, v = ((torch.randn(B, S, H * 64, device="cuda", generator=g) * amp).bfloat16() for _ in range(3))
+            lens = torch.randint(400, S + 1, (B,), device="cuda", generator=g)
+            keep = torch.arange(S, device="cuda")[None, :] < lens[:, None]
+            sh = lambda t: t.view(B, S, H, 64).transpose(1, 2)
+            if biased:      # T5: scale 1, the shared bias; the library path takes the merged dense additive mask (host/t5.py AttnSpec.dense)
+                rel = torch.randn(1, H, S, S, device="cuda", generator=g)
+                bias = AttnBias(rel, transposed=False)
+                dense = (rel + (1.0 - keep[:, None, None, :].float()) * -10000.0).bfloat16()
+                ours = lambda: long_attention(q, k, v, H, keep, scale=1.0, bias=bias)
+                lib = lambda: F.scaled_dot_product_attention(sh(q), sh(k), sh(v), attn_mask=dense, scale=1.0).transpose(1, 2).reshape(B, S, H * 64)
+            else:
+                mask = keep[:, None, None, :]
+                ours = lambda: long_attention(q, k, v, H, keep)
+                lib = lambda: F.scaled_dot_product_attention(sh(q), sh(k), sh(v), attn_mask=mask).transpose(1, 2).reshape(B, S, H * 64)
+            a, b = ours().float(), lib().float()
+            live = keep[:, :, None].float()
+            err = float(((a - b) * live).abs().max() / b.abs().max())
+            t = {"long": [], "sdpa": []}
+            for _ in range(3):
+                one(ours); one(lib)
+            for _ in range(rounds):
+                for leg, fn in (("long", ours), ("sdpa", lib)):
+                    t[leg] += [one(fn) for _ in range(5)]
+            flops = 4.0 * B * H * S * S * 64
+            for leg in ("long", "sdpa"):
+                us = statistics.median(t[leg])
+                print(f"attnbench long {name:4s} B={B} H={H} S={S} {'cold' if cold else 'warm'} {leg:4s}: median {us:8.1f} us  min {min(t[leg]):8.1f}  "
+                      f"max {max(t[leg]):8.1f}  ({len(t[leg])} calls)  {flops / (us * 1e-6) / 1e12:6.1f} TFLOP/s = {flops / (us * 1e-6) / MFMA_PEAK:.3f} of the bf16 MFMA peak")
+            print(f"attnbench long {name:4s}: long / sdpa = {statistics.median(t['long']) / statistics.median(t['sdpa']):.3f}   max |long - sdpa| / max |sdpa| = {err:.2e}",
+                  flush=True)
+
+
+if len(sys.argv) > 1 and sys.argv[1] == "long":
+    long_bench(int(sys.argv[2]) if len(sys.argv) > 2 else 4)
+    sys.exit(0)
 
 def timeit(fn, iters=30, warm=5):
     for _ in range(warm): fn()

@@ -21,6 +21,10 @@ Beam search (``--num-beams K``, K > 1): generate(num_beams = K) at the video cap
 664, max_length 20, every step run: min_length = max_length) for BART-base VL-PET on the video config (B = 50) and T5-base VL-PET
 (B = 30), hip against torch (decode.EAGER).  ``--stats FILE --num-beams K`` reads the kernel stats of a `--num-beams K --paths hip
 --reps 1 --warmup 0 --models bart` run.
+
+``--long-attention``: the hosts' LONG_ATTENTION switch on for every leg (the 664-token encoder on csrc/attn_long.hip).
+``--long-ab N`` (with ``--num-beams``): after the legs, N rounds of alternating switch-off / switch-on hip calls, two successive
+calls each: ms per call of both settings and the fraction of tokens on which the two successive calls agree (1.0 = reproducible).
 """
 import argparse
 import csv
@@ -267,6 +271,27 @@ def run_beams(args):
             print(json.dumps(dict(model=kind, tokens_equal_to_hip="graph", fraction=round(agree, 4))), flush=True)
             if args.ab_rounds > 0:
                 ab_rounds(args, {p: calls[p] for p in ("hip", "graph")}, ml - 1, dict(model=kind, num_beams=args.num_beams))
+        if args.long_ab > 0 and "hip" in calls:
+            import vlpet_amd.host.t5 as HT
+            per, agree = {"off": [], "on": []}, {"off": [], "on": []}
+            saved = (HB.LONG_ATTENTION, HT.LONG_ATTENTION)
+            try:
+                for _ in range(args.long_ab):
+                    for leg in ("off", "on"):
+                        HB.LONG_ATTENTION = HT.LONG_ATTENTION = leg == "on"
+                        torch.cuda.synchronize()
+                        t = time.perf_counter()
+                        a, b2 = calls["hip"](), calls["hip"]()
+                        torch.cuda.synchronize()
+                        per[leg].append((time.perf_counter() - t) * 1e3 / 2)
+                        agree[leg].append(float((a == b2).float().mean()) if a.shape == b2.shape else 0.0)
+            finally:
+                HB.LONG_ATTENTION, HT.LONG_ATTENTION = saved
+            print(json.dumps(dict(model=kind, num_beams=args.num_beams, B=sh["B"], enc_len=enc_len, long_ab_rounds=args.long_ab,
+                                  **{f"long_{leg}_ms": [round(x, 2) for x in per[leg]] for leg in per},
+                                  **{f"long_{leg}_mean_ms": round(sum(per[leg]) / len(per[leg]), 2) for leg in per},
+                                  **{f"long_{leg}_successive_calls_token_agreement": [round(x, 4) for x in agree[leg]] for leg in agree})),
+                  flush=True)
         if "hip" in outs and "torch" in outs:
             o, h = outs["torch"], outs["hip"]
             agree = float((o == h).float().mean()) if o.shape == h.shape else 0.0
@@ -358,7 +383,13 @@ def main():
     ap.add_argument("--stats", default=None)
     ap.add_argument("--num-beams", type=int, default=1)
     ap.add_argument("--models", nargs="+", default=["bart", "t5"], choices=list(BEAM_SHAPES))
+    ap.add_argument("--long-attention", action="store_true", help="set the hosts' LONG_ATTENTION switch for every leg")
+    ap.add_argument("--long-ab", type=int, default=0, help="with --num-beams: alternating switch-off / switch-on rounds of the hip leg")
     args = ap.parse_args()
+    if args.long_attention:
+        import vlpet_amd.host.bart as HB
+        import vlpet_amd.host.t5 as HT
+        HB.LONG_ATTENTION = HT.LONG_ATTENTION = True
     if args.stats:
         for r in (stats(args.stats) if args.num_beams == 1 else beam_stats(args.stats, args.num_beams)):
             print(json.dumps(r))

@@ -7,6 +7,8 @@ F.dropout(p=attention_dropout), bmm, head transposes.  Tensors stay in the ``[B,
 produce (no head transpose / re-pack in either direction).  ``supported`` tells the caller whether a call fits; anything
 else (fp32 parity runs, long video sequences, per-sample additive biases) stays on the library path.  A bias shared by the
 batch -- T5's relative position bias (my_transformers/modeling_t5.py:520-560, 640-660) -- is taken as ``AttnBias`` (round 4).
+``long_attention`` / ``long_self_attention`` (csrc/attn_long.hip) are the forward alone for up to 1,024 keys / queries -- the video
+configuration's 664-token encoder under ``no_grad`` -- with a fixed summation order: no dropout, no autograd.
 No CPU fallback."""
 from __future__ import annotations
 
@@ -19,15 +21,19 @@ from .functional import _need_cuda, _ptr, _stream, _timed
 from .tail import _draw_seed
 
 MAX_LEN = 128
+MAX_LONG = 1024      # the forward-only kernel of csrc/attn_long.hip (long_attention below)
 HEAD_DIM = 64
+LONG_CALLS = 0       # launches of the long kernel so far (tests tell by it which path ran)
 
 
 class AttnBias:
     """An additive score bias ``[1 or none, H, Lq, Lk]`` shared by every sample, in the layout the kernels read: fp32, both
     sequence axes zero-padded to multiples of 32, plus its transpose for the key-major phase of the backward.  Built once per
-    forward (it is the same for every layer of a T5 stack) and passed to ``short_attention(..., bias=...)``.  No gradient."""
+    forward (it is the same for every layer of a T5 stack) and passed to ``short_attention(..., bias=...)``.  No gradient.
+    ``transposed=False`` leaves the transpose to its first reader: a forward-only user (``long_attention`` at [12, 672, 672]: 21.7 MB
+    per table) never builds it."""
 
-    def __init__(self, bias: torch.Tensor):
+    def __init__(self, bias: torch.Tensor, transposed: bool = True):
         b = bias.detach()
         if b.dim() == 4:
             if b.shape[0] != 1:
@@ -38,7 +44,13 @@ class AttnBias:
         self.H, self.Lq, self.Lk = H, Lq, Lk
         self.b = torch.zeros(H, Lqp, Lkp, dtype=torch.float32, device=b.device)
         self.b[:, :Lq, :Lk] = b.float()
-        self.bt = self.b.transpose(1, 2).contiguous()
+        self._bt = self.b.transpose(1, 2).contiguous() if transposed else None
+
+    @property
+    def bt(self) -> torch.Tensor:
+        if self._bt is None:
+            self._bt = self.b.transpose(1, 2).contiguous()
+        return self._bt
 
 
 def supported(q: torch.Tensor, k: torch.Tensor, num_heads: int) -> bool:
@@ -228,3 +240,74 @@ def short_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads
         seed = _draw_seed() if pe > 0.0 else 0
     return _AttnFn.apply(q, k, v, key_mask, num_heads, bool(causal), HEAD_DIM ** -0.5 if scale is None else float(scale),
                          pe, int(seed), bool(return_mask), bias, k_slot)
+
+
+# ---- up to MAX_LONG keys / queries, forward only (csrc/attn_long.hip): the video configuration's 664-token encoder under no_grad
+def supported_long(q: torch.Tensor, k: torch.Tensor, num_heads: int) -> bool:
+    return (q.is_cuda and k.is_cuda and q.dtype == torch.bfloat16 and k.dtype == torch.bfloat16 and q.dim() == 3 and k.dim() == 3
+            and q.shape[-1] == num_heads * HEAD_DIM and k.shape[-1] == num_heads * HEAD_DIM
+            and 1 <= q.shape[1] <= MAX_LONG and 1 <= k.shape[1] <= MAX_LONG)
+
+
+def _no_grad_needed(*tensors) -> None:
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise RuntimeError("vl-pet_amd: long_attention is forward only (no autograd): call it under torch.no_grad() or on tensors "
+                           "that need no gradient")
+
+
+def _launch_long(q_ptr, k_ptr, v_ptr, key_mask, bias, o, lse, B, H, Lq, Lk, ld_q, ld_k, ld_v, causal, scale):
+    global LONG_CALLS
+    if scale == 0.0:
+        raise RuntimeError("vl-pet_amd: long_attention needs a nonzero scale")
+    if bias is not None and (bias.H, bias.Lq, bias.Lk) != (H, Lq, Lk):
+        raise RuntimeError(f"vl-pet_amd: attention bias [{bias.H}, {bias.Lq}, {bias.Lk}] does not match [{H}, {Lq}, {Lk}]")
+    lib = _lib.load()
+    LONG_CALLS += 1
+    rc = _timed("attn_long_fwd", B * Lq, lambda: lib.vlpet_attn_long_fwd(
+        q_ptr, k_ptr, v_ptr, _ptr(key_mask), bias.b.data_ptr() if bias is not None else None, o.data_ptr(), lse.data_ptr(),
+        B, H, Lq, Lk, ld_q, ld_k, ld_v, int(causal), float(scale), _stream()))
+    _lib.check(rc, "vlpet_attn_long_fwd")
+
+
+def long_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, key_mask: Optional[torch.Tensor] = None,
+                   causal: bool = False, scale: Optional[float] = None, bias: Optional[AttnBias] = None, return_lse: bool = False):
+    """q [B, Lq, H*64], k / v [B, Lk, H*64] (bf16, 1 <= Lq, Lk <= 1024) -> softmax(scale q k^T + bias + masks) v [B, Lq, H*64]; with
+    ``return_lse`` also the rows' log-sum-exp [B, H, Lq] (fp32, log2 units of the scaled scores, +inf for a row with no visible
+    key -- such a row's output is zero).  Masks and bias as in ``short_attention``; no dropout, no autograd, no CPU fallback.
+    k and v are read in place when they are column blocks of wider row-major buffers.  Bitwise reproducible; an item's result
+    does not depend on the rest of the batch."""
+    if not (isinstance(q, torch.Tensor) and isinstance(k, torch.Tensor) and isinstance(v, torch.Tensor)) or not supported_long(q, k, num_heads) \
+            or v.dtype != q.dtype or not v.is_cuda or v.shape != k.shape or k.shape[0] != q.shape[0]:
+        raise RuntimeError("vl-pet_amd: long_attention needs bf16 CUDA tensors [B, L, H*64] with 1 <= Lq, Lk <= 1024 (k and v alike)")
+    _no_grad_needed(q, k, v)
+    q, k, v = (t if _is_row_block(t) else t.contiguous() for t in (q.detach(), k.detach(), v.detach()))
+    B, Lq, E = q.shape
+    Lk = k.shape[1]
+    if key_mask is not None:
+        key_mask = _key_mask_u8(key_mask, B, Lk)
+    o = torch.empty(B, Lq, E, dtype=q.dtype, device=q.device)
+    lse = torch.empty(B, num_heads, Lq, dtype=torch.float32, device=q.device)
+    _launch_long(q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask, bias, o, lse, B, num_heads, Lq, Lk, q.stride(1), k.stride(1),
+                 v.stride(1), causal, HEAD_DIM ** -0.5 if scale is None else float(scale))
+    return (o, lse) if return_lse else o
+
+
+def long_self_attention(qkv: torch.Tensor, num_heads: int, key_mask: Optional[torch.Tensor] = None, causal: bool = False,
+                        scale: Optional[float] = None, bias: Optional[AttnBias] = None):
+    """qkv [B, L, 3*H*64] (bf16; the output of one fused q|k|v projection, L <= 1024) -> [B, L, H*64]: ``long_attention`` on the three
+    column blocks, read in place."""
+    if not (isinstance(qkv, torch.Tensor) and qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3
+            and qkv.shape[-1] == 3 * num_heads * HEAD_DIM and 1 <= qkv.shape[1] <= MAX_LONG):
+        raise RuntimeError("vl-pet_amd: long_self_attention needs a bf16 CUDA [B, L, 3*H*64] tensor with L <= 1024")
+    _no_grad_needed(qkv)
+    qkv = qkv.detach().contiguous()
+    B, L, E3 = qkv.shape
+    E = E3 // 3
+    if key_mask is not None:
+        key_mask = _key_mask_u8(key_mask, B, L)
+    o = torch.empty(B, L, E, dtype=qkv.dtype, device=qkv.device)
+    lse = torch.empty(B, num_heads, L, dtype=torch.float32, device=qkv.device)
+    base, esz = qkv.data_ptr(), qkv.element_size()
+    _launch_long(base, base + E * esz, base + 2 * E * esz, key_mask, bias, o, lse, B, num_heads, L, L, E3, E3, E3, causal,
+                 HEAD_DIM ** -0.5 if scale is None else float(scale))
+    return o

@@ -453,3 +453,6 @@ struct AttnArgs {
 };
 size_t attn_lds_bytes(int Lq, int Lk, int bwd);
 hipError_t launch_attn(const AttnArgs& a, bool bwd, hipStream_t stream);
+// the forward for up to 1,024 keys / queries (attn_long.hip): keys streamed through LDS with an online softmax; no dropout (thr, seed,
+// keep_out, dout, dq / dk / dv and bias_t are not read)
+hipError_t launch_attn_long_fwd(const AttnArgs& a, hipStream_t stream);

@@ -178,7 +178,14 @@ def relative_position_bucket(relative_position, bidirectional, num_buckets=32, m
 
 
 EAGER_ATTENTION = False   # A/B switch (tools/ab_switches.py): True = torch SDPA with a dense additive mask for every T5 attention
+LONG_ATTENTION = False    # switch (host/bart.py: the same): True = 129 .. 1,024 tokens on vlpet_amd.attention's forward-only long kernel
+                          # wherever no dropout and no gradient is needed; the dense [B, H, L, L] mask is not built on that path
 FUSE_QKV = True           # A/B switch: False = separate q / k / v projections in self-attention
+
+
+def _long_applies(Lq, Lk, p, training, *tensors) -> bool:
+    return (LONG_ATTENTION and not EAGER_ATTENTION and max(Lq, Lk) > A.MAX_LEN and Lq <= A.MAX_LONG and Lk <= A.MAX_LONG
+            and (not training or p == 0) and not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)))
 FUSE_CROSS_KEYS = True    # A/B switch: False = every decoder block projects its own cross-attention keys (host/bart.py: the same fusion)
 
 
@@ -214,7 +221,8 @@ class AttnSpec:
         if self.rel_trainable:
             return None
         if self._fast is None:
-            bias = A.AttnBias(self.rel) if self.rel is not None else None
+            # (the transposed copy is the backward's: a forward-only long-kernel pass does not build it)
+            bias = A.AttnBias(self.rel, transposed=not (LONG_ATTENTION and not torch.is_grad_enabled())) if self.rel is not None else None
             km = None if self.keep is None else (self.keep > 0.5).to(torch.uint8).contiguous()
             self._fast = (bias, km)
         return self._fast
@@ -263,8 +271,10 @@ class T5Attention(nn.Module):
         src = hidden if kv is None else kv
         k_slot = None
         spec = bias if isinstance(bias, AttnSpec) else None
+        long_ = _long_applies(Lq, src.shape[1], self.dropout, self.training, hidden, src)
         if (kv is None and FUSE_QKV and spec is not None and not EAGER_ATTENTION and hidden.is_cuda and hidden.dtype == torch.bfloat16
-                and self.d_kv == A.HEAD_DIM and Lq <= A.MAX_LEN and not any(m.weight.requires_grad for m in (self.q, self.k, self.v))):
+                and self.d_kv == A.HEAD_DIM and (Lq <= A.MAX_LEN or long_)
+                and not any(m.weight.requires_grad for m in (self.q, self.k, self.v))):
             fast = spec.fast()
             if fast is not None:
                 # self-attention with frozen projections: ONE [d -> 3 inner] GEMM each way (T5's projections carry no bias), the
@@ -275,7 +285,10 @@ class T5Attention(nn.Module):
                     qkv = VF.linear_acc(hidden, None, (w, None))
                 else:
                     qkv = F.linear(hidden, w)
-                out = A.short_self_attention(qkv, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0, bias=fast[0])
+                if Lq > A.MAX_LEN:
+                    out = A.long_self_attention(qkv, self.n_heads, fast[1], spec.causal, scale=1.0, bias=fast[0])
+                else:
+                    out = A.short_self_attention(qkv, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0, bias=fast[0])
                 return _linear(self.o, out)
         fused = (FUSE_RESIDUAL_GRAD and FUSE_NORM_GRAD and hidden.is_cuda and torch.is_grad_enabled() and src.requires_grad
                  and not any(m.weight.requires_grad for m in (self.q, self.k, self.v)))
@@ -302,6 +315,12 @@ class T5Attention(nn.Module):
             if fast is not None:        # on-chip kernels: bias shared by the batch + boolean key mask + causal flag; T5 has no 1/sqrt(d)
                 out = A.short_attention(q, k, v, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0, bias=fast[0],
                                         k_slot=k_slot)
+                return _linear(self.o, out)
+        if (spec is not None and long_ and self.d_kv == A.HEAD_DIM and v.dtype == q.dtype and A.supported_long(q, k, self.n_heads)
+                and not (torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)))):
+            fast = spec.fast()
+            if fast is not None:
+                out = A.long_attention(q, k, v, self.n_heads, fast[1], spec.causal, scale=1.0, bias=fast[0])
                 return _linear(self.o, out)
         mask = spec.dense(q.dtype) if spec is not None else (None if bias is None else bias.to(q.dtype))
         out = F.scaled_dot_product_attention(self._shape(q, B), self._shape(k.contiguous(), B), self._shape(v, B), attn_mask=mask,
