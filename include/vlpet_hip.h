@@ -563,6 +563,22 @@ int vlpet_attn_bwd_kv(const void* q, const void* k, const void* v, const void* o
 int vlpet_attn_long_fwd(const void* q, const void* k, const void* v, const uint8_t* key_mask, const float* bias, void* o,
                         float* lse, int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, int causal, float scale,
                         vlpet_stream_t stream);
+/* The training form at these lengths.  vlpet_attn_long_fwd_train: the same forward with dropout on the probabilities -- element
+ * (b, h, i, j) is kept by the rule of vlpet_attn_fwd_kv (seed, the device step counter when one is set), kept probabilities are scaled
+ * by 1 / (1 - p), lse is the log-sum-exp of the undropped scores; keep_out: optional [B, H, Lq, Lk] bytes (tests), written only when
+ * p > 0.  With p = 0 it returns the bits of vlpet_attn_long_fwd.  vlpet_attn_long_bwd: dq, dk, dv from q, k, v, o, dout and lse with the
+ * arguments of vlpet_attn_bwd_kv (bias_t is accepted and not read: may be NULL) plus `delta`, [B, H, Lq] fp32 of scratch (sum_d dO O per
+ * row, written by the first of its two launches and read by the second).  No atomics, nothing summed across workgroups: every sum's
+ * order depends on (Lq, Lk) only, so the gradients are bitwise reproducible and an item's do not depend on B.  A row with no visible
+ * key gets a zero dq row and contributes nothing to dk / dv.  p outside [0, 1): VLPET_E_SHAPE.  Both allocate nothing, enqueue on
+ * `stream` and do not synchronise. */
+int vlpet_attn_long_fwd_train(const void* q, const void* k, const void* v, const uint8_t* key_mask, const float* bias, void* o,
+                              float* lse, uint8_t* keep_out, int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, int causal,
+                              float scale, float p, uint64_t seed, vlpet_stream_t stream);
+int vlpet_attn_long_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                        const uint8_t* key_mask, const float* bias, const float* bias_t, void* dq, void* dk, void* dv,
+                        int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, int causal, float scale, float p, uint64_t seed,
+                        float* delta, vlpet_stream_t stream);
 
 /* ---- Downsample (the step before K4) -------------------------------------------------------
  * AdaptiveMaxPool2d(s_in x s_in -> s_out x s_out) over the token grid of x [n_images, s_in*s_in, dim]

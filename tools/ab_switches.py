@@ -4,7 +4,7 @@ VLPET_AB=1): the product package itself reads nothing from the environment at im
     VLPET_EAGER_FFN_ACT=1, VLPET_EAGER_LM_LOSS=1, VLPET_EAGER_ATTENTION=1, VLPET_EAGER_RMS_NORM=1, VLPET_SPLIT_WIDE=1, VLPET_SDPA=flash|efficient|math, VLPET_NO_DEFER_REDUCES=1,
     VLPET_K4_FORM=gemm|library|fused, VLPET_SAVE_PRENORM=auto|0|1, VLPET_NO_TAIL_NORM_FUSION=1, VLPET_NO_ALIAS_RESIDUAL_GRAD=1,
     VLPET_K1_BWD_FROM_X2=1, VLPET_FINALIZE_LAUNCH=1, VLPET_NO_POS_KERNEL=1, VLPET_NO_FANOUT_SUM=1, VLPET_NO_FUSED_CROSS_KEYS=1, VLPET_NO_CONCAT_DROPOUT=1,
-    VLPET_LONG_ATTENTION=1"""
+    VLPET_LONG_ATTENTION=1, VLPET_LONG_ATTENTION_TRAIN=1"""
 import os
 
 
@@ -33,6 +33,7 @@ def apply():
     put(HB, "EAGER_ATTENTION", on("VLPET_EAGER_ATTENTION"))
     put(HT, "EAGER_ATTENTION", on("VLPET_EAGER_ATTENTION"))
     put(HB, "LONG_ATTENTION", on("VLPET_LONG_ATTENTION")); put(HT, "LONG_ATTENTION", on("VLPET_LONG_ATTENTION"))      # 129 .. 1,024 tokens on the forward-only long kernel (no_grad / eval)
+    put(HB, "LONG_ATTENTION_TRAIN", on("VLPET_LONG_ATTENTION_TRAIN")); put(HT, "LONG_ATTENTION_TRAIN", on("VLPET_LONG_ATTENTION_TRAIN"))      # ... and on the long training kernels wherever dropout or a gradient is needed
     put(HB, "FUSE_QKV", not on("VLPET_NO_FUSED_QKV"))
     put(HB, "FUSE_CROSS_KEYS", not on("VLPET_NO_FUSED_CROSS_KEYS")); put(HT, "FUSE_CROSS_KEYS", not on("VLPET_NO_FUSED_CROSS_KEYS"))        # the decoder layers' cross-attention key projections as one GEMM each way
     put(HT, "FUSE_QKV", not on("VLPET_NO_FUSED_QKV"))

@@ -9,6 +9,8 @@ else (fp32 parity runs, long video sequences, per-sample additive biases) stays 
 batch -- T5's relative position bias (my_transformers/modeling_t5.py:520-560, 640-660) -- is taken as ``AttnBias`` (round 4).
 ``long_attention`` / ``long_self_attention`` (csrc/attn_long.hip) are the forward alone for up to 1,024 keys / queries -- the video
 configuration's 664-token encoder under ``no_grad`` -- with a fixed summation order: no dropout, no autograd.
+``long_attention_train`` / ``long_self_attention_train`` (csrc/attn_long.hip with dropout + csrc/attn_long_bwd.hip) are the training
+form at those lengths: dropout by the short kernels' mask rule and a backward whose sums have a fixed order as well.
 No CPU fallback."""
 from __future__ import annotations
 
@@ -24,6 +26,7 @@ MAX_LEN = 128
 MAX_LONG = 1024      # the forward-only kernel of csrc/attn_long.hip (long_attention below)
 HEAD_DIM = 64
 LONG_CALLS = 0       # launches of the long kernel so far (tests tell by it which path ran)
+LONG_TRAIN_CALLS = 0  # forward calls of long_attention_train / long_self_attention_train so far
 
 
 class AttnBias:
@@ -311,3 +314,148 @@ def long_self_attention(qkv: torch.Tensor, num_heads: int, key_mask: Optional[to
     _launch_long(base, base + E * esz, base + 2 * E * esz, key_mask, bias, o, lse, B, num_heads, L, L, E3, E3, E3, causal,
                  HEAD_DIM ** -0.5 if scale is None else float(scale))
     return o
+
+
+# ---- the training form at these lengths (csrc/attn_long.hip with dropout, csrc/attn_long_bwd.hip): dropout by the short kernels' mask
+# rule (seed + the device step counter), and a backward without atomics whose sums have an order fixed by (Lq, Lk)
+def _long_fwd_train(q_ptr, k_ptr, v_ptr, key_mask, bias, o, lse, keep, B, H, Lq, Lk, ld_q, ld_k, ld_v, causal, scale, p, seed):
+    global LONG_TRAIN_CALLS
+    if scale == 0.0:
+        raise RuntimeError("vl-pet_amd: long_attention_train needs a nonzero scale")
+    if bias is not None and (bias.H, bias.Lq, bias.Lk) != (H, Lq, Lk):
+        raise RuntimeError(f"vl-pet_amd: attention bias [{bias.H}, {bias.Lq}, {bias.Lk}] does not match [{H}, {Lq}, {Lk}]")
+    lib = _lib.load()
+    LONG_TRAIN_CALLS += 1
+    rc = _timed("attn_long_fwd_train", B * Lq, lambda: lib.vlpet_attn_long_fwd_train(
+        q_ptr, k_ptr, v_ptr, _ptr(key_mask), bias.b.data_ptr() if bias is not None else None, o.data_ptr(), lse.data_ptr(), _ptr(keep),
+        B, H, Lq, Lk, ld_q, ld_k, ld_v, int(causal), float(scale), float(p), seed, _stream()))
+    _lib.check(rc, "vlpet_attn_long_fwd_train")
+
+
+def _long_bwd(q_ptr, k_ptr, v_ptr, o, do, lse, key_mask, bias, dq_ptr, dk_ptr, dv_ptr, B, H, Lq, Lk, ld_q, ld_k, ld_v, causal, scale, p, seed):
+    lib = _lib.load()
+    delta = torch.empty(B, H, Lq, dtype=torch.float32, device=o.device)        # the kernels' scratch: sum_d dO O per row
+    # (the kernel reads the bias along keys in both passes: the transposed table, bias.bt, is never built for it)
+    rc = _timed("attn_long_bwd", B * Lq, lambda: lib.vlpet_attn_long_bwd(
+        q_ptr, k_ptr, v_ptr, o.data_ptr(), do.data_ptr(), lse.data_ptr(), _ptr(key_mask), bias.b.data_ptr() if bias is not None else None,
+        None, dq_ptr, dk_ptr, dv_ptr, B, H, Lq, Lk, ld_q, ld_k, ld_v, causal, scale, p, seed, delta.data_ptr(), _stream()))
+    _lib.check(rc, "vlpet_attn_long_bwd")
+
+
+class _LongAttnFn(torch.autograd.Function):
+    """_AttnFn at up to MAX_LONG keys / queries (k_slot: k is read in place and dk goes into the slot's block, as there)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, key_mask, H, causal, scale, p, seed, want_mask, bias=None, k_slot=None):
+        _need_cuda(q, k, v)
+        if k_slot is not None and not _is_row_block(k):
+            k_slot = None
+        q, v = q.contiguous(), v.contiguous()
+        if k_slot is None:
+            k = k.contiguous()
+        B, Lq, E = q.shape
+        Lk = k.shape[1]
+        o = torch.empty_like(q)
+        lse = torch.empty(B, H, Lq, dtype=torch.float32, device=q.device)
+        # (the kernel writes the mask only when it drops something: without dropout every element is kept)
+        keep = torch.ones(B, H, Lq, Lk, dtype=torch.uint8, device=q.device) if want_mask else None
+        _long_fwd_train(q.data_ptr(), k.data_ptr(), v.data_ptr(), key_mask, bias, o, lse, keep, B, H, Lq, Lk, q.stride(1), k.stride(1),
+                        v.stride(1), causal, scale, p, seed)
+        ctx.save_for_backward(q, k, v, o, lse, key_mask)
+        ctx.bias = bias
+        ctx.k_slot = k_slot
+        ctx.cfg = (H, int(causal), float(scale), float(p), seed)
+        if want_mask:
+            ctx.mark_non_differentiable(keep)
+            return o, keep
+        return o
+
+    @staticmethod
+    def backward(ctx, dout, *unused):
+        q, k, v, o, lse, key_mask = ctx.saved_tensors
+        H, causal, scale, p, seed = ctx.cfg
+        B, Lq, _ = q.shape
+        Lk = k.shape[1]
+        do = dout.contiguous()
+        if do.dtype != q.dtype:
+            do = do.to(q.dtype)
+        dq, dv = torch.empty_like(q), torch.empty_like(v)
+        k_slot, ctx.k_slot = ctx.k_slot, None
+        dk = torch.empty_like(k) if k_slot is None else k_slot[0].block(k, k_slot[1])      # (the slot's block has k's strides)
+        assert dk.stride() == k.stride()
+        _long_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), o, do, lse, key_mask, ctx.bias, dq.data_ptr(), dk.data_ptr(), dv.data_ptr(),
+                  B, H, Lq, Lk, q.stride(1), k.stride(1), v.stride(1), causal, scale, p, seed)
+        ctx.bias = None
+        return dq, dk, dv, None, None, None, None, None, None, None, None, None
+
+
+class _LongAttnQkvFn(torch.autograd.Function):
+    """_AttnQkvFn at up to MAX_LONG tokens: the three column blocks of qkv [B, L, 3E] are read in place and dq | dk | dv are written into
+    ONE [B, L, 3E] gradient."""
+
+    @staticmethod
+    def forward(ctx, qkv, key_mask, H, causal, scale, p, seed, bias=None):
+        _need_cuda(qkv)
+        qkv = qkv.contiguous()
+        B, L, E3 = qkv.shape
+        E = E3 // 3
+        o = torch.empty(B, L, E, dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty(B, H, L, dtype=torch.float32, device=qkv.device)
+        base, esz = qkv.data_ptr(), qkv.element_size()
+        _long_fwd_train(base, base + E * esz, base + 2 * E * esz, key_mask, bias, o, lse, None, B, H, L, L, E3, E3, E3, causal, scale, p, seed)
+        ctx.save_for_backward(qkv, o, lse, key_mask)
+        ctx.bias = bias
+        ctx.cfg = (H, int(causal), float(scale), float(p), seed)
+        return o
+
+    @staticmethod
+    def backward(ctx, dout):
+        qkv, o, lse, key_mask = ctx.saved_tensors
+        H, causal, scale, p, seed = ctx.cfg
+        B, L, E3 = qkv.shape
+        E = E3 // 3
+        do = dout.contiguous()
+        if do.dtype != qkv.dtype:
+            do = do.to(qkv.dtype)
+        dqkv = torch.empty_like(qkv)
+        base, dbase, esz = qkv.data_ptr(), dqkv.data_ptr(), qkv.element_size()
+        _long_bwd(base, base + E * esz, base + 2 * E * esz, o, do, lse, key_mask, ctx.bias, dbase, dbase + E * esz, dbase + 2 * E * esz,
+                  B, H, L, L, E3, E3, E3, causal, scale, p, seed)
+        ctx.bias = None
+        return dqkv, None, None, None, None, None, None, None
+
+
+def long_attention_train(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, num_heads: int, key_mask: Optional[torch.Tensor] = None,
+                         causal: bool = False, p: float = 0.0, training: bool = False, scale: Optional[float] = None, seed=None,
+                         return_mask: bool = False, bias: Optional[AttnBias] = None, k_slot=None):
+    """``short_attention`` for 1 <= Lq, Lk <= 1024: q [B, Lq, H*64], k / v [B, Lk, H*64] (bf16) -> dropout(softmax(scale q k^T + bias +
+    masks), p) v, with autograd.  Arguments as in ``short_attention``.  The output and the three gradients are bitwise reproducible and
+    an item's do not depend on the rest of the batch; with ``p = 0`` (or ``training=False``) the output has the bits of
+    ``long_attention``.  No CPU fallback."""
+    if not (isinstance(q, torch.Tensor) and isinstance(k, torch.Tensor) and isinstance(v, torch.Tensor)) or not supported_long(q, k, num_heads) \
+            or v.dtype != q.dtype or not v.is_cuda or v.shape != k.shape or k.shape[0] != q.shape[0]:
+        raise RuntimeError("vl-pet_amd: long_attention_train needs bf16 CUDA tensors [B, L, H*64] with 1 <= Lq, Lk <= 1024 (k and v alike)")
+    if key_mask is not None:
+        key_mask = _key_mask_u8(key_mask, k.shape[0], k.shape[1])
+    pe = float(p) if training else 0.0
+    if seed is None:
+        seed = _draw_seed() if pe > 0.0 else 0
+    return _LongAttnFn.apply(q, k, v, key_mask, num_heads, bool(causal), HEAD_DIM ** -0.5 if scale is None else float(scale),
+                             pe, int(seed), bool(return_mask), bias, k_slot)
+
+
+def long_self_attention_train(qkv: torch.Tensor, num_heads: int, key_mask: Optional[torch.Tensor] = None, causal: bool = False,
+                              p: float = 0.0, training: bool = False, scale: Optional[float] = None, seed=None,
+                              bias: Optional[AttnBias] = None):
+    """``short_self_attention`` for L <= 1024: qkv [B, L, 3*H*64] (bf16; the output of one fused q|k|v projection) -> [B, L, H*64], the
+    column blocks read in place and the gradient written as one [B, L, 3*H*64] tensor."""
+    if not (isinstance(qkv, torch.Tensor) and qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 3
+            and qkv.shape[-1] == 3 * num_heads * HEAD_DIM and 1 <= qkv.shape[1] <= MAX_LONG):
+        raise RuntimeError("vl-pet_amd: long_self_attention_train needs a bf16 CUDA [B, L, 3*H*64] tensor with L <= 1024")
+    if key_mask is not None:
+        key_mask = _key_mask_u8(key_mask, qkv.shape[0], qkv.shape[1])
+    pe = float(p) if training else 0.0
+    if seed is None:
+        seed = _draw_seed() if pe > 0.0 else 0
+    return _LongAttnQkvFn.apply(qkv, key_mask, num_heads, bool(causal), HEAD_DIM ** -0.5 if scale is None else float(scale), pe, int(seed),
+                                bias)

@@ -8,7 +8,7 @@
 #include <stdio.h>
 #include <vector>
 
-#define VLPET_VERSION 650      // 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
+#define VLPET_VERSION 651      // 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
 #define VLPET_VERSION_R3 300      // 300: column-parallel K1 backward pass (pet_cols.hip), phases bits 3 / 4, vlpet_adapter_gate_bwd_form;
 #define VLPET_VERSION_R2 221      // 221: vlpet_sublayer_tail_reduce, vlpet_layernorm_bwd_xhat, vlpet_rmsnorm_{fwd,bwd}, vlpet_colsum;  round 2: LoRA dropout generator ABI, sliced AdamW, K3 training form; 210: strided attention entry points, streaming weight gradients; 220: low-rank visual projector
 
@@ -1377,6 +1377,49 @@ extern "C" int vlpet_attn_long_fwd(const void* q, const void* k, const void* v, 
     a.key_mask = key_mask; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.causal = causal ? 1 : 0;
     a.scale = scale; a.inv_keep = 1.0f;
     return herr(launch_attn_long_fwd(a, (hipStream_t)stream));
+}
+static int attn_long_common(int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, float scale, float p) {
+    if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || Lq > VLPET_ATTN_LONG_MAX_LEN || Lk > VLPET_ATTN_LONG_MAX_LEN) return VLPET_E_SHAPE;
+    if ((int64_t)B * H * ((Lq + 127) / 128) > 0x7fffffffLL || (int64_t)B * H * ((Lk + 127) / 128) > 0x7fffffffLL) return VLPET_E_SHAPE;
+    if (!attn_ld_ok(H, ld_q, ld_k) || !attn_ld_ok(H, ld_q, ld_v) || !(scale != 0.f)) return VLPET_E_SHAPE;
+    if (!(p >= 0.0f && p < 1.0f)) return VLPET_E_SHAPE;
+    return 0;
+}
+// the training form of vlpet_attn_long_fwd: dropout on the probabilities (the short kernels' mask rule), optional export of the mask;
+// p = 0 launches the kernel of vlpet_attn_long_fwd (the same bits)
+extern "C" int vlpet_attn_long_fwd_train(const void* q, const void* k, const void* v, const uint8_t* key_mask, const float* bias, void* o,
+                                         float* lse, uint8_t* keep_out, int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v,
+                                         int causal, float scale, float p, uint64_t seed, vlpet_stream_t stream) {
+    int rc = attn_long_common(B, H, Lq, Lk, ld_q, ld_k, ld_v, scale, p);
+    if (rc) return rc;
+    if (!q || !k || !v || !o || !lse) return VLPET_E_NULL;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || (bias && !aligned16(bias))) return VLPET_E_ALIGN;
+    AttnArgs a{};
+    a.ld_q = ld_q; a.ld_kv = ld_k; a.ld_v = ld_v; a.bias = bias;
+    a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v; a.o = (__bf16*)o; a.lse = lse;
+    a.key_mask = key_mask; a.keep_out = keep_out; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.causal = causal ? 1 : 0;
+    a.scale = scale; a.thr = attn_thr(p); a.inv_keep = a.thr ? 1.0f / (1.0f - p) : 1.0f; a.seed = seed; a.seed_ctr = g_seed_ctr.load();
+    return herr(launch_attn_long_fwd(a, (hipStream_t)stream));
+}
+// ... and its backward (attn_long_bwd.hip): the arguments of vlpet_attn_bwd_kv (bias_t is accepted and not read) plus `delta`, [B, H, Lq]
+// fp32 of scratch that the caller allocates
+extern "C" int vlpet_attn_long_bwd(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
+                                   const uint8_t* key_mask, const float* bias, const float* bias_t, void* dq, void* dk, void* dv,
+                                   int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, int causal, float scale, float p,
+                                   uint64_t seed, float* delta, vlpet_stream_t stream) {
+    (void)bias_t;
+    int rc = attn_long_common(B, H, Lq, Lk, ld_q, ld_k, ld_v, scale, p);
+    if (rc) return rc;
+    if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !delta) return VLPET_E_NULL;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(dout) || !aligned16(dq) ||
+        !aligned16(dk) || !aligned16(dv) || (bias && !aligned16(bias))) return VLPET_E_ALIGN;
+    AttnArgs a{};
+    a.ld_q = ld_q; a.ld_kv = ld_k; a.ld_v = ld_v; a.bias = bias; a.bias_t = nullptr;
+    a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v; a.o = (__bf16*)const_cast<void*>(o);
+    a.lse = const_cast<float*>(lse); a.dout = (const __bf16*)dout; a.dq = (__bf16*)dq; a.dk = (__bf16*)dk; a.dv = (__bf16*)dv;
+    a.key_mask = key_mask; a.keep_out = nullptr; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.causal = causal ? 1 : 0;
+    a.scale = scale; a.thr = attn_thr(p); a.inv_keep = a.thr ? 1.0f / (1.0f - p) : 1.0f; a.seed = seed; a.seed_ctr = g_seed_ctr.load();
+    return herr(launch_attn_long_bwd(a, delta, (hipStream_t)stream));
 }
 extern "C" int vlpet_attn_fwd_bias(const void* q, const void* k, const void* v, const uint8_t* key_mask, const float* bias, void* o,
                                    float* lse, uint8_t* keep_out, int B, int H, int Lq, int Lk, int ld_q, int ld_kv, int causal,

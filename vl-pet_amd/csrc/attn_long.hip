@@ -1,7 +1,8 @@
 // Attention forward for sequences of up to 1,024 keys and 1,024 queries (head dim 64, bf16): softmax(scale * q k^T + bias + masks) v
 // with the keys streamed through LDS in chunks and an online softmax -- the video configuration's encoder self-attention (600 text
 // tokens + 64 frames = 664) and the cross-attention against it, which csrc/attn.hip (whole sequence on chip, at most 128 keys) does
-// not cover.  No dropout, no backward: the inference / no_grad form; the log-sum-exp is written for a later backward.
+// not cover.  DROP = false is the inference / no_grad form; DROP = true is the training forward (dropout on the probabilities by the
+// short kernels' mask rule, an optional export of the mask); the log-sum-exp is what the backward (csrc/attn_long_bwd.hip) starts from.
 //
 // Structure: a workgroup is four waves and 128 consecutive queries of one (batch, head); the workgroups of a pair are neighbours in the
 // grid, so that the pair's K and V are read from HBM once and from L2 afterwards.  A wave owns a 32-query block with its Q fragments
@@ -20,6 +21,9 @@
 // forms -inf - (-inf).  A chunk with no visible key for a row: m_new = m_old, factor exp2(0) = 1 (or 0 on a still-empty row whose l and
 // O are 0), every p = 0 -- the row's state is unchanged.  The first visible chunk after masked ones: factor exp2(-inf) = 0 on zeros.
 // A row with no visible key at all ends with l = 0: zeros are stored and lse = +inf.
+//
+// Dropout (DROP): element (b, h, i, j) is kept iff hash_elem(row_key(seed, (b H + h) Lq + i) + j * golden) >= p * 2^32, csrc/attn.hip's
+// rule.  l and lse are sums over the UNDROPPED probabilities; the kept ones enter the P V product scaled by 1 / (1 - p).
 //
 // The helpers below are copies of csrc/attn.hip's (the short kernels keep their code, and their register allocation, untouched).
 #include <cstdlib>
@@ -43,6 +47,21 @@ typedef short v4s16_t __attribute__((ext_vector_type(4)));
 typedef short v8s16_t __attribute__((ext_vector_type(8)));
 
 __device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // arguments here are finite or -inf, never NaN
+
+// the dropout mask of csrc/attn.hip: row key, element hash
+__device__ __forceinline__ uint32_t hash32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
+    return x;
+}
+__device__ __forceinline__ uint32_t row_key(uint64_t seed, int64_t row) {
+    const uint32_t k = hash32((uint32_t)seed ^ hash32((uint32_t)(seed >> 32) + (uint32_t)((uint64_t)row >> 32)));
+    return hash32(k + (uint32_t)row);
+}
+__device__ __forceinline__ uint32_t hash_elem(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15;
+    return __builtin_amdgcn_alignbit(x, x, 16) * 0x846ca68bU;
+}
+__device__ __forceinline__ bool keep_elem(uint32_t rk, int j, uint32_t thr) { return hash_elem(rk + (uint32_t)j * 0x9E3779B9U) >= thr; }
 
 // A operand from a row-major LDS image in the row order of an accumulator tile's registers (attn.hip: tr_acc_order)
 __device__ __forceinline__ bf16x8 tr_acc_order(const uint8_t* img, int kb, int cb, int lane) {
@@ -131,8 +150,8 @@ __device__ __forceinline__ void chunk_store(const ChunkRegs& r, uint8_t* Ks, uin
     }
 }
 
-// BIAS: a.bias != nullptr -- scores = scale * q k^T + bias[h][i][j]
-template <bool BIAS>
+// BIAS: a.bias != nullptr -- scores = scale * q k^T + bias[h][i][j];  DROP: a.thr != 0 -- the training forward
+template <bool BIAS, bool DROP>
 __global__ __launch_bounds__(AL_NW * 64, 2) void attn_long_fwd_kernel(AttnArgs a) {
     __shared__ __attribute__((aligned(16))) uint8_t kv_img[2][2][AL_IMG];       // [buffer][K | V]
     __shared__ __attribute__((aligned(16))) uint8_t stg_all[AL_NW][AL_STG];
@@ -174,6 +193,8 @@ __global__ __launch_bounds__(AL_NW * 64, 2) void attn_long_fwd_kernel(AttnArgs a
     }
     const float sc2 = a.scale * AL_LOG2E, inv_scale = 1.0f / a.scale;
     float mrun = -INFINITY, lrun = 0.f;
+    uint32_t rkey = 0;
+    if constexpr (DROP) rkey = row_key(vlpet_eff_seed(a.seed, a.seed_ctr), ((int64_t)b * a.H + h) * a.Lq + iq);
     f32x16 ot0 = zero16(), ot1 = zero16();
     __syncthreads();
 
@@ -227,6 +248,26 @@ __global__ __launch_bounds__(AL_NW * 64, 2) void attn_long_fwd_kernel(AttnArgs a
             mrun = mnew;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { ot0[r] *= alpha; ot1[r] *= alpha; }
+            if constexpr (DROP) {
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int kt = key0 + 32 * t + 4 * hh;
+                    if (a.keep_out != nullptr) {                     // (tests: export of the mask)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int key = kt + (r & 3) + 8 * (r >> 2);
+                            if (i < a.Lq && key < a.Lk)
+                                a.keep_out[(((int64_t)b * a.H + h) * a.Lq + i) * a.Lk + key] = keep_elem(rkey, key, a.thr) ? 1 : 0;
+                        }
+                    }
+                    const uint32_t kg0 = rkey + (uint32_t)kt * 0x9E3779B9U;
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int ir = (r & 3) + 8 * (r >> 2);
+                        st[t][r] = hash_elem(kg0 + (uint32_t)ir * 0x9E3779B9U) >= a.thr ? st[t][r] * a.inv_keep : 0.f;
+                    }
+                }
+            }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
 #pragma unroll
@@ -257,7 +298,14 @@ hipError_t launch_attn_long_fwd(const AttnArgs& a, hipStream_t stream) {
     const int64_t wgs = (int64_t)a.B * a.H * nqb;
     if (wgs > 0x7fffffffLL) return hipErrorInvalidValue;
     // (the workgroups of one (batch, head) pair have consecutive indices: they run together and share the pair's K and V in L2)
-    if (a.bias != nullptr) hipLaunchKernelGGL(attn_long_fwd_kernel<true>, dim3((unsigned)wgs), dim3(AL_NW * 64), 0, stream, a);
-    else hipLaunchKernelGGL(attn_long_fwd_kernel<false>, dim3((unsigned)wgs), dim3(AL_NW * 64), 0, stream, a);
+    // (thr == 0 -- no dropout, the training entry point with p = 0 included -- is the DROP = false kernel: the same bits)
+    const dim3 grid((unsigned)wgs), block(AL_NW * 64);
+    if (a.thr != 0) {
+        if (a.bias != nullptr) hipLaunchKernelGGL((attn_long_fwd_kernel<true, true>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((attn_long_fwd_kernel<false, true>), grid, block, 0, stream, a);
+    } else {
+        if (a.bias != nullptr) hipLaunchKernelGGL((attn_long_fwd_kernel<true, false>), grid, block, 0, stream, a);
+        else hipLaunchKernelGGL((attn_long_fwd_kernel<false, false>), grid, block, 0, stream, a);
+    }
     return hipGetLastError();
 }

@@ -453,6 +453,8 @@ struct AttnArgs {
 };
 size_t attn_lds_bytes(int Lq, int Lk, int bwd);
 hipError_t launch_attn(const AttnArgs& a, bool bwd, hipStream_t stream);
-// the forward for up to 1,024 keys / queries (attn_long.hip): keys streamed through LDS with an online softmax; no dropout (thr, seed,
-// keep_out, dout, dq / dk / dv and bias_t are not read)
+// the forward for up to 1,024 keys / queries (attn_long.hip): keys streamed through LDS with an online softmax; thr == 0: no dropout (seed
+// and keep_out are not read); dout, dq / dk / dv and bias_t are never read
 hipError_t launch_attn_long_fwd(const AttnArgs& a, hipStream_t stream);
+// its backward (attn_long_bwd.hip): two launches (dQ + delta, then dK / dV); delta [B, H, Lq] fp32 is scratch of the caller; bias_t is not read
+hipError_t launch_attn_long_bwd(const AttnArgs& a, float* delta, hipStream_t stream);

@@ -186,6 +186,13 @@ FUSE_QKV = True           # A/B switch: False = separate q / k / v projections i
 def _long_applies(Lq, Lk, p, training, *tensors) -> bool:
     return (LONG_ATTENTION and not EAGER_ATTENTION and max(Lq, Lk) > A.MAX_LEN and Lq <= A.MAX_LONG and Lk <= A.MAX_LONG
             and (not training or p == 0) and not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)))
+LONG_ATTENTION_TRAIN = False   # switch (host/bart.py: the same): True = those lengths on the long TRAINING kernels wherever a call needs
+                               # dropout or a gradient
+
+
+def _long_train_applies(Lq, Lk, p, training, *tensors) -> bool:
+    return (LONG_ATTENTION_TRAIN and not EAGER_ATTENTION and max(Lq, Lk) > A.MAX_LEN and Lq <= A.MAX_LONG and Lk <= A.MAX_LONG
+            and ((training and p > 0) or (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))))
 FUSE_CROSS_KEYS = True    # A/B switch: False = every decoder block projects its own cross-attention keys (host/bart.py: the same fusion)
 
 
@@ -221,8 +228,11 @@ class AttnSpec:
         if self.rel_trainable:
             return None
         if self._fast is None:
-            # (the transposed copy is the backward's: a forward-only long-kernel pass does not build it)
-            bias = A.AttnBias(self.rel, transposed=not (LONG_ATTENTION and not torch.is_grad_enabled())) if self.rel is not None else None
+            # (the transposed copy is the short backward's: a forward-only long-kernel pass does not build it, nor does the long training
+            # form, whose backward reads the table along keys; whoever needs it after all builds it on first use)
+            lazy = (LONG_ATTENTION and not torch.is_grad_enabled()) or (
+                LONG_ATTENTION_TRAIN and self.rel is not None and max(self.rel.shape[-2:]) > A.MAX_LEN)
+            bias = A.AttnBias(self.rel, transposed=not lazy) if self.rel is not None else None
             km = None if self.keep is None else (self.keep > 0.5).to(torch.uint8).contiguous()
             self._fast = (bias, km)
         return self._fast
@@ -272,8 +282,9 @@ class T5Attention(nn.Module):
         k_slot = None
         spec = bias if isinstance(bias, AttnSpec) else None
         long_ = _long_applies(Lq, src.shape[1], self.dropout, self.training, hidden, src)
+        long_train = _long_train_applies(Lq, src.shape[1], self.dropout, self.training, hidden, src)
         if (kv is None and FUSE_QKV and spec is not None and not EAGER_ATTENTION and hidden.is_cuda and hidden.dtype == torch.bfloat16
-                and self.d_kv == A.HEAD_DIM and (Lq <= A.MAX_LEN or long_)
+                and self.d_kv == A.HEAD_DIM and (Lq <= A.MAX_LEN or long_ or long_train)
                 and not any(m.weight.requires_grad for m in (self.q, self.k, self.v))):
             fast = spec.fast()
             if fast is not None:
@@ -285,7 +296,10 @@ class T5Attention(nn.Module):
                     qkv = VF.linear_acc(hidden, None, (w, None))
                 else:
                     qkv = F.linear(hidden, w)
-                if Lq > A.MAX_LEN:
+                if Lq > A.MAX_LEN and long_train:
+                    out = A.long_self_attention_train(qkv, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0,
+                                                      bias=fast[0])
+                elif Lq > A.MAX_LEN:
                     out = A.long_self_attention(qkv, self.n_heads, fast[1], spec.causal, scale=1.0, bias=fast[0])
                 else:
                     out = A.short_self_attention(qkv, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0, bias=fast[0])
@@ -321,6 +335,13 @@ class T5Attention(nn.Module):
             fast = spec.fast()
             if fast is not None:
                 out = A.long_attention(q, k, v, self.n_heads, fast[1], spec.causal, scale=1.0, bias=fast[0])
+                return _linear(self.o, out)
+        if (spec is not None and self.d_kv == A.HEAD_DIM and v.dtype == q.dtype and A.supported_long(q, k, self.n_heads)
+                and _long_train_applies(Lq, k.shape[1], self.dropout, self.training, q, k, v)):
+            fast = spec.fast()
+            if fast is not None:
+                out = A.long_attention_train(q, k, v, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0,
+                                             bias=fast[0], k_slot=k_slot)
                 return _linear(self.o, out)
         mask = spec.dense(q.dtype) if spec is not None else (None if bias is None else bias.to(q.dtype))
         out = F.scaled_dot_product_attention(self._shape(q, B), self._shape(k.contiguous(), B), self._shape(v, B), attn_mask=mask,
@@ -508,7 +529,8 @@ class T5Decoder(nn.Module):
         if not (FUSE_RESIDUAL_GRAD and FUSE_NORM_GRAD and torch.is_grad_enabled() and enc.requires_grad):
             return False
         atts = [blk.layer[1].EncDecAttention for blk in self.block]
-        if enc.shape[1] > A.MAX_LEN or atts[0].d_kv != A.HEAD_DIM or cross_bias.fast() is None:
+        # (past the short kernels' length the long training kernels read a block in place and write dk into the shared slot)
+        if (enc.shape[1] > A.MAX_LEN and not (LONG_ATTENTION_TRAIN and enc.shape[1] <= A.MAX_LONG)) or atts[0].d_kv != A.HEAD_DIM or cross_bias.fast() is None:
             return False
         return not any(m.weight.requires_grad or m.bias is not None for a in atts for m in (a.q, a.k, a.v))
 
