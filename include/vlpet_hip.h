@@ -512,7 +512,7 @@ int vlpet_ce_loss_fwd_checked(const void* logits, const int64_t* labels, float* 
  *   outputs as they are: no head transpose);  key_mask: [B, Lk] uint8, 1 = attend, or NULL;  causal: key j visible to query
  *   i iff j <= i + (Lk - Lq);  lse: [B, H, Lq] fp32 scratch written by the forward and read by the backward;
  *   keep_out: optional [B, H, Lq, Lk] uint8 export of the dropout mask (tests), NULL otherwise.
- * Dropout: element (b, h, i, j) is kept iff a hash of (seed, element index) >= p * 2^32; the backward regenerates it.
+ * Dropout: element (b, h, i, j) is kept iff a hash of (seed, element index) >= p * 2^32 (csrc/attn_common.h); the backward regenerates it.
  * A query row with no visible key yields zeros (the library path yields NaN there). */
 #define VLPET_ATTN_MAX_LEN 128
 int vlpet_attn_fwd(const void* q, const void* k, const void* v, const uint8_t* key_mask, void* o, float* lse, uint8_t* keep_out,

@@ -12,7 +12,7 @@ Two generators:
   pet_bwd, wgrad, lora8).  Counter = index of the 8-element group of the row-major tensor, key = the 64-bit seed; element j of a
   group keeps iff 16-bit lane j of the 128-bit output (word j >> 1, half j & 1) is >= ``thr``, with ``thr`` from
   ``tail_thr`` / ``make_drop`` (csrc/api.hip): ``min(int(float32(p) * 65536 + 0.5), 65535)``; ``thr == 0`` means no dropout.
-* **the attention's element hash** (csrc/attn.hip: ``hash32``, ``row_key``, ``hash_elem``, ``keep_elem``) -- one 32-bit key
+* **the attention's element hash** (csrc/attn_common.h: ``hash32``, ``row_key``, ``hash_elem``, ``keep_elem``) -- one 32-bit key
   per (b, h, i) row, then per key j ``hash_elem(rk + j * 0x9E3779B9) >= thr`` with ``thr`` from ``attn_thr`` (csrc/api.hip):
   ``min(int(float32(p) * 2^32 + 0.5), 2^32 - 1)``; ``thr == 0`` keeps everything.
 
@@ -125,9 +125,9 @@ def packed_bits(mask: np.ndarray) -> np.ndarray:
     return out
 
 
-# ------------------------------------------------------------------------------------------------ attention (csrc/attn.hip)
+# ------------------------------------------------------------------------------------------------ attention (csrc/attn_common.h)
 def hash32(x) -> np.ndarray:
-    """csrc/attn.hip hash32: xorshift-multiply, two rounds."""
+    """csrc/attn_common.h hash32: xorshift-multiply, two rounds."""
     x = _u64(x) & M32
     x ^= x >> np.uint64(16)
     x = (x * np.uint64(0x7FEB352D)) & M32
@@ -138,7 +138,7 @@ def hash32(x) -> np.ndarray:
 
 
 def row_key(seed: int, row) -> np.ndarray:
-    """csrc/attn.hip row_key: the 32-bit key of attention row(s) ``row`` = (b * H + h) * Lq + i."""
+    """csrc/attn_common.h row_key: the 32-bit key of attention row(s) ``row`` = (b * H + h) * Lq + i."""
     row = _u64(row)
     k = hash32(np.uint64(seed & 0xFFFFFFFF) ^ hash32((np.uint64((seed >> 32) & 0xFFFFFFFF) + (row >> np.uint64(32))) & M32))
     return hash32((k + (row & M32)) & M32)
@@ -153,7 +153,7 @@ def row_key_xor(seed: int, row) -> np.ndarray:
 
 
 def hash_elem(x) -> np.ndarray:
-    """csrc/attn.hip hash_elem: the per-element finaliser over (row key + j * golden) -- one multiply-xorshift round, a rotation
+    """csrc/attn_common.h hash_elem: the per-element finaliser over (row key + j * golden) -- one multiply-xorshift round, a rotation
     by 16 (v_alignbit_b32 of x with itself), a second multiply."""
     x = hash_elem_one_round(x)
     x = ((x >> np.uint64(16)) | (x << np.uint64(16))) & M32
@@ -175,7 +175,7 @@ def elem_uniform(rk, j, elem=hash_elem) -> np.ndarray:
 
 
 def keep_elem(rk, j, thr: int, elem=hash_elem) -> np.ndarray:
-    """csrc/attn.hip keep_elem."""
+    """csrc/attn_common.h keep_elem."""
     return elem_uniform(rk, j, elem) >= np.uint64(thr)
 
 

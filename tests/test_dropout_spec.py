@@ -1,4 +1,4 @@
-"""Statistics of the two dropout generators (tests/dropout_spec.py, the numpy statement of csrc/rng.h and csrc/attn.hip), on the
+"""Statistics of the two dropout generators (tests/dropout_spec.py, the numpy statement of csrc/rng.h and csrc/attn_common.h), on the
 CPU.  The reference's ``F.dropout(p)`` keeps every element i.i.d. with probability q = 1 - p; the parity tests of the dropout
 sites evaluate the oracle with the mask the kernel exported, so only these tests can see a mask that keeps the right fraction
 but is correlated, periodic or repeated.  tests/test_gpu_dropout_masks.py pins every site to the spec bit for bit.

@@ -1328,12 +1328,6 @@ extern "C" int vlpet_sublayer_tail_bwd_out(const void* dout, const void* out_sav
     return herr(launch_tail(a, io_dtype == VLPET_F32, true, (hipStream_t)stream));
 }
 
-static int attn_common(int B, int H, int Lq, int Lk, float p) {
-    if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || Lq > VLPET_ATTN_MAX_LEN || Lk > VLPET_ATTN_MAX_LEN) return VLPET_E_SHAPE;
-    if ((int64_t)B * H > 0x7fffffffLL) return VLPET_E_SHAPE;
-    if (!(p >= 0.0f && p < 1.0f)) return VLPET_E_SHAPE;
-    return 0;
-}
 static uint32_t attn_thr(float p) {
     double t = (double)p * 4294967296.0 + 0.5;
     if (t > 4294967295.0) t = 4294967295.0;
@@ -1344,62 +1338,64 @@ static int attn_ld_ok(int H, int ld_q, int ld_kv) {
     return ld_q >= H * 64 && ld_kv >= H * 64 && ld_q % 8 == 0 && ld_kv % 8 == 0;
 }
 
+// The argument checks of the attention entry points and the kernel arguments of a call that passes them.  max_len: VLPET_ATTN_MAX_LEN
+// (attn.hip) or VLPET_ATTN_LONG_MAX_LEN (attn_long.hip, attn_long_bwd.hip); bwd: dout, dq, dk, dv are required, and with them the
+// transposed copy of a bias (attn.hip) or the [B, H, Lq] of scratch `delta` (attn_long_bwd.hip, which does not read bias_t) -- a forward
+// passes NULL for all of these.  Shape errors come first (the lengths, the grid -- a workgroup per pair and 128 queries, or 128 keys in the
+// long backward's second launch: B * H at max_len = 128 --, the row strides, scale, p), then NULL, then alignment.
+static int attn_args(AttnArgs& a, int max_len, bool bwd, const void* q, const void* k, const void* v, const uint8_t* key_mask,
+                     const float* bias, const float* bias_t, const void* o, const float* lse, uint8_t* keep_out, const void* dout,
+                     void* dq, void* dk, void* dv, const float* delta, int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v,
+                     int causal, float scale, float p, uint64_t seed) {
+    const bool lng = max_len > VLPET_ATTN_MAX_LEN;
+    if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || Lq > max_len || Lk > max_len) return VLPET_E_SHAPE;
+    if ((int64_t)B * H * ((Lq + 127) / 128) > 0x7fffffffLL || (int64_t)B * H * ((Lk + 127) / 128) > 0x7fffffffLL) return VLPET_E_SHAPE;
+    if (!attn_ld_ok(H, ld_q, ld_k) || !attn_ld_ok(H, ld_q, ld_v) || !(scale != 0.f)) return VLPET_E_SHAPE;
+    if (!(p >= 0.0f && p < 1.0f)) return VLPET_E_SHAPE;
+    if (!q || !k || !v || !o || !lse) return VLPET_E_NULL;
+    if (bwd && (!dout || !dq || !dk || !dv || (lng ? !delta : (bias != nullptr) != (bias_t != nullptr)))) return VLPET_E_NULL;
+    if (lng) bias_t = nullptr;
+    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || (bias && !aligned16(bias))) return VLPET_E_ALIGN;
+    if (bwd && (!aligned16(dout) || !aligned16(dq) || !aligned16(dk) || !aligned16(dv) || (bias_t && !aligned16(bias_t)))) return VLPET_E_ALIGN;
+    a = AttnArgs{};
+    a.ld_q = ld_q; a.ld_kv = ld_k; a.ld_v = ld_v; a.bias = bias; a.bias_t = bias_t;
+    a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v; a.o = (__bf16*)const_cast<void*>(o);
+    a.lse = const_cast<float*>(lse); a.dout = (const __bf16*)dout; a.dq = (__bf16*)dq; a.dk = (__bf16*)dk; a.dv = (__bf16*)dv;
+    a.key_mask = key_mask; a.keep_out = keep_out; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.causal = causal ? 1 : 0;
+    a.scale = scale; a.thr = attn_thr(p); a.inv_keep = a.thr ? 1.0f / (1.0f - p) : 1.0f; a.seed = seed; a.seed_ctr = g_seed_ctr.load();
+    return 0;
+}
+
 // ... with separate row strides for k / dk (ld_k) and v / dv (ld_v): k may be a column block of a wider buffer (the decoder layers' fused
 // key projection of the encoder output) while v keeps its own width
 extern "C" int vlpet_attn_fwd_kv(const void* q, const void* k, const void* v, const uint8_t* key_mask, const float* bias, void* o,
                                  float* lse, uint8_t* keep_out, int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, int causal,
                                  float scale, float p, uint64_t seed, vlpet_stream_t stream) {
-    const int ld_kv = ld_k;
-    int rc = attn_common(B, H, Lq, Lk, p);
-    if (rc) return rc;
-    if (!attn_ld_ok(H, ld_q, ld_kv) || !attn_ld_ok(H, ld_q, ld_v) || !(scale != 0.f)) return VLPET_E_SHAPE;
-    if (!q || !k || !v || !o || !lse) return VLPET_E_NULL;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || (bias && !aligned16(bias))) return VLPET_E_ALIGN;
-    AttnArgs a{};
-    a.ld_q = ld_q; a.ld_kv = ld_kv; a.ld_v = ld_v; a.bias = bias; a.bias_t = nullptr;
-    a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v; a.o = (__bf16*)o; a.lse = lse;
-    a.key_mask = key_mask; a.keep_out = keep_out; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.causal = causal ? 1 : 0;
-    a.scale = scale; a.thr = attn_thr(p); a.inv_keep = a.thr ? 1.0f / (1.0f - p) : 1.0f; a.seed = seed; a.seed_ctr = g_seed_ctr.load();
-    return herr(launch_attn(a, false, (hipStream_t)stream));
+    AttnArgs a;
+    int rc = attn_args(a, VLPET_ATTN_MAX_LEN, false, q, k, v, key_mask, bias, nullptr, o, lse, keep_out, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       B, H, Lq, Lk, ld_q, ld_k, ld_v, causal, scale, p, seed);
+    return rc ? rc : herr(launch_attn(a, false, (hipStream_t)stream));
 }
 // attention forward up to VLPET_ATTN_LONG_MAX_LEN keys / queries (attn_long.hip): no dropout, no backward; same checks as vlpet_attn_fwd_kv
 extern "C" int vlpet_attn_long_fwd(const void* q, const void* k, const void* v, const uint8_t* key_mask, const float* bias, void* o,
                                    float* lse, int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, int causal, float scale,
                                    vlpet_stream_t stream) {
-    if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || Lq > VLPET_ATTN_LONG_MAX_LEN || Lk > VLPET_ATTN_LONG_MAX_LEN) return VLPET_E_SHAPE;
-    if ((int64_t)B * H * ((Lq + 127) / 128) > 0x7fffffffLL) return VLPET_E_SHAPE;
-    if (!attn_ld_ok(H, ld_q, ld_k) || !attn_ld_ok(H, ld_q, ld_v) || !(scale != 0.f)) return VLPET_E_SHAPE;
-    if (!q || !k || !v || !o || !lse) return VLPET_E_NULL;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || (bias && !aligned16(bias))) return VLPET_E_ALIGN;
-    AttnArgs a{};
-    a.ld_q = ld_q; a.ld_kv = ld_k; a.ld_v = ld_v; a.bias = bias;
-    a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v; a.o = (__bf16*)o; a.lse = lse;
-    a.key_mask = key_mask; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.causal = causal ? 1 : 0;
-    a.scale = scale; a.inv_keep = 1.0f;
+    AttnArgs a;
+    int rc = attn_args(a, VLPET_ATTN_LONG_MAX_LEN, false, q, k, v, key_mask, bias, nullptr, o, lse, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       B, H, Lq, Lk, ld_q, ld_k, ld_v, causal, scale, 0.f, 0);
+    if (rc) return rc;
+    a.seed_ctr = nullptr;      // (p = 0: thr = 0, inv_keep = 1, and no seed to step)
     return herr(launch_attn_long_fwd(a, (hipStream_t)stream));
-}
-static int attn_long_common(int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, float scale, float p) {
-    if (B <= 0 || H <= 0 || Lq <= 0 || Lk <= 0 || Lq > VLPET_ATTN_LONG_MAX_LEN || Lk > VLPET_ATTN_LONG_MAX_LEN) return VLPET_E_SHAPE;
-    if ((int64_t)B * H * ((Lq + 127) / 128) > 0x7fffffffLL || (int64_t)B * H * ((Lk + 127) / 128) > 0x7fffffffLL) return VLPET_E_SHAPE;
-    if (!attn_ld_ok(H, ld_q, ld_k) || !attn_ld_ok(H, ld_q, ld_v) || !(scale != 0.f)) return VLPET_E_SHAPE;
-    if (!(p >= 0.0f && p < 1.0f)) return VLPET_E_SHAPE;
-    return 0;
 }
 // the training form of vlpet_attn_long_fwd: dropout on the probabilities (the short kernels' mask rule), optional export of the mask;
 // p = 0 launches the kernel of vlpet_attn_long_fwd (the same bits)
 extern "C" int vlpet_attn_long_fwd_train(const void* q, const void* k, const void* v, const uint8_t* key_mask, const float* bias, void* o,
                                          float* lse, uint8_t* keep_out, int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v,
                                          int causal, float scale, float p, uint64_t seed, vlpet_stream_t stream) {
-    int rc = attn_long_common(B, H, Lq, Lk, ld_q, ld_k, ld_v, scale, p);
-    if (rc) return rc;
-    if (!q || !k || !v || !o || !lse) return VLPET_E_NULL;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || (bias && !aligned16(bias))) return VLPET_E_ALIGN;
-    AttnArgs a{};
-    a.ld_q = ld_q; a.ld_kv = ld_k; a.ld_v = ld_v; a.bias = bias;
-    a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v; a.o = (__bf16*)o; a.lse = lse;
-    a.key_mask = key_mask; a.keep_out = keep_out; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.causal = causal ? 1 : 0;
-    a.scale = scale; a.thr = attn_thr(p); a.inv_keep = a.thr ? 1.0f / (1.0f - p) : 1.0f; a.seed = seed; a.seed_ctr = g_seed_ctr.load();
-    return herr(launch_attn_long_fwd(a, (hipStream_t)stream));
+    AttnArgs a;
+    int rc = attn_args(a, VLPET_ATTN_LONG_MAX_LEN, false, q, k, v, key_mask, bias, nullptr, o, lse, keep_out, nullptr, nullptr, nullptr, nullptr, nullptr,
+                       B, H, Lq, Lk, ld_q, ld_k, ld_v, causal, scale, p, seed);
+    return rc ? rc : herr(launch_attn_long_fwd(a, (hipStream_t)stream));
 }
 // ... and its backward (attn_long_bwd.hip): the arguments of vlpet_attn_bwd_kv (bias_t is accepted and not read) plus `delta`, [B, H, Lq]
 // fp32 of scratch that the caller allocates
@@ -1407,19 +1403,10 @@ extern "C" int vlpet_attn_long_bwd(const void* q, const void* k, const void* v, 
                                    const uint8_t* key_mask, const float* bias, const float* bias_t, void* dq, void* dk, void* dv,
                                    int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, int causal, float scale, float p,
                                    uint64_t seed, float* delta, vlpet_stream_t stream) {
-    (void)bias_t;
-    int rc = attn_long_common(B, H, Lq, Lk, ld_q, ld_k, ld_v, scale, p);
-    if (rc) return rc;
-    if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || !delta) return VLPET_E_NULL;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(dout) || !aligned16(dq) ||
-        !aligned16(dk) || !aligned16(dv) || (bias && !aligned16(bias))) return VLPET_E_ALIGN;
-    AttnArgs a{};
-    a.ld_q = ld_q; a.ld_kv = ld_k; a.ld_v = ld_v; a.bias = bias; a.bias_t = nullptr;
-    a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v; a.o = (__bf16*)const_cast<void*>(o);
-    a.lse = const_cast<float*>(lse); a.dout = (const __bf16*)dout; a.dq = (__bf16*)dq; a.dk = (__bf16*)dk; a.dv = (__bf16*)dv;
-    a.key_mask = key_mask; a.keep_out = nullptr; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.causal = causal ? 1 : 0;
-    a.scale = scale; a.thr = attn_thr(p); a.inv_keep = a.thr ? 1.0f / (1.0f - p) : 1.0f; a.seed = seed; a.seed_ctr = g_seed_ctr.load();
-    return herr(launch_attn_long_bwd(a, delta, (hipStream_t)stream));
+    AttnArgs a;
+    int rc = attn_args(a, VLPET_ATTN_LONG_MAX_LEN, true, q, k, v, key_mask, bias, bias_t, o, lse, nullptr, dout, dq, dk, dv, delta,
+                       B, H, Lq, Lk, ld_q, ld_k, ld_v, causal, scale, p, seed);
+    return rc ? rc : herr(launch_attn_long_bwd(a, delta, (hipStream_t)stream));
 }
 extern "C" int vlpet_attn_fwd_bias(const void* q, const void* k, const void* v, const uint8_t* key_mask, const float* bias, void* o,
                                    float* lse, uint8_t* keep_out, int B, int H, int Lq, int Lk, int ld_q, int ld_kv, int causal,
@@ -1443,20 +1430,10 @@ extern "C" int vlpet_attn_bwd_kv(const void* q, const void* k, const void* v, co
                                  const uint8_t* key_mask, const float* bias, const float* bias_t, void* dq, void* dk, void* dv,
                                  int B, int H, int Lq, int Lk, int ld_q, int ld_k, int ld_v, int causal, float scale, float p, uint64_t seed,
                                  vlpet_stream_t stream) {
-    const int ld_kv = ld_k;
-    int rc = attn_common(B, H, Lq, Lk, p);
-    if (rc) return rc;
-    if (!attn_ld_ok(H, ld_q, ld_kv) || !attn_ld_ok(H, ld_q, ld_v) || !(scale != 0.f)) return VLPET_E_SHAPE;
-    if (!q || !k || !v || !o || !dout || !lse || !dq || !dk || !dv || ((bias != nullptr) != (bias_t != nullptr))) return VLPET_E_NULL;
-    if (!aligned16(q) || !aligned16(k) || !aligned16(v) || !aligned16(o) || !aligned16(dout) || !aligned16(dq) ||
-        !aligned16(dk) || !aligned16(dv) || (bias && (!aligned16(bias) || !aligned16(bias_t)))) return VLPET_E_ALIGN;
-    AttnArgs a{};
-    a.ld_q = ld_q; a.ld_kv = ld_kv; a.ld_v = ld_v; a.bias = bias; a.bias_t = bias_t;
-    a.q = (const __bf16*)q; a.k = (const __bf16*)k; a.v = (const __bf16*)v; a.o = (__bf16*)const_cast<void*>(o);
-    a.lse = const_cast<float*>(lse); a.dout = (const __bf16*)dout; a.dq = (__bf16*)dq; a.dk = (__bf16*)dk; a.dv = (__bf16*)dv;
-    a.key_mask = key_mask; a.keep_out = nullptr; a.B = B; a.H = H; a.Lq = Lq; a.Lk = Lk; a.causal = causal ? 1 : 0;
-    a.scale = scale; a.thr = attn_thr(p); a.inv_keep = a.thr ? 1.0f / (1.0f - p) : 1.0f; a.seed = seed; a.seed_ctr = g_seed_ctr.load();
-    return herr(launch_attn(a, true, (hipStream_t)stream));
+    AttnArgs a;
+    int rc = attn_args(a, VLPET_ATTN_MAX_LEN, true, q, k, v, key_mask, bias, bias_t, o, lse, nullptr, dout, dq, dk, dv, nullptr,
+                       B, H, Lq, Lk, ld_q, ld_k, ld_v, causal, scale, p, seed);
+    return rc ? rc : herr(launch_attn(a, true, (hipStream_t)stream));
 }
 extern "C" int vlpet_attn_bwd_bias(const void* q, const void* k, const void* v, const void* o, const void* dout, const float* lse,
                                    const uint8_t* key_mask, const float* bias, const float* bias_t, void* dq, void* dk, void* dv,

@@ -22,139 +22,27 @@
 // O are 0), every p = 0 -- the row's state is unchanged.  The first visible chunk after masked ones: factor exp2(-inf) = 0 on zeros.
 // A row with no visible key at all ends with l = 0: zeros are stored and lse = +inf.
 //
-// Dropout (DROP): element (b, h, i, j) is kept iff hash_elem(row_key(seed, (b H + h) Lq + i) + j * golden) >= p * 2^32, csrc/attn.hip's
-// rule.  l and lse are sums over the UNDROPPED probabilities; the kept ones enter the P V product scaled by 1 / (1 - p).
+// Dropout (DROP): element (b, h, i, j) is kept iff hash_elem(row_key(seed, (b H + h) Lq + i) + j * golden) >= p * 2^32, the one
+// rule of csrc/attn_common.h.  l and lse are sums over the UNDROPPED probabilities; the kept ones enter the P V product scaled by 1 / (1 - p).
 //
-// The helpers below are copies of csrc/attn.hip's (the short kernels keep their code, and their register allocation, untouched).
+// The mask rule, the LDS geometry, the operand readers, the staged row store and the chunk ring's load / store pair are csrc/attn_common.h's,
+// shared with csrc/attn.hip and csrc/attn_long_bwd.hip.
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
+#include "attn_common.h"
 
-#define AL_LD 72                       // bf16 elements per LDS row: 64 + 8 of padding (144 B)
-#define AL_ROW (AL_LD * 2)             // bytes
 #define AL_NW 4                        // waves per workgroup = 32-query blocks per workgroup
 #define AL_QWG (32 * AL_NW)            // queries per workgroup
-#define AL_CK 64                       // keys per chunk
-#define AL_IMG (AL_CK * AL_ROW)        // one K or V image of a chunk
-#define AL_SROW 144
-#define AL_STG (16 * AL_SROW)
 #define AL_MAXK 1024
-#define AL_LOG2E 1.4426950408889634f
 
 namespace {
-
-typedef short v4s16_t __attribute__((ext_vector_type(4)));
-typedef short v8s16_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // arguments here are finite or -inf, never NaN
-
-// the dropout mask of csrc/attn.hip: row key, element hash
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ uint32_t row_key(uint64_t seed, int64_t row) {
-    const uint32_t k = hash32((uint32_t)seed ^ hash32((uint32_t)(seed >> 32) + (uint32_t)((uint64_t)row >> 32)));
-    return hash32(k + (uint32_t)row);
-}
-__device__ __forceinline__ uint32_t hash_elem(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15;
-    return __builtin_amdgcn_alignbit(x, x, 16) * 0x846ca68bU;
-}
-__device__ __forceinline__ bool keep_elem(uint32_t rk, int j, uint32_t thr) { return hash_elem(rk + (uint32_t)j * 0x9E3779B9U) >= thr; }
-
-// A operand from a row-major LDS image in the row order of an accumulator tile's registers (attn.hip: tr_acc_order)
-__device__ __forceinline__ bf16x8 tr_acc_order(const uint8_t* img, int kb, int cb, int lane) {
-    const int g = lane >> 4, sl = lane & 15;
-    const uint8_t* p = img + (size_t)(kb + 4 * (g >> 1) + (sl >> 2)) * AL_ROW + (cb + 16 * (g & 1) + 4 * (sl & 3)) * 2;
-    typedef __attribute__((address_space(3))) v4s16_t lds_v4;
-    const v4s16_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(p));
-    const v4s16_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(p + 8 * AL_ROW));
-    const v8s16_t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
-}
-__device__ __forceinline__ bf16x8 nat_frag(const uint8_t* img, int row, int ks, int hh) {
-    return *reinterpret_cast<const bf16x8*>(img + (size_t)row * AL_ROW + (16 * ks + 8 * hh) * 2);
-}
-__device__ __forceinline__ bf16x8 acc_frag(const f32x16& t, int u) {
-    bf16x8 f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (__bf16)t[8 * u + j];
-    return f;
-}
-// accumulator pair D[d][row] -> global rows through the wave's staging tile, eight whole 128-byte rows per store (attn.hip: store_rows_T)
-__device__ __forceinline__ void store_rows_T(uint8_t* stg, const f32x16& t0, const f32x16& t1, __bf16* dst, int64_t rs,
-                                             int row0, int n_rows, int lane) {
-    const int m = lane & 31, hh = lane >> 5;
-    typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        if ((m >> 4) == half) {
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                const f32x16& t = dt ? t1 : t0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    bf16x4_t w;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) w[e] = (__bf16)t[4 * q + e];
-                    *reinterpret_cast<bf16x4_t*>(stg + (size_t)(m & 15) * AL_SROW + (32 * dt + 8 * q + 4 * hh) * 2) = w;
-                }
-            }
-        }
-        asm volatile("" ::: "memory");         // (same-wave LDS accesses are ordered in hardware; this orders them for the compiler)
-        u32x4 v[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int idx = lane + 64 * c, row = idx >> 3, pc = idx & 7;
-            v[c] = *reinterpret_cast<const u32x4*>(stg + (size_t)row * AL_SROW + pc * 16);
-        }
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int idx = lane + 64 * c, row = 16 * half + (idx >> 3), pc = idx & 7;
-            if (row0 + row < n_rows) *reinterpret_cast<u32x4*>(dst + (int64_t)(row0 + row) * rs + pc * 8) = v[c];
-        }
-    }
-}
-__device__ __forceinline__ f32x16 bias_tile(const float* brow, float inv_scale) {
-    f32x16 t;
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(brow + 8 * q4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) t[4 * q4 + e] = bv[e] * inv_scale;
-    }
-    return t;
-}
-
-// one chunk of K and V rows on its way from global memory to an LDS buffer: 64 rows x 8 pieces of 16 bytes per image, two per thread
-struct ChunkRegs { u32x4 k[2], v[2]; };
-__device__ __forceinline__ void chunk_load(ChunkRegs& r, const __bf16* kb, const __bf16* vb, int64_t rk, int64_t rv, int key0, int Lk, int tid) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int idx = tid + 256 * c, row = key0 + (idx >> 3), pc = idx & 7;
-        const int rr = row < Lk ? row : Lk - 1;                  // (rows past Lk: a valid address; zeros are stored below)
-        r.k[c] = *reinterpret_cast<const u32x4*>(kb + (int64_t)rr * rk + pc * 8);
-        r.v[c] = *reinterpret_cast<const u32x4*>(vb + (int64_t)rr * rv + pc * 8);
-    }
-}
-__device__ __forceinline__ void chunk_store(const ChunkRegs& r, uint8_t* Ks, uint8_t* Vs, int key0, int Lk, int tid) {
-    const u32x4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int idx = tid + 256 * c, row = idx >> 3, pc = idx & 7;
-        const bool live = key0 + row < Lk;
-        *reinterpret_cast<u32x4*>(Ks + (size_t)row * AL_ROW + pc * 16) = live ? r.k[c] : z;
-        *reinterpret_cast<u32x4*>(Vs + (size_t)row * AL_ROW + pc * 16) = live ? r.v[c] : z;
-    }
-}
 
 // BIAS: a.bias != nullptr -- scores = scale * q k^T + bias[h][i][j];  DROP: a.thr != 0 -- the training forward
 template <bool BIAS, bool DROP>
 __global__ __launch_bounds__(AL_NW * 64, 2) void attn_long_fwd_kernel(AttnArgs a) {
-    __shared__ __attribute__((aligned(16))) uint8_t kv_img[2][2][AL_IMG];       // [buffer][K | V]
-    __shared__ __attribute__((aligned(16))) uint8_t stg_all[AL_NW][AL_STG];
+    __shared__ __attribute__((aligned(16))) uint8_t kv_img[2][2][AT_IMG];       // [buffer][K | V]
+    __shared__ __attribute__((aligned(16))) uint8_t stg_all[AL_NW][AT_STG];
     __shared__ __attribute__((aligned(16))) float kval[AL_MAXK];                // per key: 0 / -inf (the key mask and the keys past Lk)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int nqb = (a.Lq + AL_QWG - 1) / AL_QWG;
@@ -175,9 +63,9 @@ __global__ __launch_bounds__(AL_NW * 64, 2) void attn_long_fwd_kernel(AttnArgs a
     const int qlast = (q0 + AL_QWG < a.Lq ? q0 + AL_QWG : a.Lq) - 1;
     int klast = a.Lk - 1;
     if (a.causal && qlast + coff < klast) klast = qlast + coff;
-    const int NC = klast < 0 ? 0 : klast / AL_CK + 1;
+    const int NC = klast < 0 ? 0 : klast / AT_CK + 1;
 
-    for (int j = tid; j < NC * AL_CK; j += AL_NW * 64) kval[j] = (j < a.Lk && (km == nullptr || km[j] != 0)) ? 0.f : -INFINITY;
+    for (int j = tid; j < NC * AT_CK; j += AL_NW * 64) kval[j] = (j < a.Lk && (km == nullptr || km[j] != 0)) ? 0.f : -INFINITY;
     ChunkRegs cr;
     if (NC > 0) {
         chunk_load(cr, kb_, vb_, rk, rv, 0, a.Lk, tid);
@@ -191,7 +79,7 @@ __global__ __launch_bounds__(AL_NW * 64, 2) void attn_long_fwd_kernel(AttnArgs a
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) qf[ks] = *reinterpret_cast<const bf16x8*>(qb_ + (int64_t)iq * rq + 16 * ks + 8 * hh);
     }
-    const float sc2 = a.scale * AL_LOG2E, inv_scale = 1.0f / a.scale;
+    const float sc2 = a.scale * AT_LOG2E, inv_scale = 1.0f / a.scale;
     float mrun = -INFINITY, lrun = 0.f;
     uint32_t rkey = 0;
     if constexpr (DROP) rkey = row_key(vlpet_eff_seed(a.seed, a.seed_ctr), ((int64_t)b * a.H + h) * a.Lq + iq);
@@ -199,9 +87,9 @@ __global__ __launch_bounds__(AL_NW * 64, 2) void attn_long_fwd_kernel(AttnArgs a
     __syncthreads();
 
     for (int c = 0; c < NC; ++c) {
-        const int key0 = AL_CK * c;
+        const int key0 = AT_CK * c;
         const bool more = c + 1 < NC;
-        if (more) chunk_load(cr, kb_, vb_, rk, rv, key0 + AL_CK, a.Lk, tid);
+        if (more) chunk_load(cr, kb_, vb_, rk, rv, key0 + AT_CK, a.Lk, tid);
         const uint8_t* Ks = kv_img[c & 1][0];
         const uint8_t* Vs = kv_img[c & 1][1];
         if (has_q) {
@@ -260,11 +148,11 @@ __global__ __launch_bounds__(AL_NW * 64, 2) void attn_long_fwd_kernel(AttnArgs a
                                 a.keep_out[(((int64_t)b * a.H + h) * a.Lq + i) * a.Lk + key] = keep_elem(rkey, key, a.thr) ? 1 : 0;
                         }
                     }
-                    const uint32_t kg0 = rkey + (uint32_t)kt * 0x9E3779B9U;
+                    const uint32_t kg0 = rkey + (uint32_t)kt * AT_GOLD;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         const int ir = (r & 3) + 8 * (r >> 2);
-                        st[t][r] = hash_elem(kg0 + (uint32_t)ir * 0x9E3779B9U) >= a.thr ? st[t][r] * a.inv_keep : 0.f;
+                        st[t][r] = hash_elem(kg0 + (uint32_t)ir * AT_GOLD) >= a.thr ? st[t][r] * a.inv_keep : 0.f;
                     }
                 }
             }
@@ -279,7 +167,7 @@ __global__ __launch_bounds__(AL_NW * 64, 2) void attn_long_fwd_kernel(AttnArgs a
             }
         }
         // the next chunk goes into the buffer whose readers all passed the barrier that ended the previous trip
-        if (more) chunk_store(cr, kv_img[(c + 1) & 1][0], kv_img[(c + 1) & 1][1], key0 + AL_CK, a.Lk, tid);
+        if (more) chunk_store(cr, kv_img[(c + 1) & 1][0], kv_img[(c + 1) & 1][1], key0 + AT_CK, a.Lk, tid);
         __syncthreads();
     }
     if (!has_q) return;

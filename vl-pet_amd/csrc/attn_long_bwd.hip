@@ -1,7 +1,7 @@
 // Attention backward for sequences of up to 1,024 keys and 1,024 queries (head dim 64, bf16): the training form of csrc/attn_long.hip.
 // Everything is recomputed from q, k, v, the forward's output and its log-sum-exp (log2 units):
 //   P = exp2(sc2 s + bias + masks - lse),  dPd = dO V^T,  dP = keep dPd / (1 - p),  delta_i = sum_d dO_id O_id,  dS = P (dP - delta),
-//   dQ = scale dS K,  dK = scale dS^T Q,  dV = (P keep / (1 - p))^T dO;   keep is regenerated from the hash of csrc/attn.hip, never stored.
+//   dQ = scale dS K,  dK = scale dS^T Q,  dV = (P keep / (1 - p))^T dO;   keep is regenerated from the hash of csrc/attn_common.h, never stored.
 //
 // Two launches, each a mirror of the forward, with the arithmetic of the short backward's two work units (attn.hip: bwd_q_unit, bwd_k_unit):
 //   attn_long_dq_kernel   a workgroup = four waves = 128 consecutive queries of one (batch, head); a wave keeps the Q and dO fragments of its
@@ -30,138 +30,26 @@
 // P = exp2(-inf) = 0 and dS = 0 * (finite) = 0; a row with no visible key has P = 0 on every key, delta = 0 (its forward output is zero),
 // a zero dQ row and no contribution to dK / dV; a fully masked item gets exact zeros in all three gradients.
 //
-// The helpers below are copies of csrc/attn.hip's and csrc/attn_long.hip's (those kernels keep their code, and their register allocation).
+// The mask rule, the LDS geometry, the operand readers, the staged row store and the chunk ring's load / store pair are csrc/attn_common.h's,
+// shared with csrc/attn.hip and csrc/attn_long.hip.
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
 #include "rng.h"
+#include "attn_common.h"
 
-#define AB_LD 72                       // bf16 elements per LDS row: 64 + 8 of padding (144 B)
-#define AB_ROW (AB_LD * 2)             // bytes
 #define AB_NW 4                        // waves per workgroup = 32-row blocks per workgroup
 #define AB_WG (32 * AB_NW)             // queries (dQ pass) / keys (dK dV pass) per workgroup
-#define AB_CK 64                       // rows per streamed chunk
-#define AB_IMG (AB_CK * AB_ROW)        // one image of a chunk
-#define AB_SROW 144
-#define AB_STG (16 * AB_SROW)
 #define AB_MAXL 1024
-#define AB_LOG2E 1.4426950408889634f
-#define AB_GOLD 0x9E3779B9U
 
 namespace {
-
-typedef short v4s16_t __attribute__((ext_vector_type(4)));
-typedef short v8s16_t __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ float fast_exp2(float x) { return __builtin_amdgcn_exp2f(x); }   // arguments here are finite or -inf, never NaN
-
-// the dropout mask of csrc/attn.hip: row key, element hash
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-    return x;
-}
-__device__ __forceinline__ uint32_t row_key(uint64_t seed, int64_t row) {
-    const uint32_t k = hash32((uint32_t)seed ^ hash32((uint32_t)(seed >> 32) + (uint32_t)((uint64_t)row >> 32)));
-    return hash32(k + (uint32_t)row);
-}
-__device__ __forceinline__ uint32_t hash_elem(uint32_t x) {
-    x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15;
-    return __builtin_amdgcn_alignbit(x, x, 16) * 0x846ca68bU;
-}
-
-__device__ __forceinline__ bf16x8 tr_acc_order(const uint8_t* img, int kb, int cb, int lane) {
-    const int g = lane >> 4, sl = lane & 15;
-    const uint8_t* p = img + (size_t)(kb + 4 * (g >> 1) + (sl >> 2)) * AB_ROW + (cb + 16 * (g & 1) + 4 * (sl & 3)) * 2;
-    typedef __attribute__((address_space(3))) v4s16_t lds_v4;
-    const v4s16_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(p));
-    const v4s16_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(p + 8 * AB_ROW));
-    const v8s16_t r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
-}
-__device__ __forceinline__ bf16x8 nat_frag(const uint8_t* img, int row, int ks, int hh) {
-    return *reinterpret_cast<const bf16x8*>(img + (size_t)row * AB_ROW + (16 * ks + 8 * hh) * 2);
-}
-__device__ __forceinline__ bf16x8 acc_frag(const f32x16& t, int u) {
-    bf16x8 f;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) f[j] = (__bf16)t[8 * u + j];
-    return f;
-}
-// accumulator pair D[d][row] -> global rows through the wave's staging tile, eight whole 128-byte rows per store (attn.hip: store_rows_T)
-__device__ __forceinline__ void store_rows_T(uint8_t* stg, const f32x16& t0, const f32x16& t1, __bf16* dst, int64_t rs,
-                                             int row0, int n_rows, int lane) {
-    const int m = lane & 31, hh = lane >> 5;
-    typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
-#pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        if ((m >> 4) == half) {
-#pragma unroll
-            for (int dt = 0; dt < 2; ++dt) {
-                const f32x16& t = dt ? t1 : t0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    bf16x4_t w;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) w[e] = (__bf16)t[4 * q + e];
-                    *reinterpret_cast<bf16x4_t*>(stg + (size_t)(m & 15) * AB_SROW + (32 * dt + 8 * q + 4 * hh) * 2) = w;
-                }
-            }
-        }
-        asm volatile("" ::: "memory");         // (same-wave LDS accesses are ordered in hardware; this orders them for the compiler)
-        u32x4 v[2];
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int idx = lane + 64 * c, row = idx >> 3, pc = idx & 7;
-            v[c] = *reinterpret_cast<const u32x4*>(stg + (size_t)row * AB_SROW + pc * 16);
-        }
-        asm volatile("" ::: "memory");
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            const int idx = lane + 64 * c, row = 16 * half + (idx >> 3), pc = idx & 7;
-            if (row0 + row < n_rows) *reinterpret_cast<u32x4*>(dst + (int64_t)(row0 + row) * rs + pc * 8) = v[c];
-        }
-    }
-}
-__device__ __forceinline__ f32x16 bias_tile(const float* brow, float inv_scale) {
-    f32x16 t;
-#pragma unroll
-    for (int q4 = 0; q4 < 4; ++q4) {
-        const f32x4 bv = *reinterpret_cast<const f32x4*>(brow + 8 * q4);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) t[4 * q4 + e] = bv[e] * inv_scale;
-    }
-    return t;
-}
-
-// one chunk of two row streams (K and V, or Q and dO) on its way from global memory to an LDS buffer: 64 rows x 8 pieces of 16 bytes per
-// image, two per thread (attn_long.hip: chunk_load / chunk_store)
-struct ChunkRegs { u32x4 x[2], y[2]; };
-__device__ __forceinline__ void chunk_load(ChunkRegs& r, const __bf16* xb, const __bf16* yb, int64_t rx, int64_t ry, int row0, int L, int tid) {
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int idx = tid + 256 * c, row = row0 + (idx >> 3), pc = idx & 7;
-        const int rr = row < L ? row : L - 1;                    // (rows past L: a valid address; zeros are stored below)
-        r.x[c] = *reinterpret_cast<const u32x4*>(xb + (int64_t)rr * rx + pc * 8);
-        r.y[c] = *reinterpret_cast<const u32x4*>(yb + (int64_t)rr * ry + pc * 8);
-    }
-}
-__device__ __forceinline__ void chunk_store(const ChunkRegs& r, uint8_t* Xs, uint8_t* Ys, int row0, int L, int tid) {
-    const u32x4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-    for (int c = 0; c < 2; ++c) {
-        const int idx = tid + 256 * c, row = idx >> 3, pc = idx & 7;
-        const bool live = row0 + row < L;
-        *reinterpret_cast<u32x4*>(Xs + (size_t)row * AB_ROW + pc * 16) = live ? r.x[c] : z;
-        *reinterpret_cast<u32x4*>(Ys + (size_t)row * AB_ROW + pc * 16) = live ? r.y[c] : z;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------------- dQ (and delta)
 // BIAS: a.bias != nullptr -- scores = scale * q k^T + bias[h][i][j]
 template <bool BIAS>
 __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dq_kernel(AttnArgs a, float* delta) {
-    __shared__ __attribute__((aligned(16))) uint8_t kv_img[2][2][AB_IMG];       // [buffer][K | V]
-    __shared__ __attribute__((aligned(16))) uint8_t stg_all[AB_NW][AB_STG];
+    __shared__ __attribute__((aligned(16))) uint8_t kv_img[2][2][AT_IMG];       // [buffer][K | V]
+    __shared__ __attribute__((aligned(16))) uint8_t stg_all[AB_NW][AT_STG];
     __shared__ __attribute__((aligned(16))) float kval[AB_MAXL];                // per key: 0 / -inf (the key mask and the keys past Lk)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint64_t seed = a.thr ? vlpet_eff_seed(a.seed, a.seed_ctr) : 0;
@@ -185,9 +73,9 @@ __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dq_kernel(AttnArgs a,
     const int qlast = (q0 + AB_WG < a.Lq ? q0 + AB_WG : a.Lq) - 1;
     int klast = a.Lk - 1;
     if (a.causal && qlast + coff < klast) klast = qlast + coff;
-    const int NC = klast < 0 ? 0 : klast / AB_CK + 1;
+    const int NC = klast < 0 ? 0 : klast / AT_CK + 1;
 
-    for (int j = tid; j < NC * AB_CK; j += AB_NW * 64) kval[j] = (j < a.Lk && (km == nullptr || km[j] != 0)) ? 0.f : -INFINITY;
+    for (int j = tid; j < NC * AT_CK; j += AB_NW * 64) kval[j] = (j < a.Lk && (km == nullptr || km[j] != 0)) ? 0.f : -INFINITY;
     ChunkRegs cr;
     if (NC > 0) {
         chunk_load(cr, kb_, vb_, rk, rv, 0, a.Lk, tid);
@@ -217,16 +105,16 @@ __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dq_kernel(AttnArgs a,
         if (i < a.Lq) l2 = a.lse[row];
         rkey = row_key(seed, row);
     }
-    const float sc2 = a.scale * AB_LOG2E, inv_scale = 1.0f / a.scale;
+    const float sc2 = a.scale * AT_LOG2E, inv_scale = 1.0f / a.scale;
     const float inv_keep = a.thr ? a.inv_keep : 1.0f;
     f32x16 dq0 = zero16(), dq1 = zero16(), pk0 = zero16(), pk1 = zero16();
     float rsum = 0.f;                                                // sum over this lane's keys of P (dP - delta~)
     __syncthreads();
 
     for (int c = 0; c < NC; ++c) {
-        const int key0 = AB_CK * c;
+        const int key0 = AT_CK * c;
         const bool more = c + 1 < NC;
-        if (more) chunk_load(cr, kb_, vb_, rk, rv, key0 + AB_CK, a.Lk, tid);
+        if (more) chunk_load(cr, kb_, vb_, rk, rv, key0 + AT_CK, a.Lk, tid);
         const uint8_t* Ks = kv_img[c & 1][0];
         const uint8_t* Vs = kv_img[c & 1][1];
         if (has_q) {
@@ -242,7 +130,7 @@ __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dq_kernel(AttnArgs a,
                     s = mfma32(nat_frag(Ks, 32 * t + m, ks, hh), qf[ks], s);             // D[key][query]
                     dp = mfma32(nat_frag(Vs, 32 * t + m, ks, hh), df[ks], dp);
                 }
-                const uint32_t kg0 = rkey + (uint32_t)(key0 + 32 * t + 4 * hh) * AB_GOLD;
+                const uint32_t kg0 = rkey + (uint32_t)(key0 + 32 * t + 4 * hh) * AT_GOLD;
                 const int ict = ic - 32 * t;
 #pragma unroll
                 for (int q4 = 0; q4 < 4; ++q4) {
@@ -253,7 +141,7 @@ __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dq_kernel(AttnArgs a,
                         float x = fmaf(s[r], sc2, kv[e] - l2);
                         x = ir > ict ? -INFINITY : x;
                         const float p = fast_exp2(x);
-                        const bool kp = hash_elem(kg0 + (uint32_t)ir * AB_GOLD) >= a.thr;
+                        const bool kp = hash_elem(kg0 + (uint32_t)ir * AT_GOLD) >= a.thr;
                         const float g = kp ? dp[r] * inv_keep : 0.f;
                         const float ds = p * (g - dl);
                         rsum += ds;
@@ -273,7 +161,7 @@ __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dq_kernel(AttnArgs a,
             }
         }
         // the next chunk goes into the buffer whose readers all passed the barrier that ended the previous trip
-        if (more) chunk_store(cr, kv_img[(c + 1) & 1][0], kv_img[(c + 1) & 1][1], key0 + AB_CK, a.Lk, tid);
+        if (more) chunk_store(cr, kv_img[(c + 1) & 1][0], kv_img[(c + 1) & 1][1], key0 + AT_CK, a.Lk, tid);
         __syncthreads();
     }
     if (!has_q) return;
@@ -288,8 +176,8 @@ __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dq_kernel(AttnArgs a,
 // ---------------------------------------------------------------------------------------------------------------- dK, dV
 template <bool BIAS>
 __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dkv_kernel(AttnArgs a, const float* delta) {
-    __shared__ __attribute__((aligned(16))) uint8_t qd_img[2][2][AB_IMG];       // [buffer][Q | dO]
-    __shared__ __attribute__((aligned(16))) uint8_t stg_all[AB_NW][AB_STG];
+    __shared__ __attribute__((aligned(16))) uint8_t qd_img[2][2][AT_IMG];       // [buffer][Q | dO]
+    __shared__ __attribute__((aligned(16))) uint8_t stg_all[AB_NW][AT_STG];
     __shared__ __attribute__((aligned(16))) float rowt[3][AB_MAXL];             // per query: lse (+inf past Lq) | delta | dropout row key
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const uint64_t seed = a.thr ? vlpet_eff_seed(a.seed, a.seed_ctr) : 0;
@@ -310,13 +198,13 @@ __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dkv_kernel(AttnArgs a
 
     // query chunks this workgroup walks: all of them, or under the causal rule those from the first query that sees its first key
     const int k0 = AB_WG * kblk, k0w = k0 + 32 * wave;
-    const int NC = (a.Lq + AB_CK - 1) / AB_CK;
+    const int NC = (a.Lq + AT_CK - 1) / AT_CK;
     int c0 = 0;
-    if (a.causal && k0 - coff > 0) c0 = (k0 - coff) / AB_CK;
+    if (a.causal && k0 - coff > 0) c0 = (k0 - coff) / AT_CK;
     if (c0 > NC) c0 = NC;
 
     const int64_t row0 = ((int64_t)b * a.H + h) * a.Lq;
-    for (int j = AB_CK * c0 + tid; j < NC * AB_CK; j += AB_NW * 64) {
+    for (int j = AT_CK * c0 + tid; j < NC * AT_CK; j += AB_NW * 64) {
         const bool live = j < a.Lq;
         const int jj = live ? j : a.Lq - 1;
         rowt[0][j] = live ? a.lse[row0 + jj] : INFINITY;
@@ -325,8 +213,8 @@ __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dkv_kernel(AttnArgs a
     }
     ChunkRegs cr;
     if (c0 < NC) {
-        chunk_load(cr, qb_, db_, rq, rs, AB_CK * c0, a.Lq, tid);
-        chunk_store(cr, qd_img[c0 & 1][0], qd_img[c0 & 1][1], AB_CK * c0, a.Lq, tid);
+        chunk_load(cr, qb_, db_, rq, rs, AT_CK * c0, a.Lq, tid);
+        chunk_store(cr, qd_img[c0 & 1][0], qd_img[c0 & 1][1], AT_CK * c0, a.Lq, tid);
     }
     const bool has_k = k0w < a.Lk;                                   // (wave-uniform; a wave without a key block only stages)
     const int key = k0w + m;
@@ -341,17 +229,17 @@ __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dkv_kernel(AttnArgs a
         }
         if (key < a.Lk && (km == nullptr || km[key] != 0)) kb = 0.f;
     }
-    const float sc2 = a.scale * AB_LOG2E, inv_scale = 1.0f / a.scale;
+    const float sc2 = a.scale * AT_LOG2E, inv_scale = 1.0f / a.scale;
     const float inv_keep = a.thr ? a.inv_keep : 1.0f;
-    const uint32_t kg = (uint32_t)key * AB_GOLD;
+    const uint32_t kg = (uint32_t)key * AT_GOLD;
     const int kc = key - coff - 4 * hh;                              // masked iff key > i + coff with i = q0 + 32 t + ir + 4 hh
     f32x16 dv0 = zero16(), dv1 = zero16(), dk0 = zero16(), dk1 = zero16();
     __syncthreads();
 
     for (int c = c0; c < NC; ++c) {
-        const int q0 = AB_CK * c;
+        const int q0 = AT_CK * c;
         const bool more = c + 1 < NC;
-        if (more) chunk_load(cr, qb_, db_, rq, rs, q0 + AB_CK, a.Lq, tid);
+        if (more) chunk_load(cr, qb_, db_, rq, rs, q0 + AT_CK, a.Lq, tid);
         const uint8_t* Qs = qd_img[c & 1][0];
         const uint8_t* Ds = qd_img[c & 1][1];
         if (has_k) {
@@ -401,7 +289,7 @@ __global__ __launch_bounds__(AB_NW * 64, 2) void attn_long_dkv_kernel(AttnArgs a
                 }
             }
         }
-        if (more) chunk_store(cr, qd_img[(c + 1) & 1][0], qd_img[(c + 1) & 1][1], q0 + AB_CK, a.Lq, tid);
+        if (more) chunk_store(cr, qd_img[(c + 1) & 1][0], qd_img[(c + 1) & 1][1], q0 + AT_CK, a.Lq, tid);
         __syncthreads();
     }
     if (!has_k) return;
