@@ -34,6 +34,7 @@ extern "C" {
 #define VLPET_E_WORKSPACE (-4)  /* workspace too small */
 #define VLPET_E_NULL (-5)       /* required pointer is NULL */
 #define VLPET_E_DTYPE (-6)
+#define VLPET_E_ALIAS (-7)      /* an output overlaps an input that must stay intact */
 
 /* gate modes (config flags of the reference) */
 #define VLPET_GATE_NONE 0       /* adapter only                                              */
@@ -748,6 +749,23 @@ int vlpet_beam_advance_at(const float* part_stats, const float* part_val, const 
                           float* hyp_score, int* hyp_meta, int64_t* hyp_tokens, int64_t ld_hyp, float* item_worst, int* item_state,
                           int* counters, const int* pos_dev, int pos_limit, int eos_token_id, int pad_token_id,
                           float length_penalty, int early_stopping, vlpet_stream_t stream);
+
+/* Sequential adapter + residual + norm of one sublayer in ONE launch, inference form (csrc/adapter_tail.hip):
+ *   out = N(res + h + scale * (up(gelu_new(down(h) + down_b)) + up_b)),   N = LayerNorm(gamma, beta, eps) (norm_mode 1) | identity (0)
+ * i.e. vlpet_parallel_adapter_fwd with x = y = h followed by vlpet_sublayer_tail_fwd without dropout, with no [M, d] round trip
+ * between them.  No dropout, nothing saved for a backward.  h, res, out: [M, d] in io_dtype; down_w [r, d], down_b [r], up_w [d, r],
+ * up_b [d]: the adapter's parameters as they are, all in param_dtype (fp32 parameters next to bf16 IO are rounded on load);
+ * gamma / beta [d] fp32 (beta may be NULL; both ignored with norm_mode 0).  A row's result depends on that row and the parameters
+ * only -- not on M, not on the workgroup that computes it; the launch reads nothing from the host and is capture-safe.
+ * Argument errors (no launch): VLPET_E_NULL; VLPET_E_SHAPE (M <= 0, unknown norm_mode); VLPET_E_RANK ((d, r) other than
+ * (768, 96), (64, 8)); VLPET_E_DTYPE; VLPET_E_ALIGN; VLPET_E_ALIAS (out overlaps h or res).
+ * vlpet_adapter_tail_applies: 1 when vlpet_adapter_tail_fwd takes (M, d, r, io_dtype), else 0.
+ * vlpet_adapter_tail_rows: the rows one workgroup computes (the row tile: tests place their edge cases around it). */
+int vlpet_adapter_tail_rows(void);
+int vlpet_adapter_tail_applies(int64_t M, int d, int r, int io_dtype);
+int vlpet_adapter_tail_fwd(const void* h, const void* res, const void* down_w, const void* down_b, const void* up_w,
+                           const void* up_b, const float* gamma, const float* beta, void* out, int64_t M, int d, int r,
+                           float scale, float eps, int norm_mode, int param_dtype, int io_dtype, vlpet_stream_t stream);
 
 #ifdef __cplusplus
 }

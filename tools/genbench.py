@@ -22,6 +22,11 @@ Beam search (``--num-beams K``, K > 1): generate(num_beams = K) at the video cap
 (B = 30), hip against torch (decode.EAGER).  ``--stats FILE --num-beams K`` reads the kernel stats of a `--num-beams K --paths hip
 --reps 1 --warmup 0 --models bart` run.
 
+``--pet single_adapter``: the Single-Adapter baseline instead of VL-PET (scripts/image-text/single_adapter.sh: a sequential adapter of
+width 96 behind every attention and feed-forward block of both stacks, no VL-PET module).  ``--adapter-tail-ab N``: after the legs, N
+rounds of alternating FUSE_ADAPTER_TAIL off / on calls of every hip / graph leg asked for (same process, same inputs; a graph leg
+re-captures after every flip, untimed): ms per call and per step of both settings, and whether the tokens agree.
+
 ``--long-attention``: the hosts' LONG_ATTENTION switch on for every leg (the 664-token encoder on csrc/attn_long.hip).
 ``--long-ab N`` (with ``--num-beams``): after the legs, N rounds of alternating switch-off / switch-on hip calls, two successive
 calls each: ms per call of both settings and the fraction of tokens on which the two successive calls agree (1.0 = reproducible).
@@ -64,17 +69,28 @@ def beam_bytes(B, K, S_enc, E, n_layers, max_length, V, esz=2):
                 advance=sum(rows * (4 * 2 * K + 2 * 8 * (p + 2) + 2 * 4 * (p + 2)) for p in range(steps)), advance_calls=steps)
 
 
-def build(dev, kind="bart", video=False):
+SINGLE_ADAPTER = dict(use_adapter=True, use_single_adapter=True, no_encoder_adapter=False, no_decoder_adapter=False,
+                      unfreeze_layer_norms=True, use_adapter_down_dim=False, reduction_factor=8, use_encoder_adapter_down_multihead=False,
+                      use_encoder_adapter_gating_large_x_lowrank=False, use_decoder_enc_attn_value_parallel_adapter_down_dim=False,
+                      unfreeze_encoder_layer_norms=False)      # single_adapter.sh
+
+
+def build(dev, kind="bart", video=False, pet="vlpet"):
     import torch
     import vlpet_amd.host.bart as HB
     import vlpet_amd.train as TR
     torch.manual_seed(0)
+    over = dict(feat_dim=512, n_boxes=64, tasks="tvqa,how2qa,tvc,yc2c") if video else {}
+    if pet == "single_adapter":
+        over.update(SINGLE_ADAPTER)
     if kind == "t5":
         import vlpet_amd.host.t5 as HT
-        cfg = HT.vlt5_config(feat_dim=512, n_boxes=64, tasks="tvqa,how2qa,tvc,yc2c") if video else HT.vlt5_config()
+        if pet == "single_adapter":
+            over.update(use_encoder_gating_scaling=False)
+        cfg = HT.vlt5_config(**over)
         model = HT.VLT5(cfg)
     else:
-        cfg = HB.vlpet_config(feat_dim=512, n_boxes=64, tasks="tvqa,how2qa,tvc,yc2c") if video else HB.vlpet_config()
+        cfg = HB.vlpet_config(**over)
         model = HB.VLBart(cfg)
     TR.trainable_names(model, cfg)
     model.to(dev)
@@ -151,6 +167,46 @@ def ab_rounds(args, calls, steps, tag):
     return row
 
 
+def adapter_tail_ab(args, calls, steps, tag):
+    """alternating FUSE_ADAPTER_TAIL off / on calls of each leg in ``calls``"""
+    import torch
+    import vlpet_amd.adapter_tail as AT
+    import vlpet_amd.decode as D
+    import vlpet_amd.host.bart as HB
+    import vlpet_amd.host.t5 as HT
+    saved = (HB.FUSE_ADAPTER_TAIL, HT.FUSE_ADAPTER_TAIL)
+    rows = []
+    try:
+        for path, call in calls.items():
+            per, outs, fused_calls = {"off": [], "on": []}, {}, {}
+            for _ in range(args.adapter_tail_ab):
+                for leg in ("off", "on"):
+                    HB.FUSE_ADAPTER_TAIL = HT.FUSE_ADAPTER_TAIL = leg == "on"
+                    D.clear_graphs()
+                    n0 = AT.CALLS
+                    call(), call()                                   # (a graph leg: eager warm-up, capture)
+                    fused_calls[leg] = (AT.CALLS - n0) // 2
+                    torch.cuda.synchronize()
+                    t = time.perf_counter()
+                    for _ in range(args.reps):
+                        outs[leg] = call()
+                    torch.cuda.synchronize()
+                    per[leg].append((time.perf_counter() - t) * 1e3 / args.reps)
+            mean = {leg: sum(v) / len(v) for leg, v in per.items()}
+            same = outs["on"].shape == outs["off"].shape and bool((outs["on"] == outs["off"]).all())
+            row = dict(tag, path=path, adapter_tail_ab_rounds=args.adapter_tail_ab, reps=args.reps, max_rows=AT.ADAPTER_TAIL_MAX_ROWS,
+                       fused_launches_per_eager_call=fused_calls,
+                       **{f"fuse_{leg}_ms": [round(x, 2) for x in v] for leg, v in per.items()},
+                       **{f"fuse_{leg}_step_ms": round(m / steps, 3) for leg, m in mean.items()},
+                       on_over_off=round(mean["on"] / mean["off"], 3), tokens_equal=same)
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+    finally:
+        HB.FUSE_ADAPTER_TAIL, HT.FUSE_ADAPTER_TAIL = saved
+        D.clear_graphs()
+    return rows
+
+
 def launches_per_step(make_call):
     """kernel launches of ONE decode step: a call of three tokens minus a call of two, counted by the torch profiler.
     ``make_call(max_length)`` returns the call."""
@@ -175,7 +231,7 @@ def run(args):
     import vlpet_amd.host.bart as HB
     import vlpet_amd.train as TR
     dev = "cuda"
-    model, cfg = build(dev)
+    model, cfg = build(dev, pet=args.pet)
     rows = []
     for shape in args.shapes:
         sh = SHAPES[shape]
@@ -220,6 +276,8 @@ def run(args):
             print(json.dumps(row), flush=True)
         if "hip" in outs and "graph" in outs and args.ab_rounds > 0:
             ab_rounds(args, {p: calls[p] for p in ("hip", "graph")}, steps, dict(shape=shape, encoder_ms=round(enc_ms, 2)))
+        if args.adapter_tail_ab > 0:
+            adapter_tail_ab(args, {p: calls[p] for p in ("hip", "graph") if p in outs}, steps, dict(shape=shape, B=sh["B"], pet=args.pet))
         if "hip" in outs:
             for p, o in outs.items():       # bf16 paths may part ways where two logits are within rounding: report, do not fail
                 agree = float((o == outs["hip"]).float().mean())
@@ -236,7 +294,7 @@ def run_beams(args):
     rows = []
     for kind in args.models:
         sh = BEAM_SHAPES[kind]
-        model, cfg = build(dev, kind, video=True)
+        model, cfg = build(dev, kind, video=True, pet=args.pet)
         gen = torch.Generator(device=dev).manual_seed(1)
         b = TR.synthetic_batch(sh["task"], sh["B"], cfg, dev, gen, no_padding=False)
         ids, vis, ml = b["input_ids"], b["vis_inputs"], sh["max_length"]
@@ -271,6 +329,9 @@ def run_beams(args):
             print(json.dumps(dict(model=kind, tokens_equal_to_hip="graph", fraction=round(agree, 4))), flush=True)
             if args.ab_rounds > 0:
                 ab_rounds(args, {p: calls[p] for p in ("hip", "graph")}, ml - 1, dict(model=kind, num_beams=args.num_beams))
+        if args.adapter_tail_ab > 0:
+            adapter_tail_ab(args, {p: calls[p] for p in ("hip", "graph") if p in outs}, ml - 1,
+                            dict(model=kind, num_beams=args.num_beams, B=sh["B"], pet=args.pet))
         if args.long_ab > 0 and "hip" in calls:
             import vlpet_amd.host.t5 as HT
             per, agree = {"off": [], "on": []}, {"off": [], "on": []}
@@ -383,6 +444,8 @@ def main():
     ap.add_argument("--stats", default=None)
     ap.add_argument("--num-beams", type=int, default=1)
     ap.add_argument("--models", nargs="+", default=["bart", "t5"], choices=list(BEAM_SHAPES))
+    ap.add_argument("--pet", default="vlpet", choices=["vlpet", "single_adapter"], help="the PET method the models are built with")
+    ap.add_argument("--adapter-tail-ab", type=int, default=0, help="alternating FUSE_ADAPTER_TAIL off / on rounds of the hip / graph legs")
     ap.add_argument("--long-attention", action="store_true", help="set the hosts' LONG_ATTENTION switch for every leg")
     ap.add_argument("--long-ab", type=int, default=0, help="with --num-beams: alternating switch-off / switch-on rounds of the hip leg")
     args = ap.parse_args()

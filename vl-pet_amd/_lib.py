@@ -167,6 +167,9 @@ SIGNATURES = {
     "vlpet_beam_advance_at": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int64, c_int64,
                                       c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p,
                                       c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "vlpet_adapter_tail_rows": (c_int, []),
+    "vlpet_adapter_tail_applies": (c_int, [c_int64, c_int, c_int, c_int]),
+    "vlpet_adapter_tail_fwd": (c_int, [c_void_p] * 9 + [c_int64, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_void_p]),
     "vlpet_lora_delta_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_uint64, c_void_p, c_void_p,
                                      c_void_p, c_int, c_void_p, c_size_t, c_int64, c_int, c_int, c_float, c_int,
                                      c_void_p]),

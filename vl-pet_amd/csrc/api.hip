@@ -8,7 +8,7 @@
 #include <stdio.h>
 #include <vector>
 
-#define VLPET_VERSION 651      // 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
+#define VLPET_VERSION 660      // 660: vlpet_adapter_tail_fwd, vlpet_adapter_tail_applies, vlpet_adapter_tail_rows (adapter_tail.hip: sequential adapter + residual + norm in one launch, inference form); 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
 #define VLPET_VERSION_R3 300      // 300: column-parallel K1 backward pass (pet_cols.hip), phases bits 3 / 4, vlpet_adapter_gate_bwd_form;
 #define VLPET_VERSION_R2 221      // 221: vlpet_sublayer_tail_reduce, vlpet_layernorm_bwd_xhat, vlpet_rmsnorm_{fwd,bwd}, vlpet_colsum;  round 2: LoRA dropout generator ABI, sliced AdamW, K3 training form; 210: strided attention entry points, streaming weight gradients; 220: low-rank visual projector
 
@@ -53,6 +53,7 @@ extern "C" const char* vlpet_error_string(int code) {
         case VLPET_E_WORKSPACE: return "workspace too small";
         case VLPET_E_NULL: return "required pointer is NULL";
         case VLPET_E_DTYPE: return "unsupported dtype";
+        case VLPET_E_ALIAS: return "output overlaps an input";
         default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown error";
     }
 }
@@ -1677,3 +1678,34 @@ extern "C" int vlpet_adamw_step_sliced(float* p, float* g, float* m, float* v, c
     return herr(launch_adamw(a, (hipStream_t)stream));
 }
 
+// ---- sequential adapter + residual + norm, inference form (adapter_tail.hip)
+extern "C" int vlpet_adapter_tail_rows(void) { return adapter_tail_rows(); }
+
+extern "C" int vlpet_adapter_tail_applies(int64_t M, int d, int r, int io_dtype) {
+    return (M > 0 && (M + adapter_tail_rows() - 1) / adapter_tail_rows() <= 0x7fffffffLL && adapter_tail_geometry_ok(d, r) && dtype_ok(io_dtype)) ? 1 : 0;
+}
+
+static inline bool ranges_overlap(const void* a, const void* b, size_t bytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + bytes && y < x + bytes;
+}
+
+extern "C" int vlpet_adapter_tail_fwd(const void* h, const void* res, const void* down_w, const void* down_b, const void* up_w,
+                                      const void* up_b, const float* gamma, const float* beta, void* out, int64_t M, int d, int r,
+                                      float scale, float eps, int norm_mode, int param_dtype, int io_dtype, vlpet_stream_t stream) {
+    if (!h || !res || !down_w || !down_b || !up_w || !up_b || !out) return VLPET_E_NULL;
+    if (norm_mode != 0 && norm_mode != 1) return VLPET_E_SHAPE;
+    if (norm_mode == 1 && !gamma) return VLPET_E_NULL;
+    if (!dtype_ok(io_dtype) || !dtype_ok(param_dtype)) return VLPET_E_DTYPE;
+    if (M <= 0 || d <= 0 || r <= 0) return VLPET_E_SHAPE;
+    if (!adapter_tail_geometry_ok(d, r)) return VLPET_E_RANK;
+    if (!vlpet_adapter_tail_applies(M, d, r, io_dtype)) return VLPET_E_SHAPE;
+    if (!aligned16(h) || !aligned16(res) || !aligned16(down_w) || !aligned16(down_b) || !aligned16(up_w) || !aligned16(up_b) ||
+        !aligned16(out) || (norm_mode == 1 && (!aligned16(gamma) || (beta && !aligned16(beta))))) return VLPET_E_ALIGN;
+    const size_t bytes = (size_t)M * d * (io_dtype == VLPET_F32 ? 4 : 2);
+    if (ranges_overlap(out, h, bytes) || ranges_overlap(out, res, bytes)) return VLPET_E_ALIAS;
+    AdapterTailArgs a{};
+    a.h = h; a.res = res; a.wd = down_w; a.bd = down_b; a.wu = up_w; a.bu = up_b; a.gamma = gamma; a.beta = beta; a.out = out;
+    a.M = M; a.d = d; a.r = r; a.scale = scale; a.eps = eps; a.norm = norm_mode;
+    return herr(launch_adapter_tail(a, io_dtype == VLPET_F32, param_dtype == VLPET_F32, (hipStream_t)stream));
+}

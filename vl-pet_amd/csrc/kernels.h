@@ -458,3 +458,23 @@ hipError_t launch_attn(const AttnArgs& a, bool bwd, hipStream_t stream);
 hipError_t launch_attn_long_fwd(const AttnArgs& a, hipStream_t stream);
 // its backward (attn_long_bwd.hip): two launches (dQ + delta, then dK / dV); delta [B, H, Lq] fp32 is scratch of the caller; bias_t is not read
 hipError_t launch_attn_long_bwd(const AttnArgs& a, float* delta, hipStream_t stream);
+
+// sequential adapter + residual + norm in one launch, inference form (adapter_tail.hip): out = N(res + h + scale * adapter(h))
+struct AdapterTailArgs {
+    const void* h;          // [M, d] IO dtype: the sublayer output the adapter reads (and adds back)
+    const void* res;        // [M, d] IO dtype: the sublayer input (residual stream)
+    const void* wd;         // [r, d] parameter dtype (down_sampler.weight)
+    const void* bd;         // [r]
+    const void* wu;         // [d, r] (up_sampler.weight)
+    const void* bu;         // [d]
+    const float* gamma;     // [d] fp32 (norm == 1)
+    const float* beta;      // [d] fp32 or nullptr
+    void* out;              // [M, d] IO dtype
+    int64_t M;
+    int d, r;
+    float scale, eps;
+    int norm;               // 0: identity (T5), 1: LayerNorm (BART)
+};
+int adapter_tail_rows(void);                     // rows per workgroup (the kernel's row tile)
+bool adapter_tail_geometry_ok(int d, int r);     // the (d, r) pairs that are instantiated
+hipError_t launch_adapter_tail(const AdapterTailArgs& a, int io_fp32, int param_fp32, hipStream_t stream);

@@ -30,11 +30,13 @@ import torch.nn.functional as F
 from .. import attention as A
 from .. import decode as D
 from .. import functional as VF
-from ..adapters import AdapterConfig
+from .. import adapter_tail as AT
+from ..adapters import AdapterConfig, AdapterController
 from ..encoder_pet import apply_pet, build_pet, has_pet
 from ..lora import LoRALinearController, LoraConfig
 from ..visual import Downsample, LowRankVisualEmbedding, VisualEmbedding
-from .common import derived_weights, eval_no_grad, is_key_mask, shift_right, unpack_vis_inputs, value_parallel_adapter
+from .common import (check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail, is_key_mask, sequential_adapters,
+                     shift_right, unpack_vis_inputs, value_parallel_adapter)
 
 TASKS = ["vqa", "gqa", "nlvr", "caption"]
 
@@ -56,7 +58,7 @@ def vlpet_config(**over) -> SimpleNamespace:
         use_visual_projector_residual_connection=False,
         # PET flags
         tasks=",".join(TASKS), use_adapter=True, use_single_adapter=True, no_encoder_adapter=True,
-        no_decoder_adapter=True, use_adapter_down_dim=True, adapter_down_dim=96,
+        no_decoder_adapter=True, add_adapter_cross_attn=True, use_adapter_down_dim=True, adapter_down_dim=96,
         use_encoder_adapter_down_multihead=True, encoder_adapter_multihead_num_head=4,
         use_encoder_adapter_gating_large_x_lowrank=True, adapter_gating_down_dim=96,
         use_encoder_adapter_gating_add=False, use_encoder_adapter_gating_small_xy_cat=False,
@@ -64,7 +66,7 @@ def vlpet_config(**over) -> SimpleNamespace:
         use_encoder_gating_scaling=False, encoder_gating_scaling_factor=1.0,
         use_encoder_adapter_scaling=False, encoder_adapter_scaling_factor=1.0,
         use_encoder_x2_scaling=False, encoder_x2_scaling_factor=1.0,
-        unfreeze_encoder_layer_norms=True,
+        unfreeze_encoder_layer_norms=True, unfreeze_layer_norms=False,
         use_decoder_enc_attn_value_parallel_adapter_down_dim=True, decoder_enc_attn_value_parallel_adapter_down_dim=96,
         use_decoder_enc_attn_value_parallel_adapter_scaling=False,
         decoder_enc_attn_value_parallel_adapter_scaling_factor=1.0,
@@ -76,6 +78,7 @@ def vlpet_config(**over) -> SimpleNamespace:
         if not hasattr(c, k):
             raise AttributeError(f"unknown config field {k}")
         setattr(c, k, v)
+    check_sequential_adapter_flags(c)
     task_list = [t for t in c.tasks.replace(" ", ",").split(",") if t]
     c.task_list = task_list
     if c.use_adapter or c.use_decoder_enc_attn_value_parallel_adapter_down_dim:
@@ -116,6 +119,24 @@ def _pet_then_tail(layer, which, residual, h, norm, p, training, config, gemm_li
     link = VF.ResidualLink()
     y = apply_pet(layer, which, residual, h, config, link=link, out_link=gemm_link)
     return sublayer_tail(residual, y, norm, p, training, link=link)
+
+
+# Sequential adapters (the Single-Adapter baseline: ``attn_adapter`` / ``ff_adapter`` of the encoder layers, ``self_attn_adapter`` /
+# ``enc_attn_adapter`` / ``ff_adapter`` of the decoder layers) sit between the sublayer and its tail.  Where no gradient and no dropout
+# is needed and the shape is one the kernel takes, adapter + residual + LayerNorm are ONE launch (vlpet_amd.adapter_tail); everywhere
+# else K2 (x and residual the same tensor) followed by K5.
+FUSE_ADAPTER_TAIL = True     # (A/B switch, tools/ab_switches.py: False = always K2 + K5)
+
+
+def _adapter_then_tail(ctl, task, residual, h, norm, p, training, gemm_link=None):
+    """``norm(residual + dropout(h + s * adapter(h)))`` -- my_transformers/modeling_bart.py:1145-1146 + :1259-1261 (encoder),
+    :1660-1661, 1717-1718, 1759-1760 (decoder)"""
+    ad = fused_adapter_tail(FUSE_ADAPTER_TAIL, ctl, task, h, residual, norm, p, training)
+    if ad is not None:
+        scale = float(ctl.config.scaling_factor) if ctl.config.use_scaling_factor else 1.0
+        return AT.adapter_tail(h, residual, ad.down_sampler.weight, ad.down_sampler.bias, ad.up_sampler.weight, ad.up_sampler.bias,
+                               norm, scale)
+    return _tail_linked(residual, ctl(h, task), norm, p, training, gemm_link)
 
 
 # The same hand-over one op further: the input of a sublayer is also the input of its first frozen projection (q|k|v, q_proj,
@@ -397,6 +418,11 @@ class BartEncoderLayer(nn.Module):
         self.fc2 = nn.Linear(config.encoder_ffn_dim, d)
         self.final_layer_norm = HostLayerNorm(d)
         build_pet(self, config, d, ("attn", "ff"))
+        # my_transformers/modeling_bart.py:932-947: one AdapterController behind the attention, one behind fc2
+        self.attn_adapter = self.ff_adapter = None
+        if sequential_adapters(config, "encoder"):
+            self.attn_adapter = AdapterController(config.adapter_config)
+            self.ff_adapter = AdapterController(config.adapter_config)
         # the reference's BART encoder layer has no adapter / x2 scaling (my_transformers/modeling_bart.py:1147-1155 is a plain
         # h + up(...)); only the T5 layers read those flags (my_transformers/modeling_t5.py:373-377, 789-793)
         self.pet_config = copy.copy(config)
@@ -407,7 +433,9 @@ class BartEncoderLayer(nn.Module):
         residual = hidden
         gl = _new_gemm_link(hidden)
         h = self.self_attn(hidden, attn_mask=attn_mask, task=task, in_link=gl)
-        if has_pet(self, "attn"):                                                   # K1 + K5
+        if self.attn_adapter is not None:                                           # K2 + K5 | the fused launch
+            hidden = _adapter_then_tail(self.attn_adapter, task, residual, h, self.self_attn_layer_norm, self.dropout, self.training, gl)
+        elif has_pet(self, "attn"):                                                 # K1 + K5
             hidden = _pet_then_tail(self, "attn", residual, h, self.self_attn_layer_norm, self.dropout, self.training,
                                     self.pet_config, gemm_link=gl)
         else:
@@ -416,6 +444,8 @@ class BartEncoderLayer(nn.Module):
         gl = _new_gemm_link(hidden)
         h = ffn_activation(_first_linear(self.fc1, hidden, gl), "gelu", self.activation_dropout, self.training)
         h = _linear(self.fc2, h)
+        if self.ff_adapter is not None:
+            return _adapter_then_tail(self.ff_adapter, task, residual, h, self.final_layer_norm, self.dropout, self.training, gl)
         if has_pet(self, "ff"):                                                     # K1 + K5
             return _pet_then_tail(self, "ff", residual, h, self.final_layer_norm, self.dropout, self.training, self.pet_config,
                                   gemm_link=gl)
@@ -437,21 +467,34 @@ class BartDecoderLayer(nn.Module):
         self.fc1 = nn.Linear(d, config.decoder_ffn_dim)
         self.fc2 = nn.Linear(config.decoder_ffn_dim, d)
         self.final_layer_norm = HostLayerNorm(d)
+        # my_transformers/modeling_bart.py:1525-1536: an AdapterController behind each of the three sublayers
+        self.self_attn_adapter = self.enc_attn_adapter = self.ff_adapter = None
+        if sequential_adapters(config, "decoder"):
+            self.self_attn_adapter = AdapterController(config.adapter_config)
+            if config.add_adapter_cross_attn:
+                self.enc_attn_adapter = AdapterController(config.adapter_config)
+            self.ff_adapter = AdapterController(config.adapter_config)
+
+    def _tail(self, ctl, task, residual, h, norm, gl=None):
+        """the sublayer's tail: behind its sequential adapter when it has one"""
+        if ctl is not None:
+            return _adapter_then_tail(ctl, task, residual, h, norm, self.dropout, self.training, gl)
+        return _tail_linked(residual, h, norm, self.dropout, self.training, gl)                            # K5
 
     def forward(self, hidden, enc, enc_mask=None, task=None, k_pre=None):
         residual = hidden
         gl = _new_gemm_link(hidden)
         h = self.self_attn(hidden, causal=True, task=task, in_link=gl)
-        hidden = _tail_linked(residual, h, self.self_attn_layer_norm, self.dropout, self.training, gl)   # K5
+        hidden = self._tail(self.self_attn_adapter, task, residual, h, self.self_attn_layer_norm, gl)
         residual = hidden
         gl = _new_gemm_link(hidden)
         h = self.encoder_attn(hidden, kv=enc, attn_mask=enc_mask, task=task, in_link=gl, k_pre=k_pre)      # K2 inside
-        hidden = _tail_linked(residual, h, self.encoder_attn_layer_norm, self.dropout, self.training, gl)  # K5
+        hidden = self._tail(self.enc_attn_adapter, task, residual, h, self.encoder_attn_layer_norm, gl)
         residual = hidden
         gl = _new_gemm_link(hidden)
         h = ffn_activation(_first_linear(self.fc1, hidden, gl), "gelu", self.activation_dropout, self.training)
         h = _linear(self.fc2, h)
-        return _tail_linked(residual, h, self.final_layer_norm, self.dropout, self.training, gl)             # K5
+        return self._tail(self.ff_adapter, task, residual, h, self.final_layer_norm, gl)
 
 
     def step(self, x, cache, pos, state, task=None):
@@ -460,11 +503,11 @@ class BartDecoderLayer(nn.Module):
         ks, vs, kx, vx = cache
         kr, pd = state.key_rows, state.pos_dev
         h = self.self_attn.step_self(x, ks, vs, pos, task, key_rows=kr if kr is None or pd is not None else kr[pos & 1], pos_dev=pd)
-        x = sublayer_tail(x, h, self.self_attn_layer_norm, self.dropout, self.training)                     # K5
+        x = self._tail(self.self_attn_adapter, task, x, h, self.self_attn_layer_norm)                       # K5 | adapter + K5 in one launch
         h = self.encoder_attn.step_cross(x, kx, vx, state.key_mask, task, group=state.group)
-        x = sublayer_tail(x, h, self.encoder_attn_layer_norm, self.dropout, self.training)                  # K5
+        x = self._tail(self.enc_attn_adapter, task, x, h, self.encoder_attn_layer_norm)
         h = ffn_activation(_linear(self.fc1, x), "gelu", self.activation_dropout, self.training)
-        return sublayer_tail(x, _linear(self.fc2, h), self.final_layer_norm, self.dropout, self.training)   # K5
+        return self._tail(self.ff_adapter, task, x, _linear(self.fc2, h), self.final_layer_norm)
 
 
 class LearnedPositionalEmbedding(nn.Embedding):

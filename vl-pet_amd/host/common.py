@@ -40,6 +40,55 @@ def value_parallel_adapter(config) -> AdapterController:
     return AdapterController(ac)
 
 
+GATE_FLAGS = ("use_encoder_adapter_gating_large_x_lowrank", "use_encoder_adapter_gating_small_xy_cat",
+              "use_encoder_adapter_gating_middle_xy_add", "use_encoder_adapter_gating_middle_ia3_add")
+
+
+def sequential_adapters(config, side: str) -> bool:
+    """``side`` = "encoder" | "decoder": the Single-Adapter placement -- an AdapterController behind every attention and feed-forward
+    block of that stack (my_transformers/modeling_bart.py:932, 1525; modeling_t5.py:307, 350, 701, 744, 847)"""
+    return bool(config.use_adapter) and not getattr(config, f"no_{side}_adapter")
+
+
+def check_sequential_adapter_flags(config) -> None:
+    """The launch scripts never combine sequential encoder adapters with the multi-head adapter (K1) or a gate, nor sequential decoder
+    adapters with the value-parallel adapter; the reference resolves such a mix by the order of its if / elif chains.  Refused here
+    rather than guessed."""
+    if sequential_adapters(config, "encoder"):
+        clash = [f for f in ("use_encoder_adapter_down_multihead",) + GATE_FLAGS if getattr(config, f, False)]
+        if clash:
+            raise ValueError("use_adapter with no_encoder_adapter=False (sequential encoder adapters) cannot be combined with "
+                             + ", ".join(clash))
+    if sequential_adapters(config, "decoder") and config.use_decoder_enc_attn_value_parallel_adapter_down_dim:
+        raise ValueError("use_adapter with no_decoder_adapter=False (sequential decoder adapters) cannot be combined with "
+                         "use_decoder_enc_attn_value_parallel_adapter_down_dim")
+
+
+def fused_adapter_tail(enabled, ctl, task, h, residual, norm, p, training):
+    """The plain ``Adapter`` of ``ctl`` for ``task`` when "adapter, then tail" may run as the one fused launch
+    (vlpet_amd.adapter_tail), else None: switched on, on the GPU, no dropout, no gradient needed, the fused ``Adapter`` with nothing
+    around it inside the controller, a shape the kernel takes, at most ``ADAPTER_TAIL_MAX_ROWS`` rows."""
+    from .. import adapter_tail as AT
+    from ..adapters.adapter_modeling import Adapter
+    if not enabled or not h.is_cuda or (training and p > 0):
+        return None
+    cfg = ctl.config
+    if cfg.use_parallel_adapter or ctl.add_layer_norm_before_adapter or ctl.add_layer_norm_after_adapter:
+        return None
+    ad = ctl.get_adapter(ctl.get_task(task))
+    if type(ad) is not Adapter or ad.eager:
+        return None
+    if torch.is_grad_enabled():
+        params = list(ad.parameters()) + ([] if norm is None else list(norm.parameters()))
+        if h.requires_grad or residual.requires_grad or any(t.requires_grad for t in params):
+            return None
+    d = h.shape[-1]
+    M = h.numel() // d
+    if M == 0 or M > AT.ADAPTER_TAIL_MAX_ROWS or not AT.applies(M, d, ad.down_sample_size, h.dtype):
+        return None
+    return ad
+
+
 def unpack_vis_inputs(vis_inputs, downsample, dtype):
     """(feats, boxes, img_ids or None, obj_ids or None) of the loader's visual tuple, the features in ``dtype``: through the
     encoder's ``Downsample`` when it has one (fp32 CLIP features -> compute dtype inside the pooling kernel; rounding is monotone:

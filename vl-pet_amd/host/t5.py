@@ -23,11 +23,13 @@ import torch.nn.functional as F
 from .. import attention as A
 from .. import decode as D
 from .. import functional as VF
-from ..adapters import AdapterConfig
+from .. import adapter_tail as AT
+from ..adapters import AdapterConfig, AdapterController
 from ..encoder_pet import apply_pet, build_pet, has_pet
 from ..visual import Downsample, T5LayerNorm, VisualEmbedding
 from .bart import TASKS, _linear
-from .common import derived_weights, eval_no_grad, shift_right, unpack_vis_inputs, value_parallel_adapter
+from .common import (check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail, sequential_adapters, shift_right,
+                     unpack_vis_inputs, value_parallel_adapter)
 
 
 # K1's gate and the sublayer tail both read the sublayer input; with a link the tail's backward hands its d/dx1 to K1's
@@ -91,6 +93,30 @@ def _tail_linked(hidden, y, p, training, link, layer=None):
     return sublayer_tail(hidden, y, None, p, training, link=link)
 
 
+# Sequential adapters (the Single-Adapter baseline: ``attn_adapter`` / ``enc_attn_adapter`` / ``ff_adapter`` of the sublayer modules):
+# ``hidden + dropout(y + s * adapter(y))`` (my_transformers/modeling_t5.py:363-364, 779-780, 886-887) is K2 (x and residual the same
+# tensor) followed by the tail.  The fused launch of vlpet_amd.adapter_tail (identity norm) takes adapter + add where no gradient and
+# no dropout is needed; the next sublayer's RMS norm then runs as its own kernel, so against K2 + the fused tail-and-norm pass it saves
+# no launch on this host -- off by default here (host/bart.py, where it replaces two launches by one, has it on).
+FUSE_ADAPTER_TAIL = False    # (A/B switch, tools/ab_switches.py)
+
+
+def _adapter_then_tail(ctl, task, hidden, y, p, training, link, layer):
+    ad = fused_adapter_tail(FUSE_ADAPTER_TAIL and sublayer_tail is _HIP_SUBLAYER_TAIL, ctl, task, y, hidden, None, p, training)
+    if ad is not None:
+        scale = float(ctl.config.scaling_factor) if ctl.config.use_scaling_factor else 1.0
+        return AT.adapter_tail(y, hidden, ad.down_sampler.weight, ad.down_sampler.bias, ad.up_sampler.weight, ad.up_sampler.bias,
+                               None, scale)
+    return _tail_linked(hidden, ctl(y, task), p, training, link, layer=layer)
+
+
+def _tail_or_adapter(ctl, task, hidden, y, p, training, link, layer):
+    """the sublayer's tail: behind its sequential adapter when it has one"""
+    if ctl is not None:
+        return _adapter_then_tail(ctl, task, hidden, y, p, training, link, layer)
+    return _tail_linked(hidden, y, p, training, link, layer=layer)             # K5 (+ the next sublayer's norm)
+
+
 def ffn_activation(x, act, p, training):
     """``dropout(relu(wi output))`` of T5DenseReluDense as one fused HIP pass (vlpet_amd.act); harnesses swap this
     attribute for the eager pair."""
@@ -131,7 +157,7 @@ def vlt5_config(**over) -> SimpleNamespace:
         feat_dim=2048, pos_dim=4, n_images=2, n_boxes=36, downsample=True, use_vis_order_embedding=True,
         use_vis_layer_norm=True, individual_vis_layer_norm=True, share_vis_lang_layer_norm=False,
         tasks=",".join(TASKS), use_adapter=True, use_single_adapter=True, no_encoder_adapter=True,
-        no_decoder_adapter=True, use_adapter_down_dim=True, adapter_down_dim=192,
+        no_decoder_adapter=True, add_adapter_cross_attn=True, use_adapter_down_dim=True, adapter_down_dim=192,
         use_encoder_adapter_down_multihead=True, encoder_adapter_multihead_num_head=4,
         use_encoder_adapter_gating_large_x_lowrank=True, adapter_gating_down_dim=192,
         use_encoder_adapter_gating_add=False, use_encoder_adapter_gating_small_xy_cat=False,
@@ -139,7 +165,7 @@ def vlt5_config(**over) -> SimpleNamespace:
         use_encoder_gating_scaling=True, encoder_gating_scaling_factor=0.3,
         use_encoder_adapter_scaling=False, encoder_adapter_scaling_factor=1.0,
         use_encoder_x2_scaling=False, encoder_x2_scaling_factor=1.0,
-        unfreeze_encoder_layer_norms=True,
+        unfreeze_encoder_layer_norms=True, unfreeze_layer_norms=False,
         use_decoder_enc_attn_value_parallel_adapter_down_dim=True, decoder_enc_attn_value_parallel_adapter_down_dim=96,
         use_decoder_enc_attn_value_parallel_adapter_scaling=False,
         decoder_enc_attn_value_parallel_adapter_scaling_factor=1.0,
@@ -151,6 +177,7 @@ def vlt5_config(**over) -> SimpleNamespace:
         if not hasattr(c, k):
             raise AttributeError(f"unknown config field {k}")
         setattr(c, k, v)
+    check_sequential_adapter_flags(c)
     c.task_list = [t for t in c.tasks.replace(" ", ",").split(",") if t]
     c.adapter_config = AdapterConfig(
         tasks=c.task_list, input_dim=c.d_model, d_model=c.d_model, use_single_adapter=c.use_single_adapter,
@@ -396,13 +423,15 @@ class T5LayerSelfAttention(nn.Module):
         self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         if not is_decoder:
             build_pet(self, config, config.d_model, ("attn",))
+        # my_transformers/modeling_t5.py:701-702, 744-745
+        self.attn_adapter = AdapterController(config.adapter_config) if sequential_adapters(config, "decoder" if is_decoder else "encoder") else None
 
     def forward(self, hidden, bias, task=None):
         nl = _new_norm_link(hidden)
         y = self.SelfAttention(_normed(self.layer_norm, hidden, nl), bias)
         if not self.is_decoder and has_pet(self, "attn"):                                 # K1 (x1 = un-normalised stream) + K5
             return _pet_then_tail(self, "attn", hidden, y, None, self.p, self.training, self.config, norm_link=nl)
-        return _tail_linked(hidden, y, self.p, self.training, nl, layer=self)             # K5 (+ the next sublayer's norm)
+        return _tail_or_adapter(self.attn_adapter, task, hidden, y, self.p, self.training, nl, self)
 
 
 class T5LayerCrossAttention(nn.Module):
@@ -412,11 +441,14 @@ class T5LayerCrossAttention(nn.Module):
         self.EncDecAttention = T5Attention(config, True, False,
                                            value_adapter=bool(config.use_decoder_enc_attn_value_parallel_adapter_down_dim))
         self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
+        # my_transformers/modeling_t5.py:847-850
+        self.enc_attn_adapter = (AdapterController(config.adapter_config)
+                                 if sequential_adapters(config, "decoder") and config.add_adapter_cross_attn else None)
 
     def forward(self, hidden, enc, bias, task=None, k_pre=None):
         nl = _new_norm_link(hidden)
         y = self.EncDecAttention(_normed(self.layer_norm, hidden, nl), bias, kv=enc, task=task, k_pre=k_pre)
-        return _tail_linked(hidden, y, self.p, self.training, nl, layer=self)
+        return _tail_or_adapter(self.enc_attn_adapter, task, hidden, y, self.p, self.training, nl, self)
 
 
 class T5LayerFF(nn.Module):
@@ -427,13 +459,15 @@ class T5LayerFF(nn.Module):
         self.layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         if not is_decoder:
             build_pet(self, config, config.d_model, ("ff",))
+        # my_transformers/modeling_t5.py:307-308, 350-351
+        self.ff_adapter = AdapterController(config.adapter_config) if sequential_adapters(config, "decoder" if is_decoder else "encoder") else None
 
     def forward(self, hidden, task=None):
         nl = _new_norm_link(hidden)
         y = self.DenseReluDense(_normed(self.layer_norm, hidden, nl))
         if not self.is_decoder and has_pet(self, "ff"):
             return _pet_then_tail(self, "ff", hidden, y, None, self.p, self.training, self.config, norm_link=nl)      # K1 + K5
-        return _tail_linked(hidden, y, self.p, self.training, nl, layer=self)
+        return _tail_or_adapter(self.ff_adapter, task, hidden, y, self.p, self.training, nl, self)
 
 
 class T5Block(nn.Module):
@@ -453,7 +487,7 @@ class T5Block(nn.Module):
         return self.layer[-1](hidden, task)
 
 
-def _block_step(blk, x, cache, pos, state, bias_row):
+def _block_step(blk, x, cache, pos, state, bias_row, task=None):
     """generate(): one decoder block on the token x [B, 1, d]; ``cache`` = this block's (self k, self v, cross k, cross v) of ``state``
     (decode.DecodeState), ``bias_row`` = row ``pos`` of its bias table.  The tails are forward's (_tail_linked: on the GPU each fused
     with the next sublayer's norm)."""
@@ -462,11 +496,11 @@ def _block_step(blk, x, cache, pos, state, bias_row):
     kr, pd = state.key_rows, state.pos_dev
     y = sa.SelfAttention.step_self(sa.layer_norm(x), ks, vs, pos, bias_row,
                                    key_rows=kr if kr is None or pd is not None else kr[pos & 1], pos_dev=pd)
-    x = _tail_linked(x, y, sa.p, sa.training, None, layer=sa)
+    x = _tail_or_adapter(sa.attn_adapter, task, x, y, sa.p, sa.training, None, sa)
     y = ca.EncDecAttention.step_cross(ca.layer_norm(x), kx, vx, state.key_mask, group=state.group)
-    x = _tail_linked(x, y, ca.p, ca.training, None, layer=ca)
+    x = _tail_or_adapter(ca.enc_attn_adapter, task, x, y, ca.p, ca.training, None, ca)
     y = ff.DenseReluDense(ff.layer_norm(x))
-    return _tail_linked(x, y, ff.p, ff.training, None, layer=ff)
+    return _tail_or_adapter(ff.ff_adapter, task, x, y, ff.p, ff.training, None, ff)
 
 
 def _pad_bias(mask, dtype):
@@ -568,11 +602,11 @@ class T5Decoder(nn.Module):
         table = sa0.compute_bias(max_length, max_length)[0].permute(1, 0, 2).float().contiguous()        # [H, q, k] -> [q, H, k]
         return D.new_decode_state(enc, sa0.inner, max_length, ks, vs, key_mask, num_beams, bias_table=table)
 
-    def step(self, tok, pos, state):
+    def step(self, tok, pos, state, task=None):
         x = F.dropout(self.embed_tokens(tok)[:, None], p=self.p, training=self.training)
         bias_row = state.bias_table if state.pos_dev is not None else state.bias_table[pos]    # (the kernel takes row *pos_dev)
         for blk, c in zip(self.block, state.layers):
-            x = _block_step(blk, x, c, pos, state, bias_row)
+            x = _block_step(blk, x, c, pos, state, bias_row, task)
         return F.dropout(self.final_layer_norm(x), p=self.p, training=self.training)[:, 0]
 
 
@@ -634,7 +668,7 @@ class VLT5(nn.Module):
             scale = cfg.d_model ** -0.5
 
             def make_step(st):
-                return lambda tok, pos: F.linear(self.decoder.step(tok, pos, st) * scale, head)
+                return lambda tok, pos: F.linear(self.decoder.step(tok, pos, st, task) * scale, head)
             if graph:
                 gs = D.GenSettings(cfg.decoder_start_token_id, eos, int(pad), int(max_length), int(min_length),
                                    int(no_repeat_ngram_size), int(num_beams), float(length_penalty), bool(early_stopping), False)

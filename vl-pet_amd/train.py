@@ -55,8 +55,14 @@ def trainable_names(model: nn.Module, config) -> List[str]:
                     config.use_encoder_adapter_gating_small_xy_cat or
                     config.use_encoder_adapter_gating_middle_xy_add or
                     config.use_encoder_adapter_gating_middle_ia3_add)
+    # the Single-Adapter placement (host.common.sequential_adapters): every AdapterController trains (trainer_base.py:389-393)
+    any_adapter = any_adapter or bool(config.use_adapter and not (config.no_encoder_adapter and config.no_decoder_adapter))
+    norm_params = set()
+    if getattr(config, "unfreeze_layer_norms", False):      # trainer_base.py:375-380: every LayerNorm / T5LayerNorm module, wherever it sits
+        from .visual import T5LayerNorm
+        norm_params = {id(p) for m in model.modules() if isinstance(m, (nn.LayerNorm, T5LayerNorm)) for p in m.parameters()}
     for n, p in model.named_parameters():
-        on = False
+        on = id(p) in norm_params
         if not config.freeze_vis_emb and "visual_embedding" in n:
             on = True
         if config.use_lora and ("lora" in n or "bias" in n):
