@@ -767,6 +767,27 @@ int vlpet_adapter_tail_fwd(const void* h, const void* res, const void* down_w, c
                            const void* up_b, const float* gamma, const float* beta, void* out, int64_t M, int d, int r,
                            float scale, float eps, int norm_mode, int param_dtype, int io_dtype, vlpet_stream_t stream);
 
+/* Compacter: the weights of one adapter's (down, up) pair of PHM layers, generated from their parameters (csrc/phm.hip).
+ *   PHMLinear(in, out, n): rule A [n, n, n], W [n, in / n, out / n];   H[a k + kk, c p + pp] = sum_i A[i, a, c] W[i, kk, pp]
+ * vlpet_phm_expand_pair_fwd writes wt_d [r, d] = H_down^T and wt_u [d, r] = H_up^T (the nn.Linear layout K2 / K1 / adapter_tail take)
+ * in ONE launch.  rule_d, W_d [n, d/n, r/n], rule_u, W_u [n, r/n, d/n] and both outputs are in param_dtype; the sums are fp32.
+ * rule_d and rule_u may be the same memory (a shared rule).
+ * vlpet_phm_expand_pair_bwd: dwt_d [r, d], dwt_u [d, r] fp32 (as the K2 backward leaves them) -> drule_d, drule_u [n, n, n],
+ * dW_d, dW_u (shapes of W_d, W_u), all fp32, overwritten:
+ *   dW[i, kk, pp] = sum_{a, c} A[i, a, c] dwt[c p + pp, a k + kk]        dA[i, a, c] = sum_{kk, pp} dwt[c p + pp, a k + kk] W[i, kk, pp]
+ * Two launches (tiles, then the sum of the tiles' rule partials in tile order); no atomics: two runs give the same bits.  workspace:
+ * vlpet_phm_workspace_bytes(d, r, n) bytes (0 for arguments the calls refuse).  Both calls read nothing from the host, allocate
+ * nothing and are capture-safe.
+ * Argument errors (no launch), in this order: VLPET_E_NULL; VLPET_E_DTYPE; VLPET_E_RANK (n outside 1 .. 8); VLPET_E_SHAPE (d or r
+ * below n, not a multiple of n, or too large for one grid); VLPET_E_ALIGN; VLPET_E_WORKSPACE; VLPET_E_ALIAS (an output overlaps an
+ * input or another output). */
+size_t vlpet_phm_workspace_bytes(int d, int r, int n);
+int vlpet_phm_expand_pair_fwd(const void* rule_d, const void* W_d, const void* rule_u, const void* W_u, void* wt_d, void* wt_u,
+                              int d, int r, int n, int param_dtype, vlpet_stream_t stream);
+int vlpet_phm_expand_pair_bwd(const float* dwt_d, const float* dwt_u, const void* rule_d, const void* W_d, const void* rule_u,
+                              const void* W_u, float* drule_d, float* dW_d, float* drule_u, float* dW_u, void* workspace,
+                              size_t workspace_bytes, int d, int r, int n, int param_dtype, vlpet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

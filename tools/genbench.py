@@ -27,6 +27,10 @@ width 96 behind every attention and feed-forward block of both stacks, no VL-PET
 rounds of alternating FUSE_ADAPTER_TAIL off / on calls of every hip / graph leg asked for (same process, same inputs; a graph leg
 re-captures after every flip, untimed): ms per call and per step of both settings, and whether the tokens agree.
 
+``--pet compacter``: the Compacter baseline (scripts/image-text/single_compacter.sh: the same placement with PHM adapters, division 2,
+no shared rule, no factorization); the expanded weights are cached for the whole call, so the decode step runs the Single-Adapter
+launches.
+
 ``--long-attention``: the hosts' LONG_ATTENTION switch on for every leg (the 664-token encoder on csrc/attn_long.hip).
 ``--long-ab N`` (with ``--num-beams``): after the legs, N rounds of alternating switch-off / switch-on hip calls, two successive
 calls each: ms per call of both settings and the fraction of tokens on which the two successive calls agree (1.0 = reproducible).
@@ -73,6 +77,8 @@ SINGLE_ADAPTER = dict(use_adapter=True, use_single_adapter=True, no_encoder_adap
                       unfreeze_layer_norms=True, use_adapter_down_dim=False, reduction_factor=8, use_encoder_adapter_down_multihead=False,
                       use_encoder_adapter_gating_large_x_lowrank=False, use_decoder_enc_attn_value_parallel_adapter_down_dim=False,
                       unfreeze_encoder_layer_norms=False)      # single_adapter.sh
+COMPACTER = dict(SINGLE_ADAPTER, use_adapter=False, use_compacter=True, hypercomplex_division=2, shared_phm_rule=False,
+                 factorized_phm=False)                         # single_compacter.sh
 
 
 def build(dev, kind="bart", video=False, pet="vlpet"):
@@ -81,11 +87,11 @@ def build(dev, kind="bart", video=False, pet="vlpet"):
     import vlpet_amd.train as TR
     torch.manual_seed(0)
     over = dict(feat_dim=512, n_boxes=64, tasks="tvqa,how2qa,tvc,yc2c") if video else {}
-    if pet == "single_adapter":
-        over.update(SINGLE_ADAPTER)
+    if pet in ("single_adapter", "compacter"):
+        over.update(SINGLE_ADAPTER if pet == "single_adapter" else COMPACTER)
     if kind == "t5":
         import vlpet_amd.host.t5 as HT
-        if pet == "single_adapter":
+        if pet in ("single_adapter", "compacter"):
             over.update(use_encoder_gating_scaling=False)
         cfg = HT.vlt5_config(**over)
         model = HT.VLT5(cfg)
@@ -444,7 +450,7 @@ def main():
     ap.add_argument("--stats", default=None)
     ap.add_argument("--num-beams", type=int, default=1)
     ap.add_argument("--models", nargs="+", default=["bart", "t5"], choices=list(BEAM_SHAPES))
-    ap.add_argument("--pet", default="vlpet", choices=["vlpet", "single_adapter"], help="the PET method the models are built with")
+    ap.add_argument("--pet", default="vlpet", choices=["vlpet", "single_adapter", "compacter"], help="the PET method the models are built with")
     ap.add_argument("--adapter-tail-ab", type=int, default=0, help="alternating FUSE_ADAPTER_TAIL off / on rounds of the hip / graph legs")
     ap.add_argument("--long-attention", action="store_true", help="set the hosts' LONG_ATTENTION switch for every leg")
     ap.add_argument("--long-ab", type=int, default=0, help="with --num-beams: alternating switch-off / switch-on rounds of the hip leg")

@@ -173,6 +173,9 @@ SIGNATURES = {
     "vlpet_lora_delta_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_uint64, c_void_p, c_void_p,
                                      c_void_p, c_int, c_void_p, c_size_t, c_int64, c_int, c_int, c_float, c_int,
                                      c_void_p]),
+    "vlpet_phm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "vlpet_phm_expand_pair_fwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p]),
+    "vlpet_phm_expand_pair_bwd": (c_int, [c_void_p] * 11 + [c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 

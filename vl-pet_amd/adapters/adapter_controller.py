@@ -2,7 +2,7 @@
 import torch
 import torch.nn as nn
 
-from .adapter_modeling import Adapter, LowRankAdapter
+from .adapter_modeling import Adapter, HyperComplexAdapter, LowRankAdapter
 
 
 class AdapterController(nn.Module):
@@ -12,12 +12,11 @@ class AdapterController(nn.Module):
 
     def __init__(self, config):
         super().__init__()
-        if getattr(config, "hypercomplex_adapters", False):
-            # Compacter's PHM layers (adapters/hypercomplex/): a baseline of the reference, out of scope per SURVEY.md sections 1 / 2
-            raise NotImplementedError("hypercomplex (PHM / Compacter) adapters are a baseline outside the VL-PET hot path (SURVEY.md section 2)")
         self.config = config
         self.low_rank_adapters = bool(getattr(config, "low_rank_adapters", False))     # eager fallback: adapter_modeling.LowRankAdapter
-        self.hypercomplex_adapters = False
+        self.hypercomplex_adapters = bool(getattr(config, "hypercomplex_adapters", False))   # Compacter: adapter_modeling.HyperComplexAdapter
+        self.shared_phm_rule = bool(getattr(config, "shared_phm_rule", False))
+        self.shared_phm_rule_over_tasks = bool(getattr(config, "shared_phm_rule_over_tasks", False))
         self.tasks = config.tasks
         self.use_single_adapter = config.use_single_adapter
         self.share_up_sampler = getattr(config, "share_up_sampler", False)
@@ -35,7 +34,7 @@ class AdapterController(nn.Module):
 
     def construct_adapters(self, tasks):
         adapters = nn.ModuleDict()
-        Adapter_ = LowRankAdapter if self.low_rank_adapters else Adapter
+        Adapter_ = HyperComplexAdapter if self.hypercomplex_adapters else LowRankAdapter if self.low_rank_adapters else Adapter
         if self.use_single_adapter:
             shared = Adapter_(self.config)
             for task in tasks:
@@ -49,6 +48,12 @@ class AdapterController(nn.Module):
             if self.share_down_sampler:
                 for task in tasks:
                     adapters[task].down_sampler = adapters[tasks[0]].down_sampler
+            if self.hypercomplex_adapters and self.shared_phm_rule_over_tasks and not self.shared_phm_rule:
+                # one rule per layer kind for every task (adapter_controller.py:79-84): the first task's parameters, registered under each
+                up_rule, down_rule = adapters[tasks[0]].up_sampler.phm_rule, adapters[tasks[0]].down_sampler.phm_rule
+                for task in tasks:
+                    adapters[task].up_sampler.phm_rule = up_rule
+                    adapters[task].down_sampler.phm_rule = down_rule
         return adapters
 
     @staticmethod
@@ -59,9 +64,11 @@ class AdapterController(nn.Module):
         return self.adapters[task]
 
     def enable_adapters(self, tasks):
+        frozen_rule = self.hypercomplex_adapters and not self.config.learn_phm       # adapter_controller.py:115-120
         for task in self.convert_to_list(tasks):
-            for p in self.get_adapter(task).parameters():
-                p.requires_grad = True
+            for name, p in self.get_adapter(task).named_parameters():
+                if not (frozen_rule and "phm_rule" in name):
+                    p.requires_grad = True
 
     def disable_adapters(self, tasks):
         for task in self.convert_to_list(tasks):

@@ -24,10 +24,23 @@ class AdapterConfig:
     use_scaling_factor: bool = False
     scaling_factor: float = 1.0
     track_z: bool = False
-    # variants outside the hot path: low-rank adapters run as plain torch ops (eager fallback), hypercomplex (PHM) ones are refused
+    # a variant outside the hot path: low-rank adapters run as plain torch ops (eager fallback)
     low_rank_adapters: bool = False
     low_rank_w_init: str = "glorot-uniform"
     low_rank_rank: int = 1
+    # Compacter (hypercomplex / PHM adapters, adapter_modeling.HyperComplexAdapter); defaults of the reference's CompactorConfig
+    # (adapters/config.py:97-109), except ``hypercomplex_adapters`` / ``shared_phm_rule``, which the hosts set from their flags
     hypercomplex_adapters: bool = False
+    hypercomplex_division: int = 4
+    learn_phm: bool = True
+    hypercomplex_nonlinearity: str = "glorot-uniform"
     shared_phm_rule: bool = False
     shared_phm_rule_over_tasks: bool = False
+    factorized_phm: bool = True
+    phm_c_init: str = "normal"
+    phm_rank: int = 1
+    phm_init_range: float = 0.0001
+    # PHM forms no flag of the reference reaches: refused by HyperComplexAdapter with a ValueError that names the field
+    shared_W_phm: bool = False
+    factorized_phm_rule: bool = False
+    kronecker_prod: bool = False

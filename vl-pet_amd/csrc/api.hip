@@ -8,7 +8,7 @@
 #include <stdio.h>
 #include <vector>
 
-#define VLPET_VERSION 660      // 660: vlpet_adapter_tail_fwd, vlpet_adapter_tail_applies, vlpet_adapter_tail_rows (adapter_tail.hip: sequential adapter + residual + norm in one launch, inference form); 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
+#define VLPET_VERSION 670      // 670: vlpet_phm_expand_pair_fwd, vlpet_phm_expand_pair_bwd, vlpet_phm_workspace_bytes (phm.hip: Compacter's PHM weight expansion of one adapter and its backward); 660: vlpet_adapter_tail_fwd, vlpet_adapter_tail_applies, vlpet_adapter_tail_rows (adapter_tail.hip: sequential adapter + residual + norm in one launch, inference form); 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
 #define VLPET_VERSION_R3 300      // 300: column-parallel K1 backward pass (pet_cols.hip), phases bits 3 / 4, vlpet_adapter_gate_bwd_form;
 #define VLPET_VERSION_R2 221      // 221: vlpet_sublayer_tail_reduce, vlpet_layernorm_bwd_xhat, vlpet_rmsnorm_{fwd,bwd}, vlpet_colsum;  round 2: LoRA dropout generator ABI, sliced AdamW, K3 training form; 210: strided attention entry points, streaming weight gradients; 220: low-rank visual projector
 
@@ -1708,4 +1708,69 @@ extern "C" int vlpet_adapter_tail_fwd(const void* h, const void* res, const void
     a.h = h; a.res = res; a.wd = down_w; a.bd = down_b; a.wu = up_w; a.bu = up_b; a.gamma = gamma; a.beta = beta; a.out = out;
     a.M = M; a.d = d; a.r = r; a.scale = scale; a.eps = eps; a.norm = norm_mode;
     return herr(launch_adapter_tail(a, io_dtype == VLPET_F32, param_dtype == VLPET_F32, (hipStream_t)stream));
+}
+
+// ---- Compacter: PHM weight expansion of one adapter's (down, up) pair and its backward (phm.hip)
+static int phm_geometry(int d, int r, int n) {
+    if (n < 1 || n > 8) return VLPET_E_RANK;
+    if (d < n || r < n || d % n != 0 || r % n != 0) return VLPET_E_SHAPE;
+    if (phm_layer_tiles(d, r, n) + phm_layer_tiles(r, d, n) > 0x7fffffffLL) return VLPET_E_SHAPE;
+    return 0;
+}
+static inline size_t phm_ws_bytes(int d, int r, int n) {
+    return align256((size_t)(phm_layer_tiles(d, r, n) + phm_layer_tiles(r, d, n)) * n * n * n * sizeof(float));
+}
+extern "C" size_t vlpet_phm_workspace_bytes(int d, int r, int n) { return phm_geometry(d, r, n) == 0 ? phm_ws_bytes(d, r, n) : 0; }
+
+struct ByteRange { const void* p; size_t bytes; };
+// every output against every input and every later output
+static bool phm_outputs_alias(const ByteRange* in, int n_in, const ByteRange* out, int n_out) {
+    for (int o = 0; o < n_out; ++o) {
+        const uintptr_t x = reinterpret_cast<uintptr_t>(out[o].p);
+        for (int i = 0; i < n_in + n_out; ++i) {
+            if (i >= n_in && i - n_in <= o) continue;
+            const ByteRange& q = i < n_in ? in[i] : out[i - n_in];
+            const uintptr_t y = reinterpret_cast<uintptr_t>(q.p);
+            if (x < y + q.bytes && y < x + out[o].bytes) return true;
+        }
+    }
+    return false;
+}
+
+extern "C" int vlpet_phm_expand_pair_fwd(const void* rule_d, const void* W_d, const void* rule_u, const void* W_u, void* wt_d, void* wt_u,
+                                         int d, int r, int n, int param_dtype, vlpet_stream_t stream) {
+    if (!rule_d || !W_d || !rule_u || !W_u || !wt_d || !wt_u) return VLPET_E_NULL;
+    if (!dtype_ok(param_dtype)) return VLPET_E_DTYPE;
+    if (int rc = phm_geometry(d, r, n)) return rc;
+    if (!aligned16(rule_d) || !aligned16(W_d) || !aligned16(rule_u) || !aligned16(W_u) || !aligned16(wt_d) || !aligned16(wt_u))
+        return VLPET_E_ALIGN;
+    const size_t es = param_dtype == VLPET_F32 ? 4 : 2, nr = (size_t)n * n * n * es, nw = (size_t)d * r / n * es, nh = (size_t)d * r * es;
+    const ByteRange in[4] = {{rule_d, nr}, {W_d, nw}, {rule_u, nr}, {W_u, nw}}, out[2] = {{wt_d, nh}, {wt_u, nh}};
+    if (phm_outputs_alias(in, 4, out, 2)) return VLPET_E_ALIAS;
+    PhmArgs a{};
+    a.l[0].rule = rule_d; a.l[0].W = W_d; a.l[0].wt = wt_d; a.l[0].in = d; a.l[0].out = r;
+    a.l[1].rule = rule_u; a.l[1].W = W_u; a.l[1].wt = wt_u; a.l[1].in = r; a.l[1].out = d;
+    a.n = n;
+    return herr(launch_phm_expand_fwd(a, param_dtype == VLPET_F32, (hipStream_t)stream));
+}
+
+extern "C" int vlpet_phm_expand_pair_bwd(const float* dwt_d, const float* dwt_u, const void* rule_d, const void* W_d, const void* rule_u,
+                                         const void* W_u, float* drule_d, float* dW_d, float* drule_u, float* dW_u, void* workspace,
+                                         size_t workspace_bytes, int d, int r, int n, int param_dtype, vlpet_stream_t stream) {
+    if (!dwt_d || !dwt_u || !rule_d || !W_d || !rule_u || !W_u || !drule_d || !dW_d || !drule_u || !dW_u || !workspace) return VLPET_E_NULL;
+    if (!dtype_ok(param_dtype)) return VLPET_E_DTYPE;
+    if (int rc = phm_geometry(d, r, n)) return rc;
+    if (!aligned16(dwt_d) || !aligned16(dwt_u) || !aligned16(rule_d) || !aligned16(W_d) || !aligned16(rule_u) || !aligned16(W_u) ||
+        !aligned16(drule_d) || !aligned16(dW_d) || !aligned16(drule_u) || !aligned16(dW_u) || !aligned16(workspace)) return VLPET_E_ALIGN;
+    const size_t need = phm_ws_bytes(d, r, n);
+    if (workspace_bytes < need) return VLPET_E_WORKSPACE;
+    const size_t es = param_dtype == VLPET_F32 ? 4 : 2, n3 = (size_t)n * n * n, nw = (size_t)d * r / n, nh = (size_t)d * r;
+    const ByteRange in[6] = {{dwt_d, nh * 4}, {dwt_u, nh * 4}, {rule_d, n3 * es}, {W_d, nw * es}, {rule_u, n3 * es}, {W_u, nw * es}};
+    const ByteRange out[5] = {{drule_d, n3 * 4}, {dW_d, nw * 4}, {drule_u, n3 * 4}, {dW_u, nw * 4}, {workspace, need}};
+    if (phm_outputs_alias(in, 6, out, 5)) return VLPET_E_ALIAS;
+    PhmArgs a{};
+    a.l[0].rule = rule_d; a.l[0].W = W_d; a.l[0].dwt = dwt_d; a.l[0].drule = drule_d; a.l[0].dW = dW_d; a.l[0].in = d; a.l[0].out = r;
+    a.l[1].rule = rule_u; a.l[1].W = W_u; a.l[1].dwt = dwt_u; a.l[1].drule = drule_u; a.l[1].dW = dW_u; a.l[1].in = r; a.l[1].out = d;
+    a.n = n; a.ws = reinterpret_cast<float*>(workspace);
+    return herr(launch_phm_expand_bwd(a, param_dtype == VLPET_F32, (hipStream_t)stream));
 }

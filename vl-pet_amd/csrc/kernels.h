@@ -478,3 +478,22 @@ struct AdapterTailArgs {
 int adapter_tail_rows(void);                     // rows per workgroup (the kernel's row tile)
 bool adapter_tail_geometry_ok(int d, int r);     // the (d, r) pairs that are instantiated
 hipError_t launch_adapter_tail(const AdapterTailArgs& a, int io_fp32, int param_fp32, hipStream_t stream);
+
+// Compacter's weight expansion of one adapter's (down, up) pair of PHM layers and its backward (phm.hip)
+struct PhmLayer {
+    const void* rule;       // [n, n, n] parameter dtype
+    const void* W;          // [n, in / n, out / n] parameter dtype
+    void* wt;               // forward: [out, in] parameter dtype (written)
+    const float* dwt;       // backward: [out, in] fp32
+    float* drule;           // backward: [n, n, n] fp32 (written)
+    float* dW;              // backward: shape of W, fp32 (written)
+    int in, out;
+};
+struct PhmArgs {
+    PhmLayer l[2];          // down (in = d, out = r), up (in = r, out = d)
+    int n;
+    float* ws;              // backward: [tiles of both layers][n^3] fp32
+};
+int64_t phm_layer_tiles(int in, int out, int n);     // workgroups of one layer
+hipError_t launch_phm_expand_fwd(const PhmArgs& a, int param_fp32, hipStream_t stream);
+hipError_t launch_phm_expand_bwd(const PhmArgs& a, int param_fp32, hipStream_t stream);     // two launches

@@ -2,7 +2,8 @@
 fallback").  They run on whatever device the tensors are on, through torch's own kernels and autograd -- in-package code that imports
 nothing from the test infrastructure.  Every call site keeps the fused path as the default and comes
 here only for a variant no launch script of the reference uses: other adapter non-linearities, ``track_z``, low-rank adapters,
-non-square / transposed LoRA layers, the shared-LayerNorm visual embedding, a wide bottleneck with an odd number of heads.
+non-square / transposed LoRA layers, the shared-LayerNorm visual embedding, a wide bottleneck with an odd number of heads; and the
+PHM (Compacter) composition for CPU tensors and divisions the expansion kernel does not take.
 Each function restates the reference's op order for its case (file:line in the docstring) so the numerics are the reference's."""
 from __future__ import annotations
 
@@ -18,6 +19,32 @@ def adapter(x: torch.Tensor, down_w, down_b, up_w, up_b, act, keep_z=None) -> to
     if keep_z is not None:
         keep_z(z)
     return F.linear(z, up_w.to(x.dtype), None if up_b is None else up_b.to(x.dtype))
+
+
+def phm_weight(rule: torch.Tensor, W: torch.Tensor) -> torch.Tensor:
+    """``H [n k, n p]`` with ``H[a k + kk, c p + pp] = sum_i rule[i, a, c] W[i, kk, pp]``: the sum of the n Kronecker products
+    ``rule[i] (x) W[i]`` -- adapters/hypercomplex/layers.py:25-28 with kronecker.py:22-33, contracted over i in the einsum itself."""
+    n, k, p = W.shape
+    return torch.einsum("iac,ikp->akcp", rule, W).reshape(n * k, n * p)
+
+
+def phm_factors(W_left: torch.Tensor, W_right: torch.Tensor) -> torch.Tensor:
+    """the n slices of a factorized W: ``W[i] = W_left[i] @ W_right[i]`` -- adapters/hypercomplex/layers.py:168-169"""
+    return torch.bmm(W_left, W_right)
+
+
+def phm_linear(x: torch.Tensor, rule: torch.Tensor, W: torch.Tensor, b: Optional[torch.Tensor]) -> torch.Tensor:
+    """``x @ H + b`` -- adapters/hypercomplex/layers.py:30-33"""
+    y = torch.matmul(x, phm_weight(rule, W).to(x.dtype))
+    return y if b is None else y + b.to(x.dtype)
+
+
+def phm_adapter(x: torch.Tensor, rule_d, W_d, b_d, rule_u, W_u, b_u, act, keep_z=None) -> torch.Tensor:
+    """``up(act(down(x)))`` with both projections PHM layers -- adapters/adapter_modeling.py:134-139"""
+    z = act(phm_linear(x, rule_d, W_d, b_d))
+    if keep_z is not None:
+        keep_z(z)
+    return phm_linear(z, rule_u, W_u, b_u)
 
 
 def adapter_gate(x1: Optional[torch.Tensor], x2: torch.Tensor, down_ws: Sequence[torch.Tensor], down_bs: Sequence[torch.Tensor],

@@ -948,3 +948,71 @@ def lora_delta(x, base, lora_a, lora_b, pk: PackedPair, scaling: float, keep=Non
         out = _empty_result(base, [lora_a, lora_b])
         return (out, torch.empty(x.shape, dtype=torch.uint8, device=x.device)) if return_mask else out
     return _LoraDeltaFn.apply(x, base, pk, scaling, keep, p, seed, return_mask, lora_a, lora_b, link)
+
+
+# ---- Compacter: the weights of one adapter's (down, up) pair of PHM layers, generated by csrc/phm.hip
+PHM_MAX_DIVISION = 8       # the kernels take 1 <= n <= 8 (include/vlpet_hip.h); other divisions run eager.phm_weight
+PHM_CALLS = 0              # expansion launches issued (tests assert on it; a replayed graph does not count)
+
+
+def phm_expand_pair_into(rule_d, W_d, rule_u, W_u, n: int, out=None):
+    """``(wt_d [r, d], wt_u [d, r])`` = (H_down^T, H_up^T) in the parameters' dtype, one launch, no autograd.  ``out``: an earlier
+    result of the same geometry to refresh IN PLACE (its buffers may be baked into a captured graph, as for ``pack_pair(out=)``)."""
+    global PHM_CALLS
+    lib = _lib.load()
+    ts = [t.detach() for t in (rule_d, W_d, rule_u, W_u)]
+    _need_cuda(*ts)
+    ts = [t if t.is_contiguous() else t.contiguous() for t in ts]
+    if len({t.dtype for t in ts}) != 1:
+        raise RuntimeError("vl-pet_amd: mixed parameter dtypes in one PHM pair")
+    n = int(n)
+    d, r = n * W_d.shape[1], n * W_d.shape[2]
+    if tuple(W_u.shape) != (n, r // n, d // n) or tuple(rule_d.shape) != (n, n, n) or tuple(rule_u.shape) != (n, n, n):
+        raise RuntimeError(f"vl-pet_amd: PHM pair shapes {tuple(rule_d.shape)}, {tuple(W_d.shape)}, {tuple(rule_u.shape)}, "
+                           f"{tuple(W_u.shape)} do not belong to one adapter with n = {n}")
+    ok = (out is not None and out[0].shape == (r, d) and out[1].shape == (d, r) and out[0].dtype == ts[1].dtype
+          and out[1].dtype == ts[1].dtype and out[0].device == ts[1].device and out[1].device == ts[1].device)
+    wt_d, wt_u = out if ok else (torch.empty(r, d, dtype=ts[1].dtype, device=ts[1].device),
+                                 torch.empty(d, r, dtype=ts[1].dtype, device=ts[1].device))
+    rc = _timed("phm_fwd", d, lambda: lib.vlpet_phm_expand_pair_fwd(
+        ts[0].data_ptr(), ts[1].data_ptr(), ts[2].data_ptr(), ts[3].data_ptr(), wt_d.data_ptr(), wt_u.data_ptr(), d, r, n,
+        _param_dtype(ts[1]), _stream()))
+    _lib.check(rc, "vlpet_phm_expand_pair_fwd")
+    PHM_CALLS += 1
+    return wt_d, wt_u
+
+
+class _PhmExpandPairFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rule_d, W_d, rule_u, W_u, n):
+        ctx.save_for_backward(rule_d, W_d, rule_u, W_u)
+        ctx.n = int(n)
+        return phm_expand_pair_into(rule_d, W_d, rule_u, W_u, n)
+
+    @staticmethod
+    def backward(ctx, dwt_d, dwt_u):
+        lib = _lib.load()
+        rule_d, W_d, rule_u, W_u = (t.detach() if t.is_contiguous() else t.detach().contiguous() for t in ctx.saved_tensors)
+        n = ctx.n
+        d, r = n * W_d.shape[1], n * W_d.shape[2]
+        f32 = dict(dtype=torch.float32, device=W_d.device)
+        # K2 / K1 hand the gradients of non-leaf weights back as fresh fp32 tensors (_grad_dest finds no sink); an unused output has none
+        g_d = torch.zeros(r, d, **f32) if dwt_d is None else dwt_d.float().contiguous()
+        g_u = torch.zeros(d, r, **f32) if dwt_u is None else dwt_u.float().contiguous()
+        drule_d, drule_u = torch.empty(n, n, n, **f32), torch.empty(n, n, n, **f32)       # (a shared rule: autograd sums the two)
+        (dW_d, s0), (dW_u, s1) = _grad_dest(ctx.saved_tensors[1], W_d.shape), _grad_dest(ctx.saved_tensors[3], W_u.shape)
+        nws = lib.vlpet_phm_workspace_bytes(d, r, n)
+        ws = torch.empty(nws, dtype=torch.uint8, device=W_d.device)
+        rc = _timed("phm_bwd", d, lambda: lib.vlpet_phm_expand_pair_bwd(
+            g_d.data_ptr(), g_u.data_ptr(), rule_d.data_ptr(), W_d.data_ptr(), rule_u.data_ptr(), W_u.data_ptr(), drule_d.data_ptr(),
+            dW_d.data_ptr(), drule_u.data_ptr(), dW_u.data_ptr(), ws.data_ptr(), nws, d, r, n, _param_dtype(W_d), _stream()))
+        _lib.check(rc, "vlpet_phm_expand_pair_bwd")
+        gW = _finish([(dW_d, s0, W_d), (dW_u, s1, W_u)])
+        return _grad_like(drule_d, rule_d), gW[0], _grad_like(drule_u, rule_u), gW[1], None
+
+
+def phm_expand_pair(rule_d, W_d, rule_u, W_u, n: int):
+    """``(wt_d, wt_u)``: the nn.Linear-layout weights of a Compacter adapter's down and up PHM layers (rule [n, n, n]; W_d
+    [n, d / n, r / n], W_u [n, r / n, d / n]; one dtype, fp32 or bf16), differentiable in all four.  They go to ``parallel_adapter`` /
+    ``adapter_gate`` as ``wd`` / ``wu``.  A rule shared by both layers is the same tensor passed twice."""
+    return _PhmExpandPairFn.apply(rule_d, W_d, rule_u, W_u, n)

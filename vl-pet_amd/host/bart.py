@@ -31,12 +31,13 @@ from .. import attention as A
 from .. import decode as D
 from .. import functional as VF
 from .. import adapter_tail as AT
-from ..adapters import AdapterConfig, AdapterController
+from ..adapters import AdapterController
 from ..encoder_pet import apply_pet, build_pet, has_pet
 from ..lora import LoRALinearController, LoraConfig
 from ..visual import Downsample, LowRankVisualEmbedding, VisualEmbedding
-from .common import (check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail, is_key_mask, sequential_adapters,
-                     shift_right, unpack_vis_inputs, value_parallel_adapter)
+from .common import (COMPACTER_DEFAULTS, check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail,
+                     install_shared_phm_rule, is_key_mask, make_adapter_config, sequential_adapters, shift_right, unpack_vis_inputs,
+                     value_parallel_adapter)
 
 TASKS = ["vqa", "gqa", "nlvr", "caption"]
 
@@ -73,6 +74,7 @@ def vlpet_config(**over) -> SimpleNamespace:
         use_lora=False, lora_dim=4, lora_alpha=32, lora_dropout=0.1, use_single_lora=False, reduction_factor=8,
         use_encoder_multihead_up_zero_init=False, use_encoder_gating_large_x_lowrank_up_zero_init=False,
         use_decoder_enc_vpa_up_zero_init=False, freeze_vis_emb=False,
+        **COMPACTER_DEFAULTS,
     )
     for k, v in over.items():
         if not hasattr(c, k):
@@ -81,11 +83,8 @@ def vlpet_config(**over) -> SimpleNamespace:
     check_sequential_adapter_flags(c)
     task_list = [t for t in c.tasks.replace(" ", ",").split(",") if t]
     c.task_list = task_list
-    if c.use_adapter or c.use_decoder_enc_attn_value_parallel_adapter_down_dim:
-        c.adapter_config = AdapterConfig(
-            tasks=task_list, input_dim=c.d_model, d_model=c.d_model, use_single_adapter=c.use_single_adapter,
-            reduction_factor=c.reduction_factor, use_adapter_down_dim=bool(c.use_adapter_down_dim),
-            adapter_down_dim=c.adapter_down_dim)
+    if c.use_adapter or c.use_compacter or c.use_decoder_enc_attn_value_parallel_adapter_down_dim:
+        c.adapter_config = make_adapter_config(c, task_list)
     else:
         c.adapter_config = None
     c.lora_config = LoraConfig(lora_dim=c.lora_dim, lora_alpha=c.lora_alpha, lora_dropout=c.lora_dropout,
@@ -134,8 +133,7 @@ def _adapter_then_tail(ctl, task, residual, h, norm, p, training, gemm_link=None
     ad = fused_adapter_tail(FUSE_ADAPTER_TAIL, ctl, task, h, residual, norm, p, training)
     if ad is not None:
         scale = float(ctl.config.scaling_factor) if ctl.config.use_scaling_factor else 1.0
-        return AT.adapter_tail(h, residual, ad.down_sampler.weight, ad.down_sampler.bias, ad.up_sampler.weight, ad.up_sampler.bias,
-                               norm, scale)
+        return AT.adapter_tail(h, residual, *ad.tail_weights(), norm, scale)
     return _tail_linked(residual, ctl(h, task), norm, p, training, gemm_link)
 
 
@@ -654,6 +652,7 @@ class VLBart(nn.Module):
         self.config = config
         self.model = VLBartModel(config)
         self.register_buffer("final_logits_bias", torch.zeros(1, config.vocab_size))
+        install_shared_phm_rule(self, [self.model], config.adapter_config)        # (Compacter with shared_phm_rule)
         self.apply(self._init_weights)
         # derived copies of frozen tensors (fused q|k|v, padded LM head, fp32 norms) must not outlive a checkpoint load
         self.register_load_state_dict_post_hook(lambda module, incompatible: VF.invalidate_caches())

@@ -8,7 +8,7 @@ import copy
 import torch
 
 from .. import functional as VF
-from ..adapters import AdapterController
+from ..adapters import AdapterConfig, AdapterController
 
 
 def derived_weights(owner, slot, mods, dtype):
@@ -45,38 +45,87 @@ GATE_FLAGS = ("use_encoder_adapter_gating_large_x_lowrank", "use_encoder_adapter
 
 
 def sequential_adapters(config, side: str) -> bool:
-    """``side`` = "encoder" | "decoder": the Single-Adapter placement -- an AdapterController behind every attention and feed-forward
-    block of that stack (my_transformers/modeling_bart.py:932, 1525; modeling_t5.py:307, 350, 701, 744, 847)"""
-    return bool(config.use_adapter) and not getattr(config, f"no_{side}_adapter")
+    """``side`` = "encoder" | "decoder": the Single-Adapter / Compacter placement -- an AdapterController behind every attention and
+    feed-forward block of that stack (my_transformers/modeling_bart.py:932, 1525; modeling_t5.py:307, 350, 701, 744, 847)"""
+    return bool(config.use_adapter or getattr(config, "use_compacter", False)) and not getattr(config, f"no_{side}_adapter")
+
+
+# the Compacter flags of both hosts (param.py:148-170, defaults as there; scripts/*/single_compacter.sh sets division 2, no shared rule,
+# no factorization)
+COMPACTER_DEFAULTS = dict(use_compacter=False, hypercomplex_division=4, phm_rank=1, shared_phm_rule=True, factorized_phm=True,
+                          phm_init_range=0.01, shared_phm_rule_over_tasks=False)
+
+
+def make_adapter_config(c, task_list) -> AdapterConfig:
+    """the ``adapter_config`` of a host config namespace (trainer_base.py:141-178); with ``use_compacter`` the hypercomplex fields"""
+    ac = AdapterConfig(tasks=task_list, input_dim=c.d_model, d_model=c.d_model, use_single_adapter=c.use_single_adapter,
+                       reduction_factor=c.reduction_factor, use_adapter_down_dim=bool(c.use_adapter_down_dim),
+                       adapter_down_dim=c.adapter_down_dim)
+    if c.use_compacter:
+        ac.hypercomplex_adapters = True
+        ac.hypercomplex_division, ac.phm_rank, ac.phm_init_range = c.hypercomplex_division, c.phm_rank, c.phm_init_range
+        ac.shared_phm_rule, ac.factorized_phm = bool(c.shared_phm_rule), bool(c.factorized_phm)
+        ac.shared_phm_rule_over_tasks = bool(c.shared_phm_rule_over_tasks)
+    return ac
+
+
+def install_shared_phm_rule(owner, roots, adapter_config) -> None:
+    """``shared_phm_rule``: the model owns ONE rule and hands it to every PHMLinear under ``roots`` (src/modeling_bart.py:1480-1520,
+    src/modeling_t5.py:454-499, with the init ranges used there).  As in the reference the parameter is registered under each layer
+    as well, so the state dict lists it under all those names and ``named_parameters`` once, under the model's."""
+    from ..adapters import PHMLinear
+    ac = adapter_config
+    if ac is None or not ac.hypercomplex_adapters or not ac.shared_phm_rule:
+        return
+    n = ac.hypercomplex_division
+    owner.phm_rule = torch.nn.Parameter(torch.empty(n, n, n), requires_grad=bool(ac.learn_phm))
+    with torch.no_grad():
+        if ac.phm_c_init == "normal":
+            owner.phm_rule.normal_(mean=0, std=ac.phm_init_range)
+        elif ac.phm_c_init == "uniform":
+            owner.phm_rule.uniform_(-1, 1)
+        else:
+            raise ValueError(f"phm_c_init {ac.phm_c_init!r}: normal or uniform")
+    for root in roots:
+        for m in root.modules():
+            if isinstance(m, PHMLinear):
+                m.set_phm_rule(owner.phm_rule)
 
 
 def check_sequential_adapter_flags(config) -> None:
     """The launch scripts never combine sequential encoder adapters with the multi-head adapter (K1) or a gate, nor sequential decoder
     adapters with the value-parallel adapter; the reference resolves such a mix by the order of its if / elif chains.  Refused here
-    rather than guessed."""
+    rather than guessed.  More than one adapter kind at once is refused as there (trainer_base.py:125)."""
+    if config.use_adapter and getattr(config, "use_compacter", False):
+        raise ValueError("use_adapter and use_compacter: at most one kind of adapters")
     if sequential_adapters(config, "encoder"):
         clash = [f for f in ("use_encoder_adapter_down_multihead",) + GATE_FLAGS if getattr(config, f, False)]
         if clash:
-            raise ValueError("use_adapter with no_encoder_adapter=False (sequential encoder adapters) cannot be combined with "
+            raise ValueError(f"{_kind(config)} with no_encoder_adapter=False (sequential encoder adapters) cannot be combined with "
                              + ", ".join(clash))
     if sequential_adapters(config, "decoder") and config.use_decoder_enc_attn_value_parallel_adapter_down_dim:
-        raise ValueError("use_adapter with no_decoder_adapter=False (sequential decoder adapters) cannot be combined with "
+        raise ValueError(f"{_kind(config)} with no_decoder_adapter=False (sequential decoder adapters) cannot be combined with "
                          "use_decoder_enc_attn_value_parallel_adapter_down_dim")
 
 
+def _kind(config) -> str:
+    return "use_compacter" if getattr(config, "use_compacter", False) else "use_adapter"
+
+
 def fused_adapter_tail(enabled, ctl, task, h, residual, norm, p, training):
-    """The plain ``Adapter`` of ``ctl`` for ``task`` when "adapter, then tail" may run as the one fused launch
-    (vlpet_amd.adapter_tail), else None: switched on, on the GPU, no dropout, no gradient needed, the fused ``Adapter`` with nothing
-    around it inside the controller, a shape the kernel takes, at most ``ADAPTER_TAIL_MAX_ROWS`` rows."""
+    """The plain ``Adapter`` (or Compacter's ``HyperComplexAdapter``) of ``ctl`` for ``task`` when "adapter, then tail" may run as the
+    one fused launch (vlpet_amd.adapter_tail), else None: switched on, on the GPU, no dropout, no gradient needed, a fused adapter
+    with nothing around it inside the controller, a shape the kernel takes, at most ``ADAPTER_TAIL_MAX_ROWS`` rows.  The caller
+    passes ``ad.tail_weights()`` to the kernel: the parameters themselves, or the cached expanded weights and ``b``."""
     from .. import adapter_tail as AT
-    from ..adapters.adapter_modeling import Adapter
+    from ..adapters.adapter_modeling import Adapter, HyperComplexAdapter
     if not enabled or not h.is_cuda or (training and p > 0):
         return None
     cfg = ctl.config
     if cfg.use_parallel_adapter or ctl.add_layer_norm_before_adapter or ctl.add_layer_norm_after_adapter:
         return None
     ad = ctl.get_adapter(ctl.get_task(task))
-    if type(ad) is not Adapter or ad.eager:
+    if type(ad) not in (Adapter, HyperComplexAdapter) or ad.eager:
         return None
     if torch.is_grad_enabled():
         params = list(ad.parameters()) + ([] if norm is None else list(norm.parameters()))

@@ -24,12 +24,13 @@ from .. import attention as A
 from .. import decode as D
 from .. import functional as VF
 from .. import adapter_tail as AT
-from ..adapters import AdapterConfig, AdapterController
+from ..adapters import AdapterController
 from ..encoder_pet import apply_pet, build_pet, has_pet
 from ..visual import Downsample, T5LayerNorm, VisualEmbedding
 from .bart import TASKS, _linear
-from .common import (check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail, sequential_adapters, shift_right,
-                     unpack_vis_inputs, value_parallel_adapter)
+from .common import (COMPACTER_DEFAULTS, check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail,
+                     install_shared_phm_rule, make_adapter_config, sequential_adapters, shift_right, unpack_vis_inputs,
+                     value_parallel_adapter)
 
 
 # K1's gate and the sublayer tail both read the sublayer input; with a link the tail's backward hands its d/dx1 to K1's
@@ -105,8 +106,7 @@ def _adapter_then_tail(ctl, task, hidden, y, p, training, link, layer):
     ad = fused_adapter_tail(FUSE_ADAPTER_TAIL and sublayer_tail is _HIP_SUBLAYER_TAIL, ctl, task, y, hidden, None, p, training)
     if ad is not None:
         scale = float(ctl.config.scaling_factor) if ctl.config.use_scaling_factor else 1.0
-        return AT.adapter_tail(y, hidden, ad.down_sampler.weight, ad.down_sampler.bias, ad.up_sampler.weight, ad.up_sampler.bias,
-                               None, scale)
+        return AT.adapter_tail(y, hidden, *ad.tail_weights(), None, scale)
     return _tail_linked(hidden, ctl(y, task), p, training, link, layer=layer)
 
 
@@ -172,6 +172,7 @@ def vlt5_config(**over) -> SimpleNamespace:
         use_lora=False, reduction_factor=8,
         use_encoder_multihead_up_zero_init=True, use_encoder_gating_large_x_lowrank_up_zero_init=True,
         use_decoder_enc_vpa_up_zero_init=True, freeze_vis_emb=False,
+        **COMPACTER_DEFAULTS,
     )
     for k, v in over.items():
         if not hasattr(c, k):
@@ -179,10 +180,7 @@ def vlt5_config(**over) -> SimpleNamespace:
         setattr(c, k, v)
     check_sequential_adapter_flags(c)
     c.task_list = [t for t in c.tasks.replace(" ", ",").split(",") if t]
-    c.adapter_config = AdapterConfig(
-        tasks=c.task_list, input_dim=c.d_model, d_model=c.d_model, use_single_adapter=c.use_single_adapter,
-        reduction_factor=c.reduction_factor, use_adapter_down_dim=bool(c.use_adapter_down_dim),
-        adapter_down_dim=c.adapter_down_dim)
+    c.adapter_config = make_adapter_config(c, c.task_list)
     c.lora_config = None
     return c
 
@@ -620,6 +618,7 @@ class VLT5(nn.Module):
         self.shared = nn.Embedding(config.vocab_size, config.d_model)
         self.encoder = JointEncoder(config, self.shared)
         self.decoder = T5Decoder(config, self.shared)
+        install_shared_phm_rule(self, [self.encoder, self.decoder], config.adapter_config)        # (Compacter with shared_phm_rule)
         self.apply(self._init_weights)
         self.register_load_state_dict_post_hook(lambda module, incompatible: VF.invalidate_caches())   # (see host/bart.py)
 

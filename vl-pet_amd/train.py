@@ -55,8 +55,13 @@ def trainable_names(model: nn.Module, config) -> List[str]:
                     config.use_encoder_adapter_gating_small_xy_cat or
                     config.use_encoder_adapter_gating_middle_xy_add or
                     config.use_encoder_adapter_gating_middle_ia3_add)
-    # the Single-Adapter placement (host.common.sequential_adapters): every AdapterController trains (trainer_base.py:389-393)
-    any_adapter = any_adapter or bool(config.use_adapter and not (config.no_encoder_adapter and config.no_decoder_adapter))
+    # the Single-Adapter / Compacter placement (host.common.sequential_adapters): every AdapterController trains (trainer_base.py:389-393)
+    compacter = bool(getattr(config, "use_compacter", False))
+    any_adapter = any_adapter or bool((config.use_adapter or compacter) and not (config.no_encoder_adapter and config.no_decoder_adapter))
+    # Compacter's rules: a rule shared by the whole model is a parameter of every AdapterController there, listed once under the model's
+    # own name "phm_rule"; with learn_phm off the rules stay frozen (AdapterController.enable_adapters)
+    ac = getattr(config, "adapter_config", None)
+    learn_phm = bool(getattr(ac, "learn_phm", True))
     norm_params = set()
     if getattr(config, "unfreeze_layer_norms", False):      # trainer_base.py:375-380: every LayerNorm / T5LayerNorm module, wherever it sits
         from .visual import T5LayerNorm
@@ -73,6 +78,10 @@ def trainable_names(model: nn.Module, config) -> List[str]:
             on = True
         if any_adapter and "adapter" in n:
             on = True
+        if compacter and any_adapter and n == "phm_rule":
+            on = True
+        if compacter and not learn_phm and "phm_rule" in n:
+            on = False
         if on:
             p.requires_grad = True
             names.append(n)
