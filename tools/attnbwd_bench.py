@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """The attention kernels through the C ABI alone (no autograd, no host work between launches): HIP events on the launch stream
-around N back-to-back calls, at the configs[1] / configs[2] shapes.  tools/attnbench.py's "bwd" column is (fwd + bwd) - fwd of
-autograd.grad and bottoms out near 100 us of host time; this is the kernel."""
+around N back-to-back calls, at the configs[1] / configs[2] shapes: the encoder's self-attention of the four tasks, then the decoder's
+self- and cross-attention at the benchmark's target lengths (TARGET_LEN 5 / 5 / 2 / 20: one query block, csrc/attn_bwd_fewq.hip).
+tools/attnbench.py's "bwd" column is (fwd + bwd) - fwd of autograd.grad and bottoms out near 100 us of host time; this is the kernel.
+VLPET_LIB selects the build (vl-pet_amd/_lib.py); with the diagnosis library, VLPET_ATTN_FEWQ=0 keeps the decoder rows on attn_bwd_kernel."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -14,7 +16,9 @@ P = float(os.environ.get("ATTNBENCH_P", "0.1"))
 lib = _lib.load()
 tag = sys.argv[1] if len(sys.argv) > 1 else ""
 SHAPES = [("vqa", 500, 56, 56), ("gqa", 833, 56, 56), ("nlvr", 166, 92, 92), ("caption", 416, 76, 76), ("dec-self", 500, 20, 20),
-          ("dec-cross", 500, 20, 56)]
+          ("dec-cross", 500, 20, 56),
+          ("self-vqa", 500, 5, 5), ("self-gqa", 833, 5, 5), ("self-nlvr", 166, 2, 2), ("self-caption", 416, 20, 20),
+          ("cross-vqa", 500, 5, 56), ("cross-gqa", 833, 5, 56), ("cross-nlvr", 166, 2, 92), ("cross-caption", 416, 20, 76)]
 for name, B, Lq, Lk in SHAPES:
     g = torch.Generator().manual_seed(1)
     mk = lambda L: (torch.randn(B, L, H * 64, generator=g) * 0.5).cuda().bfloat16()
@@ -45,4 +49,4 @@ for name, B, Lq, Lk in SHAPES:
     unit = B * H * 64 * 2 / 1e6                                   # MB per row of tokens
     mb = unit * (3 * Lq + 2 * Lk) + unit * (Lq + 2 * Lk)          # reads q, o, do, k, v; writes dq, dk, dv
     mbf = unit * (2 * Lq + 2 * Lk)                                # forward: reads q, k, v; writes o
-    print(f"attnbwd {tag} {name:9s} B={B} Lq={Lq} Lk={Lk}: bwd {t:7.1f} us ({mb / t:5.2f} TB/s of {mb:4.0f} MB)   fwd {tf:6.1f} us ({mbf / tf:5.2f} TB/s of {mbf:4.0f} MB)")
+    print(f"attnbwd {tag} {name:13s} B={B} Lq={Lq} Lk={Lk}: bwd {t:7.1f} us ({mb / t:5.2f} TB/s of {mb:4.0f} MB)   fwd {tf:6.1f} us ({mbf / tf:5.2f} TB/s of {mbf:4.0f} MB)")

@@ -446,6 +446,10 @@ hipError_t launch_attn(const AttnArgs& a_in, bool bwd, hipStream_t stream) {
             default: return hipErrorInvalidValue;
         }
     }
+    // One query block and no bias (the decoder's self- and cross-attention, 2-20 queries): a wave per pair and every score tile evaluated
+    // once (attn_bwd_fewq.hip) -- here such a call is 2-5 units for four waves with the phase-Q wave repeating the phase-K waves' tiles.
+    // VLPET_ATTN_FEWQ=0 of a diagnosis build keeps those calls on the kernel below.
+    if (a.Lq <= 32 && a.bias == nullptr && vlpet_tuning().attn_fewq != 0) return launch_attn_bwd_fewq(a, stream);
     const int Lqp = (a.Lq + 31) & ~31, Lkp = (a.Lk + 31) & ~31;
     const int units = (Lqp >> 5) + (Lkp >> 5);
     const int occ_env = vlpet_tuning().attn_occ;

@@ -453,6 +453,8 @@ struct AttnArgs {
 };
 size_t attn_lds_bytes(int Lq, int Lk, int bwd);
 hipError_t launch_attn(const AttnArgs& a, bool bwd, hipStream_t stream);
+// the backward of a call with one query block (Lq <= 32) and no bias, a wave per (batch, head) pair (attn_bwd_fewq.hip); launch_attn routes to it
+hipError_t launch_attn_bwd_fewq(const AttnArgs& a, hipStream_t stream);
 // the forward for up to 1,024 keys / queries (attn_long.hip): keys streamed through LDS with an online softmax; thr == 0: no dropout (seed
 // and keep_out are not read); dout, dq / dk / dv and bias_t are never read
 hipError_t launch_attn_long_fwd(const AttnArgs& a, hipStream_t stream);
