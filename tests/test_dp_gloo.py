@@ -70,7 +70,7 @@ def test_two_ranks_equal_one_rank(tmp_path):
 class _SinkLinearFn(torch.autograd.Function):
     """Stands in for the HIP weight-gradient kernels: writes dW / db straight into the parameter's slot of the flat
     buffer when the trainer offers one (first write of the step) and returns None to autograd, exactly like
-    functional._grad_dest / _finish do around the real kernels."""
+    functional.grad_slot / GradSlot.finish do around the real kernels."""
 
     @staticmethod
     def forward(ctx, x, w, b):
@@ -81,11 +81,10 @@ class _SinkLinearFn(torch.autograd.Function):
     def backward(ctx, dy):
         import vlpet_amd.functional as VF
         x, w, b = ctx.saved_tensors
-        (dw, sw), (db, sb) = VF._grad_dest(w, w.shape), VF._grad_dest(b, b.shape)
-        dw.copy_(dy.t() @ x)
-        db.copy_(dy.sum(0))
-        gw, gb = VF._finish([(dw, sw, w), (db, sb, b)])
-        return dy @ w, gw, gb
+        dw, db = VF.grad_slot(w, w.shape), VF.grad_slot(b, b.shape)
+        dw.t.copy_(dy.t() @ x)
+        db.t.copy_(dy.sum(0))
+        return dy @ w, dw.finish(), db.finish()
 
 
 class _SinkNet(torch.nn.Module):

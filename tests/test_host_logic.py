@@ -149,11 +149,12 @@ def test_per_task_parameter_detection():
 def _park_op():
     """A stand-in for K1 / K5 / K2: reads x and y = proj(x), parks its d/dx in the link when that is armed."""
     import torch
+    import vlpet_amd.functional as VF
 
     class Park(torch.autograd.Function):
         @staticmethod
         def forward(ctx, x, y, link, shared):
-            ctx.link = link if (link is not None and link.armed) else None
+            ctx.link = VF.ResidualLink.if_armed(link)
             ctx.shared = shared
             ctx.save_for_backward(x, y)
             return y * x.sum(-1, keepdim=True) + 3.0 * x[..., : y.shape[-1]]
@@ -165,7 +166,7 @@ def _park_op():
             dx = (g * y).sum(-1, keepdim=True).expand_as(x).clone()
             dx[..., : y.shape[-1]] += 3.0 * g
             if ctx.link is not None:
-                ctx.link.dx1, ctx.link.shared = dx, ctx.shared
+                ctx.link.park(dx, shared=ctx.shared)
                 return None, dy, None, None
             return dx, dy, None, None
     return Park
@@ -194,7 +195,7 @@ def test_linear_acc_accumulates_onto_parked_gradient(n_proj, shared):
             out = out + y.tanh()
         out.backward(g)
         if linked:
-            assert link.dx1 is None         # taken
+            assert not link.holds           # taken
         return out.detach(), x.grad
 
     (o1, g1), (o0, g0) = run(True), run(False)

@@ -4,8 +4,7 @@ HIP library is unavailable; there is deliberately no eager fallback."""
 from __future__ import annotations
 
 import ctypes
-import math
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 import torch.nn.functional as F
@@ -323,28 +322,55 @@ def _empty_result(x: torch.Tensor, params) -> torch.Tensor:
     return out
 
 
-def _grad_dest(p: torch.Tensor, shape, block: bool = False):
-    """Where a weight-gradient kernel writes: the parameter's slot of the trainer's flat gradient buffer when it
-    offers one for this step (train.GradSink: first write of the step, fp32, matching shape) -- then autograd
-    gets ``None`` for that input and no accumulate kernel runs -- else a fresh fp32 tensor returned to autograd."""
+class GradSlot:
+    """Where one weight-gradient kernel writes and what autograd gets back for it.  ``t``: the fp32 tensor the kernel fills --
+    the parameter's slot of the trainer's flat gradient buffer (``sunk``) or a fresh tensor.  ``finish()``, called once the
+    launches are enqueued, tells a sink that its slot is written and returns ``None`` (no accumulate kernel runs), else returns
+    the tensor in the parameter's dtype."""
+
+    __slots__ = ("t", "_sink", "_p")
+
+    def __init__(self, t, sink, p):
+        self.t, self._sink, self._p = t, sink, p
+
+    @staticmethod
+    def scratch(shape, device) -> "GradSlot":
+        """A destination nobody owns: the kernel needs somewhere to write, autograd gets nothing."""
+        return GradSlot(torch.empty(*shape, dtype=torch.float32, device=device), None, None)
+
+    @property
+    def ptr(self) -> int:
+        return self.t.data_ptr()
+
+    @property
+    def sunk(self) -> bool:
+        return self._sink is not None
+
+    def finish(self):
+        if self._sink is not None:
+            self._sink.done()
+            return None
+        return None if self._p is None else _grad_like(self.t, self._p)
+
+    def finish_heads(self, params):
+        """The slot holds the row blocks of ``len(params)`` heads stacked (the multi-head down projection): one gradient per head."""
+        if self._sink is not None:
+            self._sink.done()
+            return [None] * len(params)
+        rh = self.t.shape[0] // len(params)
+        return [_grad_like(self.t[i * rh:(i + 1) * rh], p) for i, p in enumerate(params)]
+
+
+def grad_slot(p: torch.Tensor, shape, block: bool = False) -> GradSlot:
+    """The slot for parameter ``p``: its part of the trainer's flat gradient buffer when that offers one for this step
+    (train.GradSink: first write of the step, fp32, matching shape and device), else a fresh fp32 tensor.  ``block``: the
+    sink that spans the stacked heads ``p`` is the first of."""
     sink = getattr(p, "_vlpet_block_sink" if block else "_vlpet_sink", None)
     if sink is not None and tuple(sink.view.shape) == tuple(shape) and sink.view.device == p.device:
         v = sink.take()
         if v is not None:
-            return v, sink
-    return torch.empty(*shape, dtype=torch.float32, device=p.device), None
-
-
-def _finish(dests):
-    """Autograd return values for (tensor, sink, param) triples: None where the kernel wrote into a sink."""
-    out = []
-    for t, sink, p in dests:
-        if sink is not None:
-            sink.done()
-            out.append(None)
-        else:
-            out.append(_grad_like(t, p))
-    return out
+            return GradSlot(v, sink, p)
+    return GradSlot(torch.empty(*shape, dtype=torch.float32, device=p.device), None, p)
 
 
 FANOUT_SUM = True          # A/B switch (tools/ab_switches.py: VLPET_NO_FANOUT_SUM=1): fanout() below
@@ -439,19 +465,58 @@ def cross_key_blocks(x: torch.Tensor, w_all: torch.Tensor, b_all: torch.Tensor, 
 
 
 class ResidualLink:
-    """Hand-over of the residual-stream gradient between the two ops that read the sublayer input x1: the gate of K1 and
-    the sublayer tail LayerNorm(x1 + dropout(y)) (my_transformers/modeling_bart.py:1196, 1259-1261).  Autograd would sum
-    their two contributions to d/dx1 with a separate elementwise pass over [M, d]; with a link the tail's backward (which
-    runs first: its output is downstream of K1's) parks its dx1 here and returns no gradient for x1, and K1's backward
-    adds it inside its kernel (vlpet_adapter_gate_bwd_saved_acc) and returns the sum.  Armed by K1's forward only when its
-    backward will take the hand-over (gated, saved-activation form)."""
+    """Hand-over of an input gradient between two ops that read the same tensor x, one of them downstream of the other's
+    output.  Autograd would sum their two contributions to d/dx with a separate elementwise pass over [M, d].  With a link
+    the upstream op arms it in its forward; the downstream op, whose backward runs first, parks its d/dx (whatever it is the
+    gradient of: the tail's residual add, K1's gate, K2, K3, or a sum that already holds an earlier hand-over) and returns
+    no gradient for x; the upstream op's backward takes it, adds its own inside its kernel or GEMM epilogue and returns the
+    sum.  The first pair was the sublayer tail LayerNorm(x1 + dropout(y)) and the gate of K1
+    (my_transformers/modeling_bart.py:1196, 1259-1261; vlpet_adapter_gate_bwd_saved_acc); DESIGN.md lists them all.
+    An op arms only when its backward will take the hand-over, and parks only in an armed link."""
 
-    __slots__ = ("armed", "dx1", "shared")
+    __slots__ = ("armed", "_grad", "_shared")
 
     def __init__(self):
         self.armed = False
-        self.dx1 = None
-        self.shared = False        # the parked tensor is also somebody else's gradient: a consumer must not write into it
+        self._grad = None
+        self._shared = False       # the parked tensor is also somebody else's gradient: nobody may write into it
+
+    def arm(self) -> "ResidualLink":
+        self.armed = True
+        return self
+
+    @staticmethod
+    def if_armed(link: Optional["ResidualLink"]) -> Optional["ResidualLink"]:
+        """``link`` where a producer may park in it, else None."""
+        return link if (link is not None and link.armed) else None
+
+    @property
+    def holds(self) -> bool:
+        return self._grad is not None
+
+    def park(self, grad: torch.Tensor, shared: bool = False):
+        """``shared``: ``grad`` is also handed to somebody else (autograd's own tensor, or returned for another input)."""
+        if self._grad is not None:
+            raise RuntimeError("vl-pet_amd: a gradient is already parked in this ResidualLink (it would be lost)")
+        self._grad, self._shared = grad, bool(shared)
+
+    def take(self, shape, dtype, writable: bool = False) -> Optional[torch.Tensor]:
+        """The parked gradient as a contiguous ``shape`` / ``dtype`` tensor (None if nothing was parked); the link is empty
+        afterwards.  ``writable``: the caller accumulates into the result in place, so a shared tensor comes back as a copy."""
+        g, shared = self._grad, self._shared
+        self._grad, self._shared = None, False
+        if g is None:
+            return None
+        parked = g
+        if g.shape != shape:
+            g = g.reshape(shape)
+        if g.dtype != dtype:
+            g = g.to(dtype)
+        if not g.is_contiguous():
+            g = g.contiguous()
+        if writable and shared and g.data_ptr() == parked.data_ptr():      # (a repair above already made a private copy)
+            g = g.clone()
+        return g
 
 
 class _LinearAccFn(torch.autograd.Function):
@@ -468,10 +533,7 @@ class _LinearAccFn(torch.autograd.Function):
     def forward(ctx, x, link, *wb):
         n = len(wb) // 2
         ws, bs = wb[:n], wb[n:]
-        ctx.link = None
-        if link is not None and ctx.needs_input_grad[0]:
-            link.armed = True
-            ctx.link = link
+        ctx.link = link.arm() if (link is not None and ctx.needs_input_grad[0]) else None
         ctx.save_for_backward(*ws)
         ctx.xshape = x.shape
         outs = tuple(F.linear(x, w, b) for w, b in zip(ws, bs))
@@ -481,20 +543,9 @@ class _LinearAccFn(torch.autograd.Function):
     def backward(ctx, *dys):
         ws = ctx.saved_tensors
         link, ctx.link = ctx.link, None
-        base = None
-        shared = False
-        if link is not None:
-            base, link.dx1, shared = link.dx1, None, link.shared
-            link.shared = False
-        K = ctx.xshape[-1]
-        acc = None
-        if base is not None:
-            if base.dtype == ws[0].dtype and base.is_contiguous() and base.numel() == math.prod(ctx.xshape):
-                acc = base.view(-1, K)
-                if shared:
-                    acc = acc.clone()
-            else:                       # (never on the product path: kept correct rather than fast)
-                acc = base.reshape(-1, K).to(ws[0].dtype).contiguous()
+        acc = link.take(ctx.xshape, ws[0].dtype, writable=True) if link is not None else None
+        if acc is not None:
+            acc = acc.view(-1, ctx.xshape[-1])
         for dy, w in zip(dys, ws):
             if dy is None:
                 continue
@@ -528,10 +579,8 @@ class _LinearTrainBiasFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, b, link=None):
-        ctx.link = None
-        if link is not None and ctx.needs_input_grad[0]:
-            link.armed = True           # K3's delta on this projection (same x, downstream of this output) parks its d/dx
-            ctx.link = link
+        # (K3's delta on this projection -- same x, downstream of this output -- parks its d/dx)
+        ctx.link = link.arm() if (link is not None and ctx.needs_input_grad[0]) else None
         ctx.save_for_backward(w, b)
         return F.linear(x, w, io_view(b, x.dtype))
 
@@ -546,31 +595,27 @@ class _LinearTrainBiasFn(torch.autograd.Function):
         dx = None
         link, ctx.link = ctx.link, None
         if ctx.needs_input_grad[0]:
-            base = None
-            if link is not None:
-                base, link.dx1, shared = link.dx1, None, link.shared
-                link.shared = False
-                if base is not None and (shared or base.dtype != w.dtype or not base.is_contiguous()):
-                    base = base.to(w.dtype).contiguous().clone() if shared else base.to(w.dtype).contiguous()
+            xshape = (*dy.shape[:-1], w.shape[1])
+            base = link.take(xshape, w.dtype, writable=True) if link is not None else None
             if base is not None:
-                dx = base.view(-1, w.shape[1]).addmm_(dy2, w).view(*dy.shape[:-1], w.shape[1])      # C += dY W in the GEMM epilogue
+                dx = base.view(-1, w.shape[1]).addmm_(dy2, w).view(xshape)      # C += dY W in the GEMM epilogue
             else:
-                dx = (dy2 @ w).view(*dy.shape[:-1], w.shape[1])
+                dx = (dy2 @ w).view(xshape)
         db = None
         if ctx.needs_input_grad[2]:
             M = dy2.shape[0]
-            (t, sink) = _grad_dest(b, (n,))
+            slot = grad_slot(b, (n,))
             nb = lib.vlpet_sublayer_tail_partials(M)
             ws = torch.empty(nb * n, dtype=torch.float32, device=dy2.device)
-            if DEFER_REDUCES and sink is not None:       # pass 1 now, the reduction with the step's other ones (flush_reduces)
+            if DEFER_REDUCES and slot.sunk:       # pass 1 now, the reduction with the step's other ones (flush_reduces)
                 rc = lib.vlpet_colsum_partial(dy2.data_ptr(), M, n, ws.data_ptr(), _io_dtype(dy2), _stream())
                 _lib.check(rc, "vlpet_colsum_partial")
-                tf = t.reshape(-1)
+                tf = slot.t.reshape(-1)
                 reduce_partials(ws, nb, n // 2, tf[:n // 2], tf[n // 2:], True)
             else:
-                rc = lib.vlpet_colsum(dy2.data_ptr(), M, n, ws.data_ptr(), t.data_ptr(), _io_dtype(dy2), _stream())
+                rc = lib.vlpet_colsum(dy2.data_ptr(), M, n, ws.data_ptr(), slot.ptr, _io_dtype(dy2), _stream())
                 _lib.check(rc, "vlpet_colsum")
-            db = _finish([(t, sink, b)])[0]
+            db = slot.finish()
         return dx, None, db, None
 
 
@@ -628,12 +673,10 @@ class _AdapterGateFn(torch.autograd.Function):
                 io, _stream()))
         _lib.check(rc, "vlpet_adapter_gate_fwd")
         ctx.act = act
-        ctx.link = None
-        if link is not None and act is not None and gate_mode != GATE_NONE and x1.requires_grad:
-            link.armed = True                   # the tail that follows may park its dx1 for this op's backward
-            ctx.link = link
+        # the tail that follows may park its d/dx1 for this op's backward
+        ctx.link = link.arm() if (link is not None and act is not None and gate_mode != GATE_NONE and x1.requires_grad) else None
         # the other direction: the sublayer's first GEMM (upstream of x2) armed `out_link` -- this backward parks d/dx1 there
-        ctx.out_link = out_link if (out_link is not None and out_link.armed and gate_mode != GATE_NONE) else None
+        ctx.out_link = ResidualLink.if_armed(out_link) if gate_mode != GATE_NONE else None
         # the multiplicative gate's backward can start from this output (dq = dy * y * (1 - g): csrc/pet_dz2.hip "YF").  Keeping it is
         # NOT free: the sublayer tail that consumes it saves its own output / pre-norm sum, not y, so one more [M, d] tensor of
         # the IO dtype lives from this forward to its backward -- 12 of them in a BART-base encoder, 24 in T5-base (43 MB each at 28,000
@@ -662,32 +705,26 @@ class _AdapterGateFn(torch.autograd.Function):
         r = pk_a.r
         rg = pk_g.r if gate else 0
         nh2 = 2 * n_heads
-        (dwd, s_wd), (dbd, s_bd) = _grad_dest(params[0], (r, d), block=True), _grad_dest(params[n_heads], (r,), block=True)
-        (dwu, s_wu), (dbu, s_bu) = _grad_dest(params[nh2], (d, r)), _grad_dest(params[nh2 + 1], (d,))
-        dwgd = dbgd = dwgu = dbgu = None
+        # down w (the heads stacked), down b, up w, up b, then the gate's four (None without a gate)
+        slots = [grad_slot(params[0], (r, d), block=True), grad_slot(params[n_heads], (r,), block=True),
+                 grad_slot(params[nh2], (d, r)), grad_slot(params[nh2 + 1], (d,))]
         if gate:
-            (dwgd, s_gd), (dbgd, s_gdb) = _grad_dest(params[nh2 + 2], (rg, d)), _grad_dest(params[nh2 + 3], (rg,))
-            (dwgu, s_gu), (dbgu, s_gub) = _grad_dest(params[nh2 + 4], (d, rg)), _grad_dest(params[nh2 + 5], (d,))
+            slots += [grad_slot(params[nh2 + 2], (rg, d)), grad_slot(params[nh2 + 3], (rg,)),
+                      grad_slot(params[nh2 + 4], (d, rg)), grad_slot(params[nh2 + 5], (d,))]
         dx2 = torch.empty_like(x2f)
         dx1 = torch.empty_like(x2f) if gate else None
         nws = lib.vlpet_bwd_workspace_bytes(M, d, pk_a.tiles, int(gate), io)
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
         args = (dyf.data_ptr(), _ptr(x1f) if gate else None, x2f.data_ptr(),
                 pk_a.buf.data_ptr(), pk_g.buf.data_ptr() if gate else None, _ptr(dx1), dx2.data_ptr(),
-                dwd.data_ptr(), dbd.data_ptr(), dwu.data_ptr(), dbu.data_ptr(),
-                _ptr(dwgd), _ptr(dbgd), _ptr(dwgu), _ptr(dbgu), r, rg,
+                *(s.ptr for s in slots), *((None,) * (8 - len(slots))), r, rg,
                 ws.data_ptr(), nws, M, d, pk_a.tiles, gate_mode, sd, s2, gs, io, _stream())
-        sinks = [s_wd, s_bd, s_wu, s_bu] + ([s_gd, s_gdb, s_gu, s_gub] if gate else [])
-        side = WGRAD_STREAM if all(s is not None for s in sinks) else None
+        side = WGRAD_STREAM if all(s.sunk for s in slots) else None
         act = ctx.act
 
         # the sublayer tail's residual-stream gradient, if it was handed over (ResidualLink): summed inside the kernel
-        dx1_in = None
-        if ctx.link is not None and ctx.link.dx1 is not None:
-            dx1_in, ctx.link.dx1 = ctx.link.dx1, None
-            if dx1_in.shape != x2f.shape or dx1_in.dtype != x2f.dtype or not dx1_in.is_contiguous():
-                dx1_in = dx1_in.reshape(x2f.shape).to(x2f.dtype).contiguous()
-        ctx.link = None
+        link, ctx.link = ctx.link, None
+        dx1_in = link.take(x2f.shape, x2f.dtype) if link is not None else None
 
         def phase(ph, a):       # one or both halves of the backward, with or without the forward's saved activations
             if K1_BWD_FINALIZE_LAUNCH:
@@ -737,27 +774,12 @@ class _AdapterGateFn(torch.autograd.Function):
         if not gate:
             # without a gate the kernel returns the adapter-branch gradient only; add the residual path
             dx2 = dx2 + s2 * dyf
-        rh = r // n_heads
-        grads: List[Optional[torch.Tensor]] = []
-        if s_wd is not None:
-            s_wd.done()
-            grads += [None] * n_heads
-        else:
-            grads += [_grad_like(dwd[i * rh:(i + 1) * rh], params[i]) for i in range(n_heads)]
-        if s_bd is not None:
-            s_bd.done()
-            grads += [None] * n_heads
-        else:
-            grads += [_grad_like(dbd[i * rh:(i + 1) * rh], params[n_heads + i]) for i in range(n_heads)]
-        grads += _finish([(dwu, s_wu, params[nh2]), (dbu, s_bu, params[nh2 + 1])])
-        if gate:
-            grads += _finish([(dwgd, s_gd, params[nh2 + 2]), (dbgd, s_gdb, params[nh2 + 3]),
-                              (dwgu, s_gu, params[nh2 + 4]), (dbgu, s_gub, params[nh2 + 5])])
+        grads = slots[0].finish_heads(params[:n_heads]) + slots[1].finish_heads(params[n_heads:nh2]) + [s.finish() for s in slots[2:]]
         gx1 = dx1.view(shp1) if gate else None
-        if ctx.out_link is not None:        # the dgrad GEMM of the sublayer's first projection accumulates onto it (_LinearAccFn)
-            ctx.out_link.dx1, ctx.out_link.shared = gx1, False
+        out_link, ctx.out_link = ctx.out_link, None
+        if out_link is not None:        # the dgrad GEMM of the sublayer's first projection accumulates onto it (_LinearAccFn)
+            out_link.park(gx1)
             gx1 = None
-            ctx.out_link = None
         return (gx1, dx2.view(shp2), None, None, None, None, None, None, None, None, None, *grads)
 
 
@@ -786,7 +808,7 @@ class _ParallelAdapterFn(torch.autograd.Function):
     def forward(ctx, x, y, pk, scale, link, wd, bd, wu, bu):
         lib = _lib.load()
         _need_cuda(x, y)
-        ctx.link = link if (link is not None and link.armed and ctx.needs_input_grad[0]) else None
+        ctx.link = ResidualLink.if_armed(link) if ctx.needs_input_grad[0] else None
         d = x.shape[-1]
         io = _io_dtype(x)
         xf, yf = _flat(x, d), _flat(y, d)
@@ -815,33 +837,31 @@ class _ParallelAdapterFn(torch.autograd.Function):
         M, d = xf.shape
         io = _io_dtype(xf)
         dyf = _flat(dy, d)
-        f32 = dict(dtype=torch.float32, device=xf.device)
         r = pk.r
-        (dwd, s0), (dbd, s1), (dwu, s2) = _grad_dest(wd, (r, d)), _grad_dest(bd, (r,)), _grad_dest(wu, (d, r))
         # bu is None when the up bias belongs to another half of a split bottleneck (encoder_pet._apply_pet_split)
-        (dbu, s3) = _grad_dest(bu, (d,)) if bu is not None else (torch.empty(d, dtype=torch.float32, device=xf.device), None)
+        dwd, dbd, dwu, dbu = (grad_slot(wd, (r, d)), grad_slot(bd, (r,)), grad_slot(wu, (d, r)),
+                              grad_slot(bu, (d,)) if bu is not None else GradSlot.scratch((d,), xf.device))
         dx = torch.empty_like(xf)
         nws = lib.vlpet_bwd_workspace_bytes(M, d, pk.tiles, 0, io)
         ws = torch.empty(nws, dtype=torch.uint8, device=xf.device)
         act = ctx.act
         if act is not None:
             rc = _timed("k2_bwd", M, lambda: lib.vlpet_parallel_adapter_bwd_saved(
-                dyf.data_ptr(), xf.data_ptr(), act.data_ptr(), pk.buf.data_ptr(), dx.data_ptr(), dwd.data_ptr(), dbd.data_ptr(),
-                dwu.data_ptr(), dbu.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io, _stream()))
+                dyf.data_ptr(), xf.data_ptr(), act.data_ptr(), pk.buf.data_ptr(), dx.data_ptr(), dwd.ptr, dbd.ptr,
+                dwu.ptr, dbu.ptr, r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io, _stream()))
         else:
             rc = _timed("k2_bwd", M, lambda: lib.vlpet_parallel_adapter_bwd(
-                dyf.data_ptr(), xf.data_ptr(), pk.buf.data_ptr(), dx.data_ptr(), dwd.data_ptr(), dbd.data_ptr(),
-                dwu.data_ptr(), dbu.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io, _stream()))
+                dyf.data_ptr(), xf.data_ptr(), pk.buf.data_ptr(), dx.data_ptr(), dwd.ptr, dbd.ptr,
+                dwu.ptr, dbu.ptr, r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io, _stream()))
         ctx.act = None
         _lib.check(rc, "vlpet_parallel_adapter_bwd")
-        gw = _finish([(dwd, s0, wd), (dbd, s1, bd), (dwu, s2, wu)])
-        gbu = _finish([(dbu, s3, bu)])[0] if bu is not None else None
+        grads = [s.finish() for s in (dwd, dbd, dwu, dbu)]
         gx = dx.view(ctx.shape)
-        if ctx.link is not None:        # the projection that made `y` from the same `x` accumulates its dgrad onto dx (_LinearAccFn)
-            ctx.link.dx1, ctx.link.shared = gx, False
+        link, ctx.link = ctx.link, None
+        if link is not None:        # the projection that made `y` from the same `x` accumulates its dgrad onto dx (_LinearAccFn)
+            link.park(gx)
             gx = None
-            ctx.link = None
-        return (gx, dy, None, None, None, *gw, gbu)
+        return (gx, dy, None, None, None, *grads)
 
 
 def parallel_adapter(x, y, wd, bd, wu, bu, pk: PackedPair, scale: float = 1.0, link: Optional[ResidualLink] = None):
@@ -864,7 +884,7 @@ class _LoraDeltaFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, base, pk, scaling, keep, p, seed, want_mask, lora_a, lora_b, link=None):
         # (`link`: armed by the frozen projection that produced `base` from the same x -- its dgrad GEMM takes over d/dx)
-        ctx.link = link if (link is not None and link.armed and ctx.needs_input_grad[0]) else None
+        ctx.link = ResidualLink.if_armed(link) if ctx.needs_input_grad[0] else None
         lib = _lib.load()
         _need_cuda(x, base)
         d = x.shape[-1]
@@ -918,7 +938,7 @@ class _LoraDeltaFn(torch.autograd.Function):
         io = _io_dtype(xf)
         dyf = _flat(dy, d)
         r = pk.r
-        (da, s0), (db, s1) = _grad_dest(lora_a, (r, d)), _grad_dest(lora_b, (d, r))
+        da, db = grad_slot(lora_a, (r, d)), grad_slot(lora_b, (d, r))
         dx = torch.empty_like(xf)
         nws = lib.vlpet_bwd_workspace_bytes(M, d, pk.tiles, 0, io)
         ws = torch.empty(nws, dtype=torch.uint8, device=xf.device)
@@ -926,19 +946,19 @@ class _LoraDeltaFn(torch.autograd.Function):
         if act is not None:
             rc = _timed("k3_bwd", M, lambda: lib.vlpet_lora_delta_bwd_saved(
                 dyf.data_ptr(), xf.data_ptr(), act.data_ptr(), pk.buf.data_ptr(), _ptr(ctx.keep), p, seed, dx.data_ptr(),
-                da.data_ptr(), db.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io, _stream()))
+                da.ptr, db.ptr, r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io, _stream()))
         else:
             rc = _timed("k3_bwd", M, lambda: lib.vlpet_lora_delta_bwd(
-                dyf.data_ptr(), xf.data_ptr(), pk.buf.data_ptr(), _ptr(ctx.keep), p, seed, dx.data_ptr(), da.data_ptr(),
-                db.data_ptr(), r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io, _stream()))
+                dyf.data_ptr(), xf.data_ptr(), pk.buf.data_ptr(), _ptr(ctx.keep), p, seed, dx.data_ptr(), da.ptr,
+                db.ptr, r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io, _stream()))
         ctx.act = None
         _lib.check(rc, "vlpet_lora_delta_bwd")
         gx = dx.view(shape)
-        if ctx.link is not None:
-            ctx.link.dx1, ctx.link.shared = gx, False
+        link, ctx.link = ctx.link, None
+        if link is not None:
+            link.park(gx)
             gx = None
-            ctx.link = None
-        return (gx, dy, None, None, None, None, None, None, *_finish([(da, s0, lora_a), (db, s1, lora_b)]), None)
+        return (gx, dy, None, None, None, None, None, None, da.finish(), db.finish(), None)
 
 
 def lora_delta(x, base, lora_a, lora_b, pk: PackedPair, scaling: float, keep=None, p: float = 0.0, seed: int = 0,
@@ -996,19 +1016,19 @@ class _PhmExpandPairFn(torch.autograd.Function):
         n = ctx.n
         d, r = n * W_d.shape[1], n * W_d.shape[2]
         f32 = dict(dtype=torch.float32, device=W_d.device)
-        # K2 / K1 hand the gradients of non-leaf weights back as fresh fp32 tensors (_grad_dest finds no sink); an unused output has none
+        # K2 / K1 hand the gradients of non-leaf weights back as fresh fp32 tensors (grad_slot finds no sink); an unused output has none
         g_d = torch.zeros(r, d, **f32) if dwt_d is None else dwt_d.float().contiguous()
         g_u = torch.zeros(d, r, **f32) if dwt_u is None else dwt_u.float().contiguous()
         drule_d, drule_u = torch.empty(n, n, n, **f32), torch.empty(n, n, n, **f32)       # (a shared rule: autograd sums the two)
-        (dW_d, s0), (dW_u, s1) = _grad_dest(ctx.saved_tensors[1], W_d.shape), _grad_dest(ctx.saved_tensors[3], W_u.shape)
+        dW_d, dW_u = grad_slot(ctx.saved_tensors[1], W_d.shape), grad_slot(ctx.saved_tensors[3], W_u.shape)
         nws = lib.vlpet_phm_workspace_bytes(d, r, n)
         ws = torch.empty(nws, dtype=torch.uint8, device=W_d.device)
         rc = _timed("phm_bwd", d, lambda: lib.vlpet_phm_expand_pair_bwd(
             g_d.data_ptr(), g_u.data_ptr(), rule_d.data_ptr(), W_d.data_ptr(), rule_u.data_ptr(), W_u.data_ptr(), drule_d.data_ptr(),
-            dW_d.data_ptr(), drule_u.data_ptr(), dW_u.data_ptr(), ws.data_ptr(), nws, d, r, n, _param_dtype(W_d), _stream()))
+            dW_d.ptr, drule_u.data_ptr(), dW_u.ptr, ws.data_ptr(), nws, d, r, n, _param_dtype(W_d), _stream()))
         _lib.check(rc, "vlpet_phm_expand_pair_bwd")
-        gW = _finish([(dW_d, s0, W_d), (dW_u, s1, W_u)])
-        return _grad_like(drule_d, rule_d), gW[0], _grad_like(drule_u, rule_u), gW[1], None
+        gW_d, gW_u = dW_d.finish(), dW_u.finish()
+        return _grad_like(drule_d, rule_d), gW_d, _grad_like(drule_u, rule_u), gW_u, None
 
 
 def phm_expand_pair(rule_d, W_d, rule_u, W_u, n: int):

@@ -179,7 +179,8 @@ def sublayer_tail(residual, h, norm, p, training, link=None):
 def _tail_linked(residual, h, norm, p, training, link):
     """K5 whose d/dresidual goes to the sublayer's first dgrad GEMM when that armed ``link`` (the swapped-in eager tail of
     the parity harness takes no link: it is only ever called without one)."""
-    if link is None or not link.armed:
+    link = VF.ResidualLink.if_armed(link)
+    if link is None:
         return sublayer_tail(residual, h, norm, p, training)
     return sublayer_tail(residual, h, norm, p, training, link=link)
 

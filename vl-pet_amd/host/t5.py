@@ -86,10 +86,11 @@ def _fused_tail_ok(layer, y):
 
 def _tail_linked(hidden, y, p, training, link, layer=None):
     nxt = _fused_tail_ok(layer, y) if layer is not None else None
+    link = VF.ResidualLink.if_armed(link)
     if nxt is not None:
         from ..tail import sublayer_tail_rms
-        return sublayer_tail_rms(hidden, y, nxt, p, training, link=link if (link is not None and link.armed) else None)
-    if link is None or not link.armed:
+        return sublayer_tail_rms(hidden, y, nxt, p, training, link=link)
+    if link is None:                # (the swapped-in eager tail of the parity harness takes no link)
         return sublayer_tail(hidden, y, None, p, training)
     return sublayer_tail(hidden, y, None, p, training, link=link)
 

@@ -11,13 +11,13 @@ data: they get no gradient.  No CPU fallback."""
 from __future__ import annotations
 
 import ctypes
-from typing import List, Optional, Sequence
+from typing import Optional, Sequence
 
 import torch
 
 from . import _lib
 from . import functional as Fn
-from .functional import _flat, _grad_dest, _grad_like, _io_dtype, _need_cuda, _param_dtype, _ptr, _stream, _timed
+from .functional import _flat, _grad_like, _io_dtype, _need_cuda, _param_dtype, _ptr, _stream, _timed, grad_slot
 
 
 class LowRankPack:
@@ -150,36 +150,21 @@ class _LowRankProjFn(torch.autograd.Function):
         r = pk_a.r
         rg = pk_g.r if gated else 0
         nh2 = 2 * n_heads
-        (dwd, s_wd), (dbd, s_bd) = _grad_dest(params[0], (r, F_), block=True), _grad_dest(params[n_heads], (r,), block=True)
-        (dwu, s_wu), (dbu, s_bu) = _grad_dest(params[nh2], (d, r)), _grad_dest(params[nh2 + 1], (d,))
-        dwgd = dbgd = dwgu = dbgu = None
+        # down w (the heads stacked), down b, up w, up b, then the gate's four (None without a gate), as in functional._AdapterGateFn
+        slots = [grad_slot(params[0], (r, F_), block=True), grad_slot(params[n_heads], (r,), block=True),
+                 grad_slot(params[nh2], (d, r)), grad_slot(params[nh2 + 1], (d,))]
         if gated:
-            (dwgd, s_gd), (dbgd, s_gdb) = _grad_dest(params[nh2 + 2], (rg, F_)), _grad_dest(params[nh2 + 3], (rg,))
-            (dwgu, s_gu), (dbgu, s_gub) = _grad_dest(params[nh2 + 4], (d, rg)), _grad_dest(params[nh2 + 5], (d,))
+            slots += [grad_slot(params[nh2 + 2], (rg, F_)), grad_slot(params[nh2 + 3], (rg,)),
+                      grad_slot(params[nh2 + 4], (d, rg)), grad_slot(params[nh2 + 5], (d,))]
         nws = lib.vlpet_lowrank_bwd_workspace_bytes(M, F_, d, pk_a.tiles, io)
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
         rc = _timed("f4_bwd", M, lambda: lib.vlpet_lowrank_gate_bwd(
             dfe.data_ptr(), ff.data_ptr(), act.data_ptr(), pk_a.buf.data_ptr(), pk_g.buf.data_ptr() if gated else None,
-            dwd.data_ptr(), dbd.data_ptr(), dwu.data_ptr(), dbu.data_ptr(), _ptr(dwgd), _ptr(dbgd), _ptr(dwgu), _ptr(dbgu),
+            *(sl.ptr for sl in slots), *((None,) * (8 - len(slots))),
             r, rg, ws.data_ptr(), nws, M, F_, d, pk_a.tiles, gate_residual, io, _stream()))
         ctx.act = None
         _lib.check(rc, "vlpet_lowrank_gate_bwd")
-        rh = r // n_heads
-        grads: List[Optional[torch.Tensor]] = []
-        if s_wd is not None:
-            s_wd.done()
-            grads += [None] * n_heads
-        else:
-            grads += [_grad_like(dwd[i * rh:(i + 1) * rh], params[i]) for i in range(n_heads)]
-        if s_bd is not None:
-            s_bd.done()
-            grads += [None] * n_heads
-        else:
-            grads += [_grad_like(dbd[i * rh:(i + 1) * rh], params[n_heads + i]) for i in range(n_heads)]
-        grads += Fn._finish([(dwu, s_wu, params[nh2]), (dbu, s_bu, params[nh2 + 1])])
-        if gated:
-            grads += Fn._finish([(dwgd, s_gd, params[nh2 + 2]), (dbgd, s_gdb, params[nh2 + 3]),
-                                 (dwgu, s_gu, params[nh2 + 4]), (dbgu, s_gub, params[nh2 + 5])])
+        grads = slots[0].finish_heads(params[:n_heads]) + slots[1].finish_heads(params[n_heads:nh2]) + [sl.finish() for sl in slots[2:]]
         grads += [_grad_like(s[0], params[-2]), _grad_like(s[1], params[-1])]
         dR = dout.reshape(rshape).to(rdtype) if ctx.needs_input_grad[1] else None      # the residual joins after the norm
         return (None, dR, None, None, None, None, None, *grads)

@@ -13,7 +13,7 @@ from typing import Optional
 import torch
 
 from . import _lib
-from .functional import _finish, _flat, _grad_dest, _grad_like, _io_dtype, _need_cuda, _ptr, _stream, _timed
+from .functional import ResidualLink, _flat, _io_dtype, _need_cuda, _ptr, _stream, _timed, grad_slot, reduce_partials
 
 
 # K5 with a LayerNorm: the backward needs the normalised rows.  Two forms: (a) the forward saves nothing but its own output (which
@@ -144,7 +144,7 @@ class _TailFn(torch.autograd.Function):
         from_out = bool(norm) and need_bwd and h is None
         ctx.save_for_backward(out if from_out else h, mean, rstd, g32, gamma, beta, b32 if from_out else None)
         ctx.cfg = (float(p), seed, int(norm), y.shape, io, from_out)
-        ctx.link = link if (link is not None and link.armed) else None     # the op that armed it (K1, or a linear_acc GEMM) sums our dx1 into its own
+        ctx.link = ResidualLink.if_armed(link)     # the op that armed it (K1, or a linear_acc GEMM) sums our dx1 into its own
         out = out.view(y.shape)
         if want_mask:
             ctx.mark_non_differentiable(mask)
@@ -162,11 +162,12 @@ class _TailFn(torch.autograd.Function):
         # plain residual tail (T5): d/dx1 IS dout -- handed on as it is (no copy: a third of the pass's traffic), marked shared for a
         # consumer that would accumulate in place; without dropout the whole backward is the identity
         alias = (not norm) and ALIAS_RESIDUAL_GRAD
+        link, ctx.link = ctx.link, None
         if alias and p == 0:
             gx1 = df.view(shape)
-            if ctx.link is not None:
-                ctx.link.dx1, ctx.link.shared, gx1 = df.view(shape), True, None
-                ctx.link = None
+            if link is not None:
+                link.park(gx1, shared=True)
+                gx1 = None
             return df.view(shape), gx1, None, None, None, None, None, None, None, None
         dx1 = df if alias else torch.empty_like(df)
         dy = torch.empty_like(df) if p > 0 else None
@@ -187,25 +188,19 @@ class _TailFn(torch.autograd.Function):
         dgamma = dbeta = None
         if train_ln:
             # one launch sums the partials, straight into the parameters' slots of the trainer's flat gradient buffer when it
-            # offers them (functional._grad_dest: then autograd gets None and runs no accumulate kernel)
-            want_g = bool(ctx.needs_input_grad[2])
-            want_b = beta is not None and bool(ctx.needs_input_grad[3])
-            (tg, sg) = _grad_dest(gamma, (d,)) if want_g else (None, None)
-            (tb, sb) = _grad_dest(beta, (d,)) if want_b else (None, None)
-            from .functional import reduce_partials
-            reduce_partials(part, part.shape[0], d, tg, tb, deferrable=(tg is None or sg is not None) and (tb is None or sb is not None))
-            if want_g:
-                dgamma = _finish([(tg, sg, gamma)])[0]
-            if want_b:
-                dbeta = _finish([(tb, sb, beta)])[0]
+            # offers them (functional.grad_slot: then autograd gets None and runs no accumulate kernel)
+            sg = grad_slot(gamma, (d,)) if ctx.needs_input_grad[2] else None
+            sb = grad_slot(beta, (d,)) if (beta is not None and ctx.needs_input_grad[3]) else None
+            reduce_partials(part, part.shape[0], d, sg.t if sg else None, sb.t if sb else None,
+                            deferrable=(sg is None or sg.sunk) and (sb is None or sb.sunk))
+            dgamma = sg.finish() if sg else None
+            dbeta = sb.finish() if sb else None
         dx1 = dx1.view(shape)
         dyv = dy.view(shape) if dy is not None else dx1
         gx1 = dx1
-        if ctx.link is not None:        # functional.ResidualLink: K1's backward / the sublayer's first dgrad GEMM returns the sum for x1
-            ctx.link.dx1 = dx1
-            ctx.link.shared = dy is None or alias   # without dropout dy IS dx1 / the aliased dout is autograd's tensor: a consumer must not accumulate into it in place
+        if link is not None:        # functional.ResidualLink: K1's backward / the sublayer's first dgrad GEMM returns the sum for x1
+            link.park(dx1, shared=dy is None or alias)  # without dropout dy IS dx1 / the aliased dout is autograd's tensor: nobody may accumulate into it in place
             gx1 = None
-            ctx.link = None
         return dyv, gx1, dgamma, dbeta, None, None, None, None, None, None
 
 
@@ -232,10 +227,8 @@ class _RmsNormFn(torch.autograd.Function):
     def forward(ctx, x, weight, eps, link=None):
         lib = _lib.load()
         _need_cuda(x)
-        ctx.link = None
-        if link is not None and ctx.needs_input_grad[0]:
-            link.armed = True               # the other reader of x (the tail / K1, downstream) parks its d/dx here
-            ctx.link = link
+        # (the other reader of x -- the tail / K1, downstream -- parks its d/dx here)
+        ctx.link = link.arm() if (link is not None and ctx.needs_input_grad[0]) else None
         d = x.shape[-1]
         io = _io_dtype(x)
         xf = _flat(x, d)
@@ -260,13 +253,8 @@ class _RmsNormFn(torch.autograd.Function):
         if df.dtype != xf.dtype:
             df = df.to(xf.dtype)
         dx = torch.empty_like(xf)
-        dx_in = None
-        if ctx.link is not None:
-            dx_in, ctx.link.dx1 = ctx.link.dx1, None
-            ctx.link.shared = False
-            ctx.link = None
-            if dx_in is not None and (dx_in.dtype != xf.dtype or dx_in.numel() != xf.numel() or not dx_in.is_contiguous()):
-                dx_in = dx_in.reshape(xf.shape).to(xf.dtype).contiguous()
+        link, ctx.link = ctx.link, None
+        dx_in = link.take(xf.shape, xf.dtype) if link is not None else None
         train = bool(ctx.needs_input_grad[1])
         part = torch.empty(lib.vlpet_sublayer_tail_partials(M), 2, d, dtype=torch.float32, device=xf.device) if train else None
         rc = _timed("rms_bwd", M, lambda: lib.vlpet_rmsnorm_bwd(df.data_ptr(), xf.data_ptr(), rstd.data_ptr(), g32.data_ptr(),
@@ -274,10 +262,9 @@ class _RmsNormFn(torch.autograd.Function):
         _lib.check(rc, "vlpet_rmsnorm_bwd")
         dgamma = None
         if train:
-            (tg, sg) = _grad_dest(weight, (d,))
-            from .functional import reduce_partials
-            reduce_partials(part, part.shape[0], d, tg, None, deferrable=sg is not None)      # (queued by a trainer: flush_reduces)
-            dgamma = _finish([(tg, sg, weight)])[0]
+            sg = grad_slot(weight, (d,))
+            reduce_partials(part, part.shape[0], d, sg.t, None, deferrable=sg.sunk)      # (queued by a trainer: flush_reduces)
+            dgamma = sg.finish()
         return dx.view(shape), dgamma, None, None
 
 
@@ -323,10 +310,8 @@ class _TailRmsFn(torch.autograd.Function):
         _lib.check(rc, "vlpet_sublayer_tail_rms_fwd")
         ctx.save_for_backward(out, rstd, g32, weight)
         ctx.cfg = (float(p), seed, y.shape, io)
-        ctx.link = link if (link is not None and link.armed) else None       # K1 (or a linear_acc GEMM) takes our d/dx1
-        ctx.norm_link = norm_link                                            # the sum's later readers park their gradients here
-        if norm_link is not None:
-            norm_link.armed = True
+        ctx.link = ResidualLink.if_armed(link)                                          # K1 (or a linear_acc GEMM) takes our d/dx1
+        ctx.norm_link = norm_link.arm() if norm_link is not None else None              # the sum's later readers park their gradients here
         return out.view(y.shape), normed.view(y.shape)
 
     @staticmethod
@@ -335,17 +320,11 @@ class _TailRmsFn(torch.autograd.Function):
         out, rstd, g32, weight = ctx.saved_tensors
         p, seed, shape, io = ctx.cfg
         M, d = out.shape
-        dx_in = None
-        if ctx.norm_link is not None:
-            dx_in, ctx.norm_link.dx1 = ctx.norm_link.dx1, None
-            ctx.norm_link.shared = False
-            ctx.norm_link = None
-        for extra in (d_sum,):              # a reader of the sum that did not use the link: autograd hands its gradient here
-            if extra is not None:
-                e = extra.reshape(out.shape)
-                dx_in = e if dx_in is None else dx_in.reshape(out.shape) + e
-        if dx_in is not None and (dx_in.dtype != out.dtype or dx_in.numel() != out.numel() or not dx_in.is_contiguous()):
-            dx_in = dx_in.reshape(out.shape).to(out.dtype).contiguous()
+        norm_link, ctx.norm_link = ctx.norm_link, None
+        dx_in = norm_link.take(out.shape, out.dtype) if norm_link is not None else None
+        if d_sum is not None:               # a reader of the sum that did not use the link: autograd hands its gradient here
+            e = d_sum.reshape(out.shape).to(out.dtype)
+            dx_in = (e if dx_in is None else dx_in + e).contiguous()
         if d_normed is None:                # the normalised rows were never used: the plain tail's backward on d_sum
             d_normed = torch.zeros_like(out)
         df = _flat(d_normed, d)
@@ -361,18 +340,16 @@ class _TailRmsFn(torch.autograd.Function):
         _lib.check(rc, "vlpet_rmsnorm_tail_bwd")
         dgamma = None
         if train:
-            (tg, sg) = _grad_dest(weight, (d,))
-            from .functional import reduce_partials
-            reduce_partials(part, part.shape[0], d, tg, None, deferrable=sg is not None)
-            dgamma = _finish([(tg, sg, weight)])[0]
+            sg = grad_slot(weight, (d,))
+            reduce_partials(part, part.shape[0], d, sg.t, None, deferrable=sg.sunk)
+            dgamma = sg.finish()
         dx1 = dx1.view(shape)
         dyv = dy.view(shape) if dy is not None else dx1
         gx1 = dx1
-        if ctx.link is not None:
-            ctx.link.dx1 = dx1
-            ctx.link.shared = dy is None
+        link, ctx.link = ctx.link, None
+        if link is not None:
+            link.park(dx1, shared=dy is None)
             gx1 = None
-            ctx.link = None
         return dyv, gx1, dgamma, None, None, None, None, None
 
 
@@ -381,7 +358,6 @@ def sublayer_tail_rms(x1: torch.Tensor, y: torch.Tensor, next_norm: torch.nn.Mod
     """T5 form of K5 fused with the NEXT sublayer's RMS norm: returns ``sum = x1 + dropout(y, p)``, which carries the already normalised
     rows for ``next_norm`` (``sum._vlpet_norm``: visual.T5LayerNorm.forward returns them instead of launching, host.t5._new_norm_link returns
     the link through which the sum's later readers -- the next tail's add, K1's gate -- hand over their gradients)."""
-    from .functional import ResidualLink
     p_eff = float(p) if training else 0.0
     if seed is None:
         seed = _draw_seed() if p_eff > 0 else 0

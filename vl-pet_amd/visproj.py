@@ -9,7 +9,7 @@ from __future__ import annotations
 import torch
 
 from . import _lib
-from .functional import _finish, _flat, _grad_dest, _grad_like, _io_dtype, _need_cuda, _param_dtype, _ptr, _stream, _timed
+from .functional import _flat, _grad_like, _io_dtype, _need_cuda, _param_dtype, _ptr, _stream, _timed, grad_slot, reduce_partials
 
 
 # K4 forward, bf16:
@@ -177,7 +177,7 @@ class _VisProjFn(torch.autograd.Function):
         M, F = ff.shape
         d_out = w.shape[0]
         io = _io_dtype(ff)
-        s_g = s_be = None
+        s_g = s_be = None           # (LayerNorm form: the slots of dgamma / dbeta)
         if rms:         # T5's RMS norm: library ops (one call per step on [M_v, d])
             dyf = _flat(dy, d_out).float()
             xh = xhat.float()
@@ -185,7 +185,6 @@ class _VisProjFn(torch.autograd.Function):
             c2 = (g * xh).mean(dim=1, keepdim=True)
             dpre = (g - xh * c2) * rstd[:, None]
             dgamma = (dyf * xh).sum(0)
-            dbeta = None
             dpre_io = dpre.to(ff.dtype).contiguous()
         else:           # LayerNorm: K5's backward kernel on the saved xhat, its partial sums reduced into the gradient slots
             from .tail import _f32_frozen
@@ -204,29 +203,27 @@ class _VisProjFn(torch.autograd.Function):
                     dyc.data_ptr(), xhat.data_ptr(), rstd.data_ptr(), _f32_frozen(gamma).data_ptr(), dpre_io.data_ptr(), _ptr(part),
                     M, d_out, io, _stream()))
             _lib.check(rc, "vlpet_layernorm_bwd_xhat")
-            dgamma = dbeta = None
             if train_ln:
-                (dgamma, s_g) = _grad_dest(gamma, (d_out,))
-                (dbeta, s_be) = _grad_dest(beta, (d_out,)) if has_beta else (None, None)
-                from .functional import reduce_partials
-                reduce_partials(part, part.shape[0], d_out, dgamma, dbeta, deferrable=s_g is not None and (dbeta is None or s_be is not None))
-        (dw, s_w), (db, s_b) = _grad_dest(w, (d_out, F)), _grad_dest(b, (d_out,))
+                s_g = grad_slot(gamma, (d_out,))
+                s_be = grad_slot(beta, (d_out,)) if has_beta else None
+                reduce_partials(part, part.shape[0], d_out, s_g.t, s_be.t if s_be else None,
+                                deferrable=s_g.sunk and (s_be is None or s_be.sunk))
+        dw, db = grad_slot(w, (d_out, F)), grad_slot(b, (d_out,))
         nws = lib.vlpet_visproj_wgrad_workspace_bytes_io(M, F, d_out, io)
         ws = torch.empty(nws, dtype=torch.uint8, device=ff.device)
         rc = _timed("k4_wgrad", M, lambda: lib.vlpet_visproj_wgrad(
-            dpre_io.data_ptr(), ff.data_ptr(), dw.data_ptr(), db.data_ptr(), ws.data_ptr(), nws, M, F, d_out, io,
+            dpre_io.data_ptr(), ff.data_ptr(), dw.ptr, db.ptr, ws.data_ptr(), nws, M, F, d_out, io,
             _stream()))
         _lib.check(rc, "vlpet_visproj_wgrad")
         dR = dy.to(r_dtype) if has_r else None
-        gw, gb = _finish([(dw, s_w, w), (db, s_b, b)])
+        gw, gb = dw.finish(), db.finish()
         # the CLIP features of K4 carry no gradient; the low-rank projector's bottleneck activations do (library GEMM)
         dfeats = (dpre_io @ w.detach().to(dpre_io.dtype)).view(*lead, F) if ctx.needs_input_grad[0] else None
-        if rms or dgamma is None:
-            gg = _grad_like(dgamma, gamma) if dgamma is not None else None
-            gbe = None
+        if rms:
+            gg, gbe = _grad_like(dgamma, gamma), None
         else:
-            gg = _finish([(dgamma, s_g, gamma)])[0]
-            gbe = _finish([(dbeta, s_be, beta)])[0] if has_beta else None
+            gg = s_g.finish() if s_g else None
+            gbe = s_be.finish() if s_be else None
         return (dfeats, dR, gw, gb, gg, gbe, None, None, None, None, None)
 
 
@@ -318,21 +315,21 @@ class _VisPosFn(torch.autograd.Function):
         if dy.dtype != want:
             dy = dy.to(want)
         n_img = img_table.shape[0] if (has_img and ctx.needs_input_grad[5]) else 0
-        (dw, s_w), (db, s_b), (dg, s_g) = _grad_dest(w, (d, 5)), _grad_dest(b, (d,)), _grad_dest(gamma, (d,))
-        (dbe, s_be) = _grad_dest(beta, (d,)) if has_beta else (None, None)
-        (di, s_i) = _grad_dest(img_table, (n_img, d)) if n_img else (None, None)
+        dw, db, dg = grad_slot(w, (d, 5)), grad_slot(b, (d,)), grad_slot(gamma, (d,))
+        dbe = grad_slot(beta, (d,)) if has_beta else None
+        di = grad_slot(img_table, (n_img, d)) if n_img else None
         nws = lib.vlpet_vispos_bwd_workspace_bytes(M, d, n_img)
         ws = torch.empty(nws, dtype=torch.uint8, device=dy.device)
         wf, bf, gf = _f32c(w), _f32c(b), _f32c(gamma)
         rc = _timed("k4_pos_bwd", M, lambda: lib.vlpet_vispos_bwd(
             dy.data_ptr(), pf.data_ptr(), wf.data_ptr(), bf.data_ptr(), gf.data_ptr(),
             n_img, ik.data_ptr() if has_ids else None, ibs,
-            dw.data_ptr(), db.data_ptr(), dg.data_ptr(), _ptr(dbe), _ptr(di),
+            dw.ptr, db.ptr, dg.ptr, dbe.ptr if dbe else None, di.ptr if di else None,
             ws.data_ptr(), nws, M, N, d, eps, int(rms), io, _stream()))
         _lib.check(rc, "vlpet_vispos_bwd")
-        gw, gb, gg = _finish([(dw, s_w, w), (db, s_b, b), (dg, s_g, gamma)])
-        gbe = _finish([(dbe, s_be, beta)])[0] if has_beta else None
-        gi = _finish([(di, s_i, img_table)])[0] if n_img else None
+        gw, gb, gg = dw.finish(), db.finish(), dg.finish()
+        gbe = dbe.finish() if dbe else None
+        gi = di.finish() if di else None
         return (None, gw, gb, gg, gbe, gi, None, None, None, None, None, None)
 
 
