@@ -93,6 +93,35 @@ def test_fused_key_projection_with_the_attention_kernels_takes_one_gemm_each_way
     assert err <= 2e-2, err         # n bf16-rounded partial sums (autograd) vs one fp32-accumulated GEMM
 
 
+@pytest.mark.parametrize("family,Lk", [("short", 40), ("long_train", 130)])
+def test_second_backward_over_a_strided_key_block(family, Lk):
+    """Keys that are block 1 of a [B, Lk, 3 E] leaf, read in place with a KeyGradSlot, and two backwards over the retained graph: the
+    first writes dk into the slot's block, the second -- the slot is spent -- into a fresh tensor with k's own strides.  Both give the bits
+    of the call on contiguous keys without a slot.  (Before dk was allocated with k's strides the second backward raised AssertionError,
+    ``dk.stride() == k.stride()``, in both families: torch.empty_like of a non-dense view is dense.)"""
+    import vlpet_amd.attention as A
+    fn = {"short": A.short_attention, "long_train": A.long_attention_train}[family]
+    torch.manual_seed(Lk)
+    B, Lq = 2, 5
+    mk = lambda *s: (torch.randn(*s) * 0.5).cuda().bfloat16().requires_grad_(True)
+    q, v, kall = mk(B, Lq, E), mk(B, Lk, E), mk(B, Lk, 3 * E)
+    dout = (torch.randn(B, Lq, E) * 0.5).cuda().bfloat16()
+    # the path that exists without a slot: contiguous keys, two backwards, the same bits twice
+    kc = kall.detach()[..., E:2 * E].contiguous().requires_grad_(True)
+    out_c = fn(q, kc, v, H, p=0.0, training=False)
+    ref = [t.clone() for t in torch.autograd.grad(out_c, (q, kc, v), dout, retain_graph=True)]
+    for a, b in zip(torch.autograd.grad(out_c, (q, kc, v), dout, retain_graph=True), ref):
+        assert torch.equal(a, b)
+    kblk = kall[..., E:2 * E]
+    assert not kblk.is_contiguous()
+    out = fn(q, kblk, v, H, p=0.0, training=False, k_slot=(A.KeyGradSlot(3, E), 1))
+    assert torch.equal(out, out_c)
+    for _ in range(2):
+        grads = torch.autograd.grad(out, (q, kblk, v), dout, retain_graph=True)
+        for g, r in zip(grads, ref):
+            assert g.shape == r.shape and torch.equal(g, r)
+
+
 def _small_bart():
     import vlpet_amd.host.bart as HB
     import vlpet_amd.train as TR

@@ -240,22 +240,14 @@ def _sdpa_ctx():
 def attention_core(q, k, v, num_heads, attn_mask, causal, p, training, k_slot=None):
     """``dropout(softmax(q k^T / sqrt(d) + mask), p) v`` on the projection outputs ``[B, L, H * d]``.  Sequences of at most
     128 tokens in bf16 with head dim 64 (every image-text shape) run on vlpet_amd.attention's on-chip kernels; anything
-    else (fp32 parity runs, the 664-token video encoder, non-boolean masks) on torch's SDPA -- or, with ``LONG_ATTENTION`` set and
-    neither dropout nor a gradient needed, up to 1,024 tokens on the forward-only long kernel; with ``LONG_ATTENTION_TRAIN`` set and
-    dropout or a gradient needed, on the long training kernels.  The parity / CPU-baseline harnesses swap this module attribute for
-    the eager chain."""
+    else (fp32 parity runs, the 664-token video encoder, non-boolean masks) on torch's SDPA -- or, up to 1,024 tokens, on the long
+    kernels where ``attention.route`` says so under this module's switches.  The parity / CPU-baseline harnesses swap this module
+    attribute for the eager chain."""
     B, Lq, E = q.shape
-    if not EAGER_ATTENTION and (attn_mask is None or is_key_mask(attn_mask)) and A.supported(q, k, num_heads):
+    kind = _route(Lq, k.shape[1], p, training, q, k, v) if attn_mask is None or is_key_mask(attn_mask) else None
+    if A.fits(kind, q, k, v, num_heads):
         km = None if attn_mask is None else attn_mask[:, 0, 0, :]
-        return A.short_attention(q, k, v, num_heads, km, causal and attn_mask is None, p, training, k_slot=k_slot)
-    if ((attn_mask is None or is_key_mask(attn_mask)) and _long_applies(Lq, k.shape[1], p, training, q, k, v)
-            and v.dtype == q.dtype and A.supported_long(q, k, num_heads)):
-        km = None if attn_mask is None else attn_mask[:, 0, 0, :]
-        return A.long_attention(q, k, v, num_heads, km, causal and attn_mask is None)
-    if ((attn_mask is None or is_key_mask(attn_mask)) and _long_train_applies(Lq, k.shape[1], p, training, q, k, v)
-            and v.dtype == q.dtype and A.supported_long(q, k, num_heads)):
-        km = None if attn_mask is None else attn_mask[:, 0, 0, :]
-        return A.long_attention_train(q, k, v, num_heads, km, causal and attn_mask is None, p, training, k_slot=k_slot)
+        return A.attend(kind, q, k, v, num_heads, km, causal and attn_mask is None, p, training, k_slot=k_slot)
     sh = lambda t: t.reshape(B, -1, num_heads, E // num_heads).transpose(1, 2)
     with _sdpa_ctx():
         out = F.scaled_dot_product_attention(sh(q), sh(k), sh(v), attn_mask=attn_mask, is_causal=causal and attn_mask is None,
@@ -267,21 +259,22 @@ FUSE_BIAS_GRAD = True    # A/B switch (tools/ab_switches.py): False = autograd's
 EAGER_ATTENTION = False   # A/B switch: the library (SDPA) path for every shape
 LONG_ATTENTION = False    # switch: True = sequences of 129 .. 1,024 tokens (the 664-token video encoder) run on vlpet_amd.attention's
                           # forward-only long kernel wherever no dropout and no gradient is needed: a bitwise reproducible encoder
-
-
-def _long_applies(Lq, Lk, p, training, *tensors) -> bool:
-    """the long kernel instead of SDPA: switched on, a length past the short kernels and within its own, no dropout, no gradient"""
-    return (LONG_ATTENTION and not EAGER_ATTENTION and max(Lq, Lk) > A.MAX_LEN and Lq <= A.MAX_LONG and Lk <= A.MAX_LONG
-            and (not training or p == 0) and not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)))
 LONG_ATTENTION_TRAIN = False   # switch: True = the same lengths on the long TRAINING kernels (dropout by the device generator, a backward
                                # with a fixed summation order) wherever a call needs dropout or a gradient
 
 
+def _route(Lq, Lk, p, training, *tensors, grad=False):
+    """attention.route under this module's switches (``grad``: the caller knows of a gradient that the tensors do not show)"""
+    return A.route(Lq, Lk, p, training, A.needs_grad(*tensors, grad=grad), eager=EAGER_ATTENTION, long_on=LONG_ATTENTION,
+                   long_train_on=LONG_ATTENTION_TRAIN)
+
+
+def _long_applies(Lq, Lk, p, training, *tensors) -> bool:
+    return _route(Lq, Lk, p, training, *tensors) == "long"
+
+
 def _long_train_applies(Lq, Lk, p, training, *tensors, grad=False) -> bool:
-    """the long training kernels instead of SDPA: switched on, a length past the short kernels and within their own, and dropout or a
-    gradient needed (``grad``: the caller knows of one that the tensors do not show)"""
-    return (LONG_ATTENTION_TRAIN and not EAGER_ATTENTION and max(Lq, Lk) > A.MAX_LEN and Lq <= A.MAX_LONG and Lk <= A.MAX_LONG
-            and ((training and p > 0) or (torch.is_grad_enabled() and (grad or any(t.requires_grad for t in tensors)))))
+    return _route(Lq, Lk, p, training, *tensors, grad=grad) == "long_train"
 FUSE_QKV = True              # A/B switch: False = separate q / k / v projections in self-attention
 FUSE_CROSS_KEYS = True       # A/B switch: False = every decoder layer projects its own cross-attention keys (round 5)
 SDPA_BACKEND = None          # A/B switch: "flash" | "efficient" | "math" pins torch SDPA's backend on the library path
@@ -325,22 +318,16 @@ class BartAttention(nn.Module):
             # self-attention with frozen projections: one [E -> 3E] GEMM each way, the attention kernels read / write the
             # q | k | v column blocks in place (one input gradient instead of three that autograd would have to sum)
             frozen = not any(t.requires_grad for m in (self.q_proj, self.k_proj, self.v_proj) for t in (m.weight, m.bias))
-            long_ = _long_applies(L, L, self.dropout, self.training, hidden)
-            long_train = _long_train_applies(L, L, self.dropout, self.training, hidden, grad=in_link is not None)
+            kind = _route(L, L, self.dropout, self.training, hidden, grad=in_link is not None)
             if (frozen and (attn_mask is None or is_key_mask(attn_mask)) and hidden.is_cuda and hidden.dtype == torch.bfloat16
-                    and (L <= A.MAX_LEN or long_ or long_train) and self.head_dim == A.HEAD_DIM):
+                    and kind is not None and self.head_dim == A.HEAD_DIM):
                 w, b = self._fused_qkv(hidden.dtype)
                 if in_link is not None:
                     qkv = VF.linear_acc(hidden, in_link, (w, b))
                 else:
                     qkv = F.linear(hidden, w, b)
                 km = None if attn_mask is None else attn_mask[:, 0, 0, :]
-                if L > A.MAX_LEN and long_train:
-                    out = A.long_self_attention_train(qkv, self.num_heads, km, causal and attn_mask is None, self.dropout, self.training)
-                elif L > A.MAX_LEN:
-                    out = A.long_self_attention(qkv, self.num_heads, km, causal and attn_mask is None)
-                else:
-                    out = A.short_self_attention(qkv, self.num_heads, km, causal and attn_mask is None, self.dropout, self.training)
+                out = A.attend_qkv(kind, qkv, self.num_heads, km, causal and attn_mask is None, self.dropout, self.training)
                 return _linear(self.out_proj, out)
         if self.use_lora:
             q = self.q_proj(hidden, task)
@@ -592,12 +579,9 @@ class BartDecoder(nn.Module):
         if not FUSE_CROSS_KEYS or EAGER_ATTENTION or len(self.layers) < 2 or not enc.is_cuda or enc.dtype != torch.bfloat16:
             return False
         a0 = self.layers[0].encoder_attn
-        # (past the short kernels' length only the forward-only long kernel reads a column block in place: no gradient, no dropout)
-        long_ = LONG_ATTENTION and enc.shape[1] <= A.MAX_LONG and not torch.is_grad_enabled() and not (self.training and a0.dropout > 0)
-        # (... and the long training kernels, which also write dk into the shared slot, wherever a call needs dropout or a gradient)
-        long_train = (LONG_ATTENTION_TRAIN and enc.shape[1] <= A.MAX_LONG
-                      and (torch.is_grad_enabled() or (self.training and a0.dropout > 0)))
-        if (enc.shape[1] > A.MAX_LEN and not long_ and not long_train) or a0.head_dim != A.HEAD_DIM:
+        # (past the short kernels' length the forward-only long kernel reads a column block in place, and so do the long training kernels,
+        # which also write dk into the shared slot; any gradient mode counts as a gradient needed: the queries are not known here)
+        if _route(enc.shape[1], enc.shape[1], a0.dropout, self.training, grad=True) is None or a0.head_dim != A.HEAD_DIM:
             return False
         if enc_mask is not None and not is_key_mask(enc_mask):
             return False

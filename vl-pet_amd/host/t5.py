@@ -209,17 +209,23 @@ LONG_ATTENTION = False    # switch (host/bart.py: the same): True = 129 .. 1,024
 FUSE_QKV = True           # A/B switch: False = separate q / k / v projections in self-attention
 
 
-def _long_applies(Lq, Lk, p, training, *tensors) -> bool:
-    return (LONG_ATTENTION and not EAGER_ATTENTION and max(Lq, Lk) > A.MAX_LEN and Lq <= A.MAX_LONG and Lk <= A.MAX_LONG
-            and (not training or p == 0) and not (torch.is_grad_enabled() and any(t.requires_grad for t in tensors)))
 LONG_ATTENTION_TRAIN = False   # switch (host/bart.py: the same): True = those lengths on the long TRAINING kernels wherever a call needs
                                # dropout or a gradient
+FUSE_CROSS_KEYS = True    # A/B switch: False = every decoder block projects its own cross-attention keys (host/bart.py: the same fusion)
+
+
+def _route(Lq, Lk, p, training, *tensors, grad=False):
+    """attention.route under this module's switches (host/bart.py: the same)"""
+    return A.route(Lq, Lk, p, training, A.needs_grad(*tensors, grad=grad), eager=EAGER_ATTENTION, long_on=LONG_ATTENTION,
+                   long_train_on=LONG_ATTENTION_TRAIN)
+
+
+def _long_applies(Lq, Lk, p, training, *tensors) -> bool:
+    return _route(Lq, Lk, p, training, *tensors) == "long"
 
 
 def _long_train_applies(Lq, Lk, p, training, *tensors) -> bool:
-    return (LONG_ATTENTION_TRAIN and not EAGER_ATTENTION and max(Lq, Lk) > A.MAX_LEN and Lq <= A.MAX_LONG and Lk <= A.MAX_LONG
-            and ((training and p > 0) or (torch.is_grad_enabled() and any(t.requires_grad for t in tensors))))
-FUSE_CROSS_KEYS = True    # A/B switch: False = every decoder block projects its own cross-attention keys (host/bart.py: the same fusion)
+    return _route(Lq, Lk, p, training, *tensors) == "long_train"
 
 
 class AttnSpec:
@@ -307,10 +313,8 @@ class T5Attention(nn.Module):
         src = hidden if kv is None else kv
         k_slot = None
         spec = bias if isinstance(bias, AttnSpec) else None
-        long_ = _long_applies(Lq, src.shape[1], self.dropout, self.training, hidden, src)
-        long_train = _long_train_applies(Lq, src.shape[1], self.dropout, self.training, hidden, src)
-        if (kv is None and FUSE_QKV and spec is not None and not EAGER_ATTENTION and hidden.is_cuda and hidden.dtype == torch.bfloat16
-                and self.d_kv == A.HEAD_DIM and (Lq <= A.MAX_LEN or long_ or long_train)
+        kind = _route(Lq, Lq, self.dropout, self.training, hidden) if kv is None and FUSE_QKV and spec is not None else None
+        if (kind is not None and hidden.is_cuda and hidden.dtype == torch.bfloat16 and self.d_kv == A.HEAD_DIM
                 and not any(m.weight.requires_grad for m in (self.q, self.k, self.v))):
             fast = spec.fast()
             if fast is not None:
@@ -322,13 +326,7 @@ class T5Attention(nn.Module):
                     qkv = VF.linear_acc(hidden, None, (w, None))
                 else:
                     qkv = F.linear(hidden, w)
-                if Lq > A.MAX_LEN and long_train:
-                    out = A.long_self_attention_train(qkv, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0,
-                                                      bias=fast[0])
-                elif Lq > A.MAX_LEN:
-                    out = A.long_self_attention(qkv, self.n_heads, fast[1], spec.causal, scale=1.0, bias=fast[0])
-                else:
-                    out = A.short_self_attention(qkv, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0, bias=fast[0])
+                out = A.attend_qkv(kind, qkv, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0, bias=fast[0])
                 return _linear(self.o, out)
         fused = (FUSE_RESIDUAL_GRAD and FUSE_NORM_GRAD and hidden.is_cuda and torch.is_grad_enabled() and src.requires_grad
                  and not any(m.weight.requires_grad for m in (self.q, self.k, self.v)))
@@ -350,24 +348,12 @@ class T5Attention(nn.Module):
             q, k, v = _linear(self.q, hidden), _linear(self.k, src), _linear(self.v, src)
             if kv is not None and self.attn_value_parallel_adapter is not None:
                 v = self.attn_value_parallel_adapter(src, task, y=v)                      # K2
-        if spec is not None and not EAGER_ATTENTION and self.d_kv == A.HEAD_DIM and A.supported(q, k, self.n_heads):
+        kind = _route(Lq, k.shape[1], self.dropout, self.training, q, k, v) if spec is not None and self.d_kv == A.HEAD_DIM else None
+        if A.fits(kind, q, k, v, self.n_heads):
             fast = spec.fast()
             if fast is not None:        # on-chip kernels: bias shared by the batch + boolean key mask + causal flag; T5 has no 1/sqrt(d)
-                out = A.short_attention(q, k, v, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0, bias=fast[0],
-                                        k_slot=k_slot)
-                return _linear(self.o, out)
-        if (spec is not None and long_ and self.d_kv == A.HEAD_DIM and v.dtype == q.dtype and A.supported_long(q, k, self.n_heads)
-                and not (torch.is_grad_enabled() and any(t.requires_grad for t in (q, k, v)))):
-            fast = spec.fast()
-            if fast is not None:
-                out = A.long_attention(q, k, v, self.n_heads, fast[1], spec.causal, scale=1.0, bias=fast[0])
-                return _linear(self.o, out)
-        if (spec is not None and self.d_kv == A.HEAD_DIM and v.dtype == q.dtype and A.supported_long(q, k, self.n_heads)
-                and _long_train_applies(Lq, k.shape[1], self.dropout, self.training, q, k, v)):
-            fast = spec.fast()
-            if fast is not None:
-                out = A.long_attention_train(q, k, v, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0,
-                                             bias=fast[0], k_slot=k_slot)
+                out = A.attend(kind, q, k, v, self.n_heads, fast[1], spec.causal, self.dropout, self.training, scale=1.0, bias=fast[0],
+                               k_slot=k_slot)
                 return _linear(self.o, out)
         mask = spec.dense(q.dtype) if spec is not None else (None if bias is None else bias.to(q.dtype))
         out = F.scaled_dot_product_attention(self._shape(q, B), self._shape(k.contiguous(), B), self._shape(v, B), attn_mask=mask,
@@ -562,8 +548,9 @@ class T5Decoder(nn.Module):
         if not (FUSE_RESIDUAL_GRAD and FUSE_NORM_GRAD and torch.is_grad_enabled() and enc.requires_grad):
             return False
         atts = [blk.layer[1].EncDecAttention for blk in self.block]
-        # (past the short kernels' length the long training kernels read a block in place and write dk into the shared slot)
-        if (enc.shape[1] > A.MAX_LEN and not (LONG_ATTENTION_TRAIN and enc.shape[1] <= A.MAX_LONG)) or atts[0].d_kv != A.HEAD_DIM or cross_bias.fast() is None:
+        # (past the short kernels' length the long training kernels read a block in place and write dk into the shared slot; a gradient is
+        # needed here: see above)
+        if _route(enc.shape[1], enc.shape[1], atts[0].dropout, self.training, grad=True) is None or atts[0].d_kv != A.HEAD_DIM or cross_bias.fast() is None:
             return False
         return not any(m.weight.requires_grad or m.bias is not None for a in atts for m in (a.q, a.k, a.v))
 
