@@ -136,7 +136,13 @@ static int check_common(int64_t M, int d, int tiles, int io_dtype) {
     return 0;
 }
 
-static int gate_flags(int gate_mode, int* flags);
+static int gate_flags(int gate_mode, int* flags) {
+    *flags = 0;
+    if (gate_mode == VLPET_GATE_MUL) *flags = PET_GATE;
+    else if (gate_mode == VLPET_GATE_ADD) *flags = PET_GATE | PET_GATE_ADD;
+    else if (gate_mode != VLPET_GATE_NONE) return VLPET_E_SHAPE;
+    return 0;
+}
 
 // the forward's saved bottleneck activations: four [M, 32*tiles] IO-dtype tensors (z_a, gelu'_a, z_g, gelu'_g)
 static size_t saved_stride(int64_t M, int tiles, int io_dtype) {
@@ -246,65 +252,67 @@ static int run_fwd(const void* xa, const void* res, const void* xg, const void* 
     return herr(launch_pet_fwd(a, io_dtype == VLPET_F32, (hipStream_t)stream));
 }
 
+// K1 / K2 / K3 forward: one argument check per operator in front of run_fwd.  `save`: the `_save` entry point, whose block is required.
+static int k1_fwd(const void* x1, const void* x2, const void* packed_a, const void* packed_g, void* out, void* saved, bool save,
+                  int64_t M, int d, int tiles, int gate_mode, float delta_scale, float x2_scale, float gate_scale, int io_dtype,
+                  vlpet_stream_t stream) {
+    int flags;
+    if (gate_flags(gate_mode, &flags)) return VLPET_E_SHAPE;
+    if (save && !saved) return VLPET_E_NULL;
+    return run_fwd(x2, x2, x1, packed_a, packed_g, NO_DROP, out, M, d, tiles, x2_scale, delta_scale,
+                   flags ? gate_scale : 1.f, flags, io_dtype, stream, saved);
+}
+static int k2_fwd(const void* x, const void* y, const void* packed, void* out, void* saved, bool save, int64_t M, int d, int tiles,
+                  float scale, int io_dtype, vlpet_stream_t stream) {
+    if (save && !saved) return VLPET_E_NULL;
+    return run_fwd(x, y, nullptr, packed, nullptr, NO_DROP, out, M, d, tiles, 1.f, scale, 1.f, 0, io_dtype, stream, saved);
+}
+static int k3_fwd(const void* x, const void* base, const void* packed, const uint8_t* keep_mask, float p, uint64_t seed,
+                  uint8_t* keep_out, void* out, void* saved, bool save, int64_t M, int d, int tiles, float scaling, int io_dtype,
+                  vlpet_stream_t stream) {
+    if (save && !saved) return VLPET_E_NULL;
+    DropSpec ds;
+    if (int rc = make_drop(keep_mask, p, seed, keep_out, &ds)) return rc;
+    return run_fwd(x, base, nullptr, packed, nullptr, ds, out, M, d, tiles, 1.f, scaling, 1.f, PET_ACT_IDENTITY, io_dtype, stream, saved);
+}
+
 extern "C" int vlpet_adapter_gate_fwd(const void* x1, const void* x2, const void* packed_a,
                                       const void* packed_g, void* out, int64_t M, int d, int tiles,
                                       int gate_mode, float delta_scale, float x2_scale, float gate_scale,
                                       int io_dtype, vlpet_stream_t stream) {
-    int flags = 0;
-    if (gate_mode == VLPET_GATE_MUL) flags = PET_GATE;
-    else if (gate_mode == VLPET_GATE_ADD) flags = PET_GATE | PET_GATE_ADD;
-    else if (gate_mode != VLPET_GATE_NONE) return VLPET_E_SHAPE;
-    return run_fwd(x2, x2, x1, packed_a, packed_g, NO_DROP, out, M, d, tiles, x2_scale, delta_scale,
-                   flags ? gate_scale : 1.f, flags, io_dtype, stream);
+    return k1_fwd(x1, x2, packed_a, packed_g, out, nullptr, false, M, d, tiles, gate_mode, delta_scale, x2_scale, gate_scale, io_dtype, stream);
 }
-
 extern "C" int vlpet_adapter_gate_fwd_save(const void* x1, const void* x2, const void* packed_a,
                                            const void* packed_g, void* out, void* saved, int64_t M, int d, int tiles,
                                            int gate_mode, float delta_scale, float x2_scale, float gate_scale,
                                            int io_dtype, vlpet_stream_t stream) {
-    int flags;
-    if (gate_flags(gate_mode, &flags)) return VLPET_E_SHAPE;
-    if (!saved) return VLPET_E_NULL;
-    return run_fwd(x2, x2, x1, packed_a, packed_g, NO_DROP, out, M, d, tiles, x2_scale, delta_scale,
-                   flags ? gate_scale : 1.f, flags, io_dtype, stream, saved);
+    return k1_fwd(x1, x2, packed_a, packed_g, out, saved, true, M, d, tiles, gate_mode, delta_scale, x2_scale, gate_scale, io_dtype, stream);
 }
-
 extern "C" int vlpet_parallel_adapter_fwd(const void* x, const void* y, const void* packed, void* out,
                                           int64_t M, int d, int tiles, float scale, int io_dtype,
                                           vlpet_stream_t stream) {
-    return run_fwd(x, y, nullptr, packed, nullptr, NO_DROP, out, M, d, tiles, 1.f, scale, 1.f, 0, io_dtype, stream);
+    return k2_fwd(x, y, packed, out, nullptr, false, M, d, tiles, scale, io_dtype, stream);
 }
-
 extern "C" int vlpet_parallel_adapter_fwd_save(const void* x, const void* y, const void* packed, void* out, void* saved,
                                                int64_t M, int d, int tiles, float scale, int io_dtype,
                                                vlpet_stream_t stream) {
-    if (!saved) return VLPET_E_NULL;
-    return run_fwd(x, y, nullptr, packed, nullptr, NO_DROP, out, M, d, tiles, 1.f, scale, 1.f, 0, io_dtype, stream, saved);
+    return k2_fwd(x, y, packed, out, saved, true, M, d, tiles, scale, io_dtype, stream);
 }
-
 extern "C" int vlpet_lora_delta_fwd(const void* x, const void* base, const void* packed,
                                     const uint8_t* keep_mask, float p, uint64_t seed, uint8_t* keep_out, void* out,
                                     int64_t M, int d, int tiles, float scaling, int io_dtype, vlpet_stream_t stream) {
-    DropSpec ds;
-    if (int rc = make_drop(keep_mask, p, seed, keep_out, &ds)) return rc;
-    return run_fwd(x, base, nullptr, packed, nullptr, ds, out, M, d, tiles, 1.f, scaling, 1.f,
-                   PET_ACT_IDENTITY, io_dtype, stream);
+    return k3_fwd(x, base, packed, keep_mask, p, seed, keep_out, out, nullptr, false, M, d, tiles, scaling, io_dtype, stream);
+}
+extern "C" int vlpet_lora_delta_fwd_save(const void* x, const void* base, const void* packed,
+                                         const uint8_t* keep_mask, float p, uint64_t seed, uint8_t* keep_out, void* out,
+                                         void* saved, int64_t M, int d, int tiles, float scaling, int io_dtype,
+                                         vlpet_stream_t stream) {
+    return k3_fwd(x, base, packed, keep_mask, p, seed, keep_out, out, saved, true, M, d, tiles, scaling, io_dtype, stream);
 }
 
 extern "C" size_t vlpet_lora_saved_bytes(int64_t M, int d, int tiles, int io_dtype) {
     if (M <= 0 || d <= 0 || !tiles_ok(tiles)) return 0;
     return saved_stride(M, tiles, io_dtype) + align256((size_t)M * (d / 8));      // z, then 1 bit per element of the mask
-}
-
-extern "C" int vlpet_lora_delta_fwd_save(const void* x, const void* base, const void* packed,
-                                         const uint8_t* keep_mask, float p, uint64_t seed, uint8_t* keep_out, void* out,
-                                         void* saved, int64_t M, int d, int tiles, float scaling, int io_dtype,
-                                         vlpet_stream_t stream) {
-    if (!saved) return VLPET_E_NULL;
-    DropSpec ds;
-    if (int rc = make_drop(keep_mask, p, seed, keep_out, &ds)) return rc;
-    return run_fwd(x, base, nullptr, packed, nullptr, ds, out, M, d, tiles, 1.f, scaling, 1.f,
-                   PET_ACT_IDENTITY, io_dtype, stream, saved);
 }
 
 // K3 at rank <= 8: the streaming form (lora8.hip).  `saved` NULL = inference form; else the training form's saved block
@@ -598,6 +606,45 @@ extern "C" int vlpet_adapter_gate_bwd_finalize_launch(int64_t M, int d, int tile
     return 0;
 }
 
+// K1 / K2 / K3 backward: one argument check per operator in front of run_bwd.
+// The five K1 variants differ in what they require (the forward's block, dx1_in, a gate), in the `phases` bits they pass on (`mask`) and
+// in those of which one must be set (`any`); `y`, and `dx1_in` where it is not required, may be NULL.
+struct K1BwdForm { bool saved, dx1_in, gate; int mask, any; };
+static int k1_bwd(const K1BwdForm& f, int phases, const void* dy, const void* x1, const void* x2, const void* y, const void* saved,
+                  const void* packed_a, const void* packed_g, const void* dx1_in, void* dx1, void* dx2,
+                  float* dwd, float* dbd, float* dwu, float* dbu,
+                  float* dwgd, float* dbgd, float* dwgu, float* dbgu, int r, int rg,
+                  void* workspace, size_t workspace_bytes, int64_t M, int d, int tiles,
+                  int gate_mode, float delta_scale, float x2_scale, float gate_scale,
+                  int io_dtype, vlpet_stream_t stream) {
+    int flags;
+    if (gate_flags(gate_mode, &flags)) return VLPET_E_SHAPE;
+    if (!dbd || !dbu || (f.saved && !saved) || (f.dx1_in && !dx1_in) || (f.gate && !flags) || (phases & f.any) == 0) return VLPET_E_NULL;
+    return run_bwd(dy, x2, x2, x1, packed_a, packed_g, NO_DROP, dx2, dx1, dwd, dbd, dwu, dbu,
+                   dwgd, dbgd, dwgu, dbgu, r, rg, workspace, workspace_bytes, M, d, tiles,
+                   x2_scale, delta_scale, flags ? gate_scale : 1.f, flags, io_dtype, stream, phases & f.mask, saved, dx1_in, y);
+}
+// (`need_saved`: the `_saved` entry point, whose block is required)
+static int k2_bwd(const void* dy, const void* x, const void* saved, bool need_saved, const void* packed, void* dx,
+                  float* dwd, float* dbd, float* dwu, float* dbu, int r, void* workspace, size_t workspace_bytes, int64_t M, int d,
+                  int tiles, float scale, int io_dtype, vlpet_stream_t stream) {
+    if (!dbd || !dbu || (need_saved && !saved)) return VLPET_E_NULL;
+    return run_bwd(dy, x, nullptr, nullptr, packed, nullptr, NO_DROP, dx, nullptr, dwd, dbd, dwu, dbu,
+                   nullptr, nullptr, nullptr, nullptr, r, 0, workspace, workspace_bytes, M, d, tiles,
+                   1.f, scale, 1.f, 0, io_dtype, stream, 3, saved);
+}
+static int k3_bwd(const void* dy, const void* x, const void* saved, bool need_saved, const void* packed, const uint8_t* keep_mask,
+                  float p, uint64_t seed, void* dx, float* da, float* db, int r, void* workspace, size_t workspace_bytes,
+                  int64_t M, int d, int tiles, float scaling, int io_dtype, vlpet_stream_t stream) {
+    if (need_saved && !saved) return VLPET_E_NULL;
+    DropSpec ds;
+    if (int rc = make_drop(keep_mask, p, seed, nullptr, &ds)) return rc;
+    return run_bwd(dy, x, nullptr, nullptr, packed, nullptr, ds, dx, nullptr,
+                   da, nullptr, db, nullptr, nullptr, nullptr, nullptr, nullptr, r, 0,
+                   workspace, workspace_bytes, M, d, tiles, 1.f, scaling, 1.f, PET_ACT_IDENTITY,
+                   io_dtype, stream, 3, saved);
+}
+
 extern "C" int vlpet_adapter_gate_bwd(const void* dy, const void* x1, const void* x2,
                                       const void* packed_a, const void* packed_g, void* dx1, void* dx2,
                                       float* dwd, float* dbd, float* dwu, float* dbu,
@@ -605,24 +652,9 @@ extern "C" int vlpet_adapter_gate_bwd(const void* dy, const void* x1, const void
                                       void* workspace, size_t workspace_bytes, int64_t M, int d, int tiles,
                                       int gate_mode, float delta_scale, float x2_scale, float gate_scale,
                                       int io_dtype, vlpet_stream_t stream) {
-    int flags = 0;
-    if (gate_mode == VLPET_GATE_MUL) flags = PET_GATE;
-    else if (gate_mode == VLPET_GATE_ADD) flags = PET_GATE | PET_GATE_ADD;
-    else if (gate_mode != VLPET_GATE_NONE) return VLPET_E_SHAPE;
-    if (!dbd || !dbu) return VLPET_E_NULL;
-    return run_bwd(dy, x2, x2, x1, packed_a, packed_g, NO_DROP, dx2, dx1, dwd, dbd, dwu, dbu,
-                   dwgd, dbgd, dwgu, dbgu, r, rg, workspace, workspace_bytes, M, d, tiles,
-                   x2_scale, delta_scale, flags ? gate_scale : 1.f, flags, io_dtype, stream);
+    return k1_bwd({false, false, false, 7, 3}, 3, dy, x1, x2, nullptr, nullptr, packed_a, packed_g, nullptr, dx1, dx2, dwd, dbd, dwu, dbu, dwgd, dbgd, dwgu, dbgu, r, rg,
+                  workspace, workspace_bytes, M, d, tiles, gate_mode, delta_scale, x2_scale, gate_scale, io_dtype, stream);
 }
-
-static int gate_flags(int gate_mode, int* flags) {
-    *flags = 0;
-    if (gate_mode == VLPET_GATE_MUL) *flags = PET_GATE;
-    else if (gate_mode == VLPET_GATE_ADD) *flags = PET_GATE | PET_GATE_ADD;
-    else if (gate_mode != VLPET_GATE_NONE) return VLPET_E_SHAPE;
-    return 0;
-}
-
 extern "C" int vlpet_adapter_gate_bwd_phase(int phases, const void* dy, const void* x1, const void* x2,
                                             const void* packed_a, const void* packed_g, void* dx1, void* dx2,
                                             float* dwd, float* dbd, float* dwu, float* dbu,
@@ -630,14 +662,9 @@ extern "C" int vlpet_adapter_gate_bwd_phase(int phases, const void* dy, const vo
                                             void* workspace, size_t workspace_bytes, int64_t M, int d, int tiles,
                                             int gate_mode, float delta_scale, float x2_scale, float gate_scale,
                                             int io_dtype, vlpet_stream_t stream) {
-    int flags;
-    if (gate_flags(gate_mode, &flags)) return VLPET_E_SHAPE;
-    if (!dbd || !dbu || (phases & 3) == 0) return VLPET_E_NULL;
-    return run_bwd(dy, x2, x2, x1, packed_a, packed_g, NO_DROP, dx2, dx1, dwd, dbd, dwu, dbu,
-                   dwgd, dbgd, dwgu, dbgu, r, rg, workspace, workspace_bytes, M, d, tiles,
-                   x2_scale, delta_scale, flags ? gate_scale : 1.f, flags, io_dtype, stream, phases & 7);
+    return k1_bwd({false, false, false, 7, 3}, phases, dy, x1, x2, nullptr, nullptr, packed_a, packed_g, nullptr, dx1, dx2, dwd, dbd, dwu, dbu, dwgd, dbgd, dwgu, dbgu, r, rg,
+                  workspace, workspace_bytes, M, d, tiles, gate_mode, delta_scale, x2_scale, gate_scale, io_dtype, stream);
 }
-
 extern "C" int vlpet_adapter_gate_bwd_saved(int phases, const void* dy, const void* x1, const void* x2, const void* saved,
                                             const void* packed_a, const void* packed_g, void* dx1, void* dx2,
                                             float* dwd, float* dbd, float* dwu, float* dbu,
@@ -645,14 +672,9 @@ extern "C" int vlpet_adapter_gate_bwd_saved(int phases, const void* dy, const vo
                                             void* workspace, size_t workspace_bytes, int64_t M, int d, int tiles,
                                             int gate_mode, float delta_scale, float x2_scale, float gate_scale,
                                             int io_dtype, vlpet_stream_t stream) {
-    int flags;
-    if (gate_flags(gate_mode, &flags)) return VLPET_E_SHAPE;
-    if (!dbd || !dbu || !saved || (phases & 19) == 0) return VLPET_E_NULL;
-    return run_bwd(dy, x2, x2, x1, packed_a, packed_g, NO_DROP, dx2, dx1, dwd, dbd, dwu, dbu,
-                   dwgd, dbgd, dwgu, dbgu, r, rg, workspace, workspace_bytes, M, d, tiles,
-                   x2_scale, delta_scale, flags ? gate_scale : 1.f, flags, io_dtype, stream, phases & 63, saved);
+    return k1_bwd({true, false, false, 63, 19}, phases, dy, x1, x2, nullptr, saved, packed_a, packed_g, nullptr, dx1, dx2, dwd, dbd, dwu, dbu, dwgd, dbgd, dwgu, dbgu, r, rg,
+                  workspace, workspace_bytes, M, d, tiles, gate_mode, delta_scale, x2_scale, gate_scale, io_dtype, stream);
 }
-
 extern "C" int vlpet_adapter_gate_bwd_saved_acc(int phases, const void* dy, const void* x1, const void* x2, const void* saved,
                                                 const void* packed_a, const void* packed_g, const void* dx1_in, void* dx1, void* dx2,
                                                 float* dwd, float* dbd, float* dwu, float* dbu,
@@ -660,14 +682,9 @@ extern "C" int vlpet_adapter_gate_bwd_saved_acc(int phases, const void* dy, cons
                                                 void* workspace, size_t workspace_bytes, int64_t M, int d, int tiles,
                                                 int gate_mode, float delta_scale, float x2_scale, float gate_scale,
                                                 int io_dtype, vlpet_stream_t stream) {
-    int flags;
-    if (gate_flags(gate_mode, &flags)) return VLPET_E_SHAPE;
-    if (!dbd || !dbu || !saved || !dx1_in || !flags || (phases & 19) == 0) return VLPET_E_NULL;
-    return run_bwd(dy, x2, x2, x1, packed_a, packed_g, NO_DROP, dx2, dx1, dwd, dbd, dwu, dbu,
-                   dwgd, dbgd, dwgu, dbgu, r, rg, workspace, workspace_bytes, M, d, tiles,
-                   x2_scale, delta_scale, gate_scale, flags, io_dtype, stream, phases & 63, saved, dx1_in);
+    return k1_bwd({true, true, true, 63, 19}, phases, dy, x1, x2, nullptr, saved, packed_a, packed_g, dx1_in, dx1, dx2, dwd, dbd, dwu, dbu, dwgd, dbgd, dwgu, dbgu, r, rg,
+                  workspace, workspace_bytes, M, d, tiles, gate_mode, delta_scale, x2_scale, gate_scale, io_dtype, stream);
 }
-
 // The same with the forward's output y at hand (round 5): pass 1 of the two-pass forms then needs the gate chain's up projection
 // only (dq = dy * y * (1 - g)); dx1_in is optional here.  y == NULL: exactly vlpet_adapter_gate_bwd_saved / _acc.
 extern "C" int vlpet_adapter_gate_bwd_saved_y(int phases, const void* dy, const void* x1, const void* x2, const void* y, const void* saved,
@@ -677,61 +694,36 @@ extern "C" int vlpet_adapter_gate_bwd_saved_y(int phases, const void* dy, const 
                                               void* workspace, size_t workspace_bytes, int64_t M, int d, int tiles,
                                               int gate_mode, float delta_scale, float x2_scale, float gate_scale,
                                               int io_dtype, vlpet_stream_t stream) {
-    int flags;
-    if (gate_flags(gate_mode, &flags)) return VLPET_E_SHAPE;
-    if (!dbd || !dbu || !saved || !flags || (phases & 19) == 0) return VLPET_E_NULL;
-    return run_bwd(dy, x2, x2, x1, packed_a, packed_g, NO_DROP, dx2, dx1, dwd, dbd, dwu, dbu,
-                   dwgd, dbgd, dwgu, dbgu, r, rg, workspace, workspace_bytes, M, d, tiles,
-                   x2_scale, delta_scale, gate_scale, flags, io_dtype, stream, phases & 63, saved, dx1_in, y);
+    return k1_bwd({true, false, true, 63, 19}, phases, dy, x1, x2, y, saved, packed_a, packed_g, dx1_in, dx1, dx2, dwd, dbd, dwu, dbu, dwgd, dbgd, dwgu, dbgu, r, rg,
+                  workspace, workspace_bytes, M, d, tiles, gate_mode, delta_scale, x2_scale, gate_scale, io_dtype, stream);
 }
 
 extern "C" int vlpet_parallel_adapter_bwd(const void* dy, const void* x, const void* packed, void* dx,
                                           float* dwd, float* dbd, float* dwu, float* dbu, int r,
                                           void* workspace, size_t workspace_bytes, int64_t M, int d,
                                           int tiles, float scale, int io_dtype, vlpet_stream_t stream) {
-    if (!dbd || !dbu) return VLPET_E_NULL;
-    return run_bwd(dy, x, nullptr, nullptr, packed, nullptr, NO_DROP, dx, nullptr, dwd, dbd, dwu, dbu,
-                   nullptr, nullptr, nullptr, nullptr, r, 0, workspace, workspace_bytes, M, d, tiles,
-                   1.f, scale, 1.f, 0, io_dtype, stream);
+    return k2_bwd(dy, x, nullptr, false, packed, dx, dwd, dbd, dwu, dbu, r, workspace, workspace_bytes, M, d, tiles, scale, io_dtype, stream);
 }
-
 extern "C" int vlpet_parallel_adapter_bwd_saved(const void* dy, const void* x, const void* saved, const void* packed, void* dx,
                                                 float* dwd, float* dbd, float* dwu, float* dbu, int r,
                                                 void* workspace, size_t workspace_bytes, int64_t M, int d,
                                                 int tiles, float scale, int io_dtype, vlpet_stream_t stream) {
-    if (!dbd || !dbu || !saved) return VLPET_E_NULL;
-    return run_bwd(dy, x, nullptr, nullptr, packed, nullptr, NO_DROP, dx, nullptr, dwd, dbd, dwu, dbu,
-                   nullptr, nullptr, nullptr, nullptr, r, 0, workspace, workspace_bytes, M, d, tiles,
-                   1.f, scale, 1.f, 0, io_dtype, stream, 3, saved);
+    return k2_bwd(dy, x, saved, true, packed, dx, dwd, dbd, dwu, dbu, r, workspace, workspace_bytes, M, d, tiles, scale, io_dtype, stream);
 }
-
 extern "C" int vlpet_lora_delta_bwd(const void* dy, const void* x, const void* packed,
                                     const uint8_t* keep_mask, float p, uint64_t seed, void* dx,
                                     float* da, float* db, int r, void* workspace, size_t workspace_bytes,
                                     int64_t M, int d, int tiles, float scaling, int io_dtype,
                                     vlpet_stream_t stream) {
-    DropSpec ds;
-    if (int rc = make_drop(keep_mask, p, seed, nullptr, &ds)) return rc;
-    return run_bwd(dy, x, nullptr, nullptr, packed, nullptr, ds, dx, nullptr,
-                   da, nullptr, db, nullptr, nullptr, nullptr, nullptr, nullptr, r, 0,
-                   workspace, workspace_bytes, M, d, tiles, 1.f, scaling, 1.f, PET_ACT_IDENTITY,
-                   io_dtype, stream);
+    return k3_bwd(dy, x, nullptr, false, packed, keep_mask, p, seed, dx, da, db, r, workspace, workspace_bytes, M, d, tiles, scaling, io_dtype, stream);
 }
-
 extern "C" int vlpet_lora_delta_bwd_saved(const void* dy, const void* x, const void* saved, const void* packed,
                                           const uint8_t* keep_mask, float p, uint64_t seed, void* dx,
                                           float* da, float* db, int r, void* workspace, size_t workspace_bytes,
                                           int64_t M, int d, int tiles, float scaling, int io_dtype,
                                           vlpet_stream_t stream) {
-    if (!saved) return VLPET_E_NULL;
-    DropSpec ds;
-    if (int rc = make_drop(keep_mask, p, seed, nullptr, &ds)) return rc;
-    return run_bwd(dy, x, nullptr, nullptr, packed, nullptr, ds, dx, nullptr,
-                   da, nullptr, db, nullptr, nullptr, nullptr, nullptr, nullptr, r, 0,
-                   workspace, workspace_bytes, M, d, tiles, 1.f, scaling, 1.f, PET_ACT_IDENTITY,
-                   io_dtype, stream, 3, saved);
+    return k3_bwd(dy, x, saved, true, packed, keep_mask, p, seed, dx, da, db, r, workspace, workspace_bytes, M, d, tiles, scaling, io_dtype, stream);
 }
-
 
 // ------------------------------------------------------------------ K4: visual projection
 static inline bool dout_ok(int d) { return d == 64 || d == 128 || d == 768; }

@@ -179,8 +179,6 @@ def pack_pair(down_w: Sequence[torch.Tensor], down_b: Optional[Sequence[torch.Te
     return PackedPair(buf, tiles, r, d, io_dtype)
 
 
-# Bumped by optimizers that update parameters behind autograd's back (the fused flat-buffer AdamW writes through
-# raw pointers, which does not touch ``Tensor._version``); part of every pack-cache key.
 # keep the gated forward's bottleneck activations for the backward (vlpet_adapter_gate_fwd_save / _bwd_saved); False = the
 # backward recomputes them from x1, x2 (no extra memory between forward and backward)
 SAVE_ACTIVATIONS = True
@@ -197,6 +195,8 @@ K1_BWD_FROM_OUTPUT = True
 # weight gradients.
 K1_BWD_FINALIZE_LAUNCH = False
 
+# Bumped by optimizers that update parameters behind autograd's back (the fused flat-buffer AdamW writes through
+# raw pointers, which does not touch ``Tensor._version``); part of every pack-cache key.
 WEIGHTS_EPOCH = 0
 # Part of the keys of the derived copies of FROZEN tensors (fused q|k|v weight, padded LM head, fp32 LayerNorm copies, the
 # logits-bias flag).  Those keys also carry (data_ptr, Tensor._version), but ``p.data`` has its own version counter: in-place
@@ -371,6 +371,31 @@ def grad_slot(p: torch.Tensor, shape, block: bool = False) -> GradSlot:
         if v is not None:
             return GradSlot(v, sink, p)
     return GradSlot(torch.empty(*shape, dtype=torch.float32, device=p.device), None, p)
+
+
+class AdapterSlots:
+    """The gradient slots of one adapter pair in the order of the kernels' eight gradient arguments: down weight and bias (the heads
+    stacked, one block slot each), up weight and bias, then -- with ``rg`` -- the gate's four.  ``params``: N_h down weights, N_h down
+    biases, up w, up b, [the gate's four].  ``d_in``: the down projections' input width (K1: d; the low-rank projector: feat_dim)."""
+
+    __slots__ = ("slots",)
+
+    def __init__(self, params, n_heads, r, rg, d, d_in=None):
+        d_in, n = d if d_in is None else d_in, 2 * n_heads
+        shapes = [(r, d_in), (r,), (d, r), (d,)] + ([(rg, d_in), (rg,), (d, rg), (d,)] if rg else [])
+        owners = [params[0], params[n_heads]] + list(params[n:n + len(shapes) - 2])
+        self.slots = [grad_slot(p, shape, block=i < 2) for i, (p, shape) in enumerate(zip(owners, shapes))]
+
+    def ptrs(self):         # (NULL for the gate's four without a gate)
+        return (*(s.ptr for s in self.slots), *((None,) * (8 - len(self.slots))))
+
+    @property
+    def all_sunk(self) -> bool:
+        return all(s.sunk for s in self.slots)
+
+    def finish(self, params, n_heads):      # one gradient per parameter (see GradSlot.finish)
+        return (self.slots[0].finish_heads(params[:n_heads]) + self.slots[1].finish_heads(params[n_heads:2 * n_heads])
+                + [s.finish() for s in self.slots[2:]])
 
 
 FANOUT_SUM = True          # A/B switch (tools/ab_switches.py: VLPET_NO_FANOUT_SUM=1): fanout() below
@@ -644,6 +669,69 @@ def linear_acc(x: torch.Tensor, link: Optional[ResidualLink], *mods):
     return _LinearAccFn.apply(x, link, *ws, *bs)
 
 
+def _saved_block(ctx, nbytes, device):
+    """Training (SAVE_ACTIVATIONS, read per call): a fresh block of ``nbytes()`` in which the forward of K1 / K2 / K3 leaves z and
+    gelu'(pre) of its chains (up to 4 x [M, 32*tiles], IO dtype), so that the backward neither recomputes the down projections nor
+    reads their inputs for them.  Kept in ``ctx.act`` until the backward; None otherwise."""
+    ctx.act = torch.empty(nbytes(), dtype=torch.uint8, device=device) if (SAVE_ACTIVATIONS and any(ctx.needs_input_grad)) else None
+    return ctx.act
+
+
+def _block_call(entry, suffix, block, timer, M, head, tail):
+    """One launch of K1 / K2 / K3: with the saved block, ``entry + suffix`` and the block between ``head`` and ``tail``; else ``entry``."""
+    fn = getattr(_lib.load(), entry if block is None else entry + suffix)
+    args = (*head, *tail) if block is None else (*head, block.data_ptr(), *tail)
+    _lib.check(_timed(timer, M, lambda: fn(*args, _stream())), entry)
+
+
+def _bwd_workspace(lib, M, d, tiles, gate, io, device):
+    nws = lib.vlpet_bwd_workspace_bytes(M, d, tiles, int(gate), io)
+    return torch.empty(nws, dtype=torch.uint8, device=device), nws
+
+
+def _park_or_return(ctx, attr, g):
+    """The ending of a backward whose d/dx may be handed over: into the armed link ``ctx.<attr>`` (autograd gets None) or back."""
+    link = getattr(ctx, attr)
+    setattr(ctx, attr, None)
+    if link is None:
+        return g
+    link.park(g)
+    return None
+
+
+def k1_bwd_schedule(gate: bool, saved: bool, side: bool, previous_split: bool, bracketed: bool, form: int, finalize_due: bool):
+    """The calls of one K1 backward, in order: [(timer name or None, ``phases`` bits, on the side stream)].  ``side``: the weight
+    gradients go to WGRAD_STREAM; ``bracketed``: the timer wants ``k1_bwd_rows``; ``form``: vlpet_adapter_gate_bwd_form's answer;
+    ``finalize_due``: pass 2 ends in a finalize launch.  The split forms (bit 2: the first half already delivers dx1 / dx2 -- the
+    two-pass form produces them in its second) come first, and a timer brackets the half whose name it wants.  Else the op is one
+    call, or -- bracketed -- the same work with its kernels bracketed separately, EVERY step once ``k1_bwd_rows`` is wanted (bit 3:
+    pass 2 leaves its partial sums, bit 4: the finalize launch alone).  Bit 5 (K1_BWD_FINALIZE_LAUNCH) is the caller's."""
+    rows, wgrad = "k1_bwd_rows", "k1_bwd_wgrad"
+    if side or previous_split:
+        return [(rows, 1 | 4, False), (wgrad, 2 | 4, bool(side))]
+    if not bracketed:
+        return [(None, 3, False)]
+    if not gate:
+        # adapter-only K1 (small / middle gate scripts): its two-pass form is taken for the WHOLE op only (csrc/api.hip ng2), so the
+        # bracketed path issues it as one call too -- split phases would time the round-2 row kernel instead of what ships
+        return [(rows, 3, False)]
+    if not (saved and form == 2):
+        return [(rows, 1, False), (wgrad, 2, False)]
+    return [(rows, 1, False), (wgrad, 2 | 8, False)] + ([("k1_bwd_fin", 16, False)] if finalize_due else [])
+
+
+def _k1_bwd_entry(lib, gate, dy, x1, x2, pk_a, pk_g, act, y, dx1_in):
+    """The K1 backward's C call for what is present, and its arguments between ``phases`` and ``dx1``.  With a gate and the forward's
+    block: the entry point that takes ``y`` and ``dx1_in``, either of which may be NULL (the same call as _bwd_saved / _bwd_saved_acc)."""
+    head = (dy.data_ptr(), _ptr(x1) if gate else None, x2.data_ptr())
+    packs = (pk_a.buf.data_ptr(), pk_g.buf.data_ptr() if gate else None)
+    if act is None:
+        return lib.vlpet_adapter_gate_bwd_phase, (*head, *packs)
+    if not gate:
+        return lib.vlpet_adapter_gate_bwd_saved, (*head, act.data_ptr(), *packs)
+    return lib.vlpet_adapter_gate_bwd_saved_y, (*head, _ptr(y), act.data_ptr(), *packs, _ptr(dx1_in))
+
+
 class _AdapterGateFn(torch.autograd.Function):
     """K1.  inputs: x1, x2, then N_h down weights, N_h down biases, up w, up b, gate down w/b, gate up w/b."""
 
@@ -657,22 +745,10 @@ class _AdapterGateFn(torch.autograd.Function):
         x1f = _flat(x1, d) if gate_mode != GATE_NONE else None
         M = x2f.shape[0]
         out = torch.empty_like(x2f)
-        # training: the forward leaves z and gelu'(pre) of its chains (up to 4 x [M, 32*tiles], IO dtype) and the
-        # backward neither recomputes the down projections nor reads x1 / x2 for them
-        act = None
-        if SAVE_ACTIVATIONS and any(ctx.needs_input_grad):
-            act = torch.empty(lib.vlpet_saved_bytes(M, pk_a.tiles, io), dtype=torch.uint8, device=x2f.device)
-            rc = _timed("k1_fwd", M, lambda: lib.vlpet_adapter_gate_fwd_save(
-                _ptr(x1f), x2f.data_ptr(), pk_a.buf.data_ptr(), pk_g.buf.data_ptr() if pk_g is not None else None,
-                out.data_ptr(), act.data_ptr(), M, d, pk_a.tiles, gate_mode, float(delta_scale), float(x2_scale),
-                float(gate_scale), io, _stream()))
-        else:
-            rc = _timed("k1_fwd", M, lambda: lib.vlpet_adapter_gate_fwd(
-                _ptr(x1f), x2f.data_ptr(), pk_a.buf.data_ptr(), pk_g.buf.data_ptr() if pk_g is not None else None,
-                out.data_ptr(), M, d, pk_a.tiles, gate_mode, float(delta_scale), float(x2_scale), float(gate_scale),
-                io, _stream()))
-        _lib.check(rc, "vlpet_adapter_gate_fwd")
-        ctx.act = act
+        act = _saved_block(ctx, lambda: lib.vlpet_saved_bytes(M, pk_a.tiles, io), x2f.device)
+        _block_call("vlpet_adapter_gate_fwd", "_save", act, "k1_fwd", M,
+                    (_ptr(x1f), x2f.data_ptr(), pk_a.buf.data_ptr(), pk_g.buf.data_ptr() if pk_g is not None else None, out.data_ptr()),
+                    (M, d, pk_a.tiles, gate_mode, float(delta_scale), float(x2_scale), float(gate_scale), io))
         # the tail that follows may park its d/dx1 for this op's backward
         ctx.link = link.arm() if (link is not None and act is not None and gate_mode != GATE_NONE and x1.requires_grad) else None
         # the other direction: the sublayer's first GEMM (upstream of x2) armed `out_link` -- this backward parks d/dx1 there
@@ -701,85 +777,52 @@ class _AdapterGateFn(torch.autograd.Function):
         io = _io_dtype(x2f)
         gate = gate_mode != GATE_NONE
         dyf = _flat(dy, d)
-        dev = x2f.device
-        r = pk_a.r
-        rg = pk_g.r if gate else 0
-        nh2 = 2 * n_heads
-        # down w (the heads stacked), down b, up w, up b, then the gate's four (None without a gate)
-        slots = [grad_slot(params[0], (r, d), block=True), grad_slot(params[n_heads], (r,), block=True),
-                 grad_slot(params[nh2], (d, r)), grad_slot(params[nh2 + 1], (d,))]
-        if gate:
-            slots += [grad_slot(params[nh2 + 2], (rg, d)), grad_slot(params[nh2 + 3], (rg,)),
-                      grad_slot(params[nh2 + 4], (d, rg)), grad_slot(params[nh2 + 5], (d,))]
+        r, rg = pk_a.r, (pk_g.r if gate else 0)
+        slots = AdapterSlots(params, n_heads, r, rg, d)
         dx2 = torch.empty_like(x2f)
         dx1 = torch.empty_like(x2f) if gate else None
-        nws = lib.vlpet_bwd_workspace_bytes(M, d, pk_a.tiles, int(gate), io)
-        ws = torch.empty(nws, dtype=torch.uint8, device=dev)
-        args = (dyf.data_ptr(), _ptr(x1f) if gate else None, x2f.data_ptr(),
-                pk_a.buf.data_ptr(), pk_g.buf.data_ptr() if gate else None, _ptr(dx1), dx2.data_ptr(),
-                *(s.ptr for s in slots), *((None,) * (8 - len(slots))), r, rg,
-                ws.data_ptr(), nws, M, d, pk_a.tiles, gate_mode, sd, s2, gs, io, _stream())
-        side = WGRAD_STREAM if all(s.sunk for s in slots) else None
-        act = ctx.act
-
+        ws, nws = _bwd_workspace(lib, M, d, pk_a.tiles, gate, io, x2f.device)
+        act, ctx.act = ctx.act, None
         # the sublayer tail's residual-stream gradient, if it was handed over (ResidualLink): summed inside the kernel
         link, ctx.link = ctx.link, None
         dx1_in = link.take(x2f.shape, x2f.dtype) if link is not None else None
+        fn, lead = _k1_bwd_entry(lib, gate, dyf, x1f, x2f, pk_a, pk_g, act, yf, dx1_in)
+        args = (*lead, _ptr(dx1), dx2.data_ptr(), *slots.ptrs(), r, rg, ws.data_ptr(), nws, M, d, pk_a.tiles, gate_mode, sd, s2, gs, io)
+        side = WGRAD_STREAM if slots.all_sunk else None
+        split = side is not None or K1_BWD_PREVIOUS_SPLIT
+        # (the schedule's bracketed branch, the only one that asks the library for the form: there the timer brackets EVERY step)
+        bracketed = not split and TIMER is not None and TIMER.wants("k1_bwd_rows")
+        form = lib.vlpet_adapter_gate_bwd_form(M, d, pk_a.tiles, io) if (bracketed and gate and act is not None) else 0
+        fin = form == 2 and (K1_BWD_FINALIZE_LAUNCH or lib.vlpet_adapter_gate_bwd_finalize_launch(M, d, pk_a.tiles, io) == 1)
+        # (A/B, bit 5: the round-3 form -- partial slabs + a finalize launch -- instead of the in-launch reduce-scatter)
+        fin_bit = 32 if K1_BWD_FINALIZE_LAUNCH else 0
 
-        def phase(ph, a):       # one or both halves of the backward, with or without the forward's saved activations
-            if K1_BWD_FINALIZE_LAUNCH:
-                ph |= 32            # (A/B: the round-3 form -- partial slabs + a finalize launch -- instead of the in-launch reduce-scatter)
-            if act is not None and yf is not None:
-                return lib.vlpet_adapter_gate_bwd_saved_y(ph, a[0], a[1], a[2], yf.data_ptr(), act.data_ptr(), a[3], a[4], _ptr(dx1_in),
-                                                          *a[5:])
-            if act is not None and dx1_in is not None:
-                return lib.vlpet_adapter_gate_bwd_saved_acc(ph, a[0], a[1], a[2], act.data_ptr(), a[3], a[4], dx1_in.data_ptr(),
-                                                            *a[5:])
-            if act is not None:
-                return lib.vlpet_adapter_gate_bwd_saved(ph, a[0], a[1], a[2], act.data_ptr(), *a[3:])
-            return lib.vlpet_adapter_gate_bwd_phase(ph, *a)
+        def step(name, bits):
+            call = lambda: fn(bits | fin_bit, *args, _stream())     # (the current stream: the side stream's inside its context)
+            if name is None or TIMER is None or not (bracketed or TIMER.wants(name)):
+                return call()
+            return TIMER.bracket(name, M, call)
 
-        if side is not None:
-            # (bit 2: the form whose first half already delivers dx1 / dx2 -- the two-pass form produces them in its second)
-            rc = _timed("k1_bwd_rows", M, lambda: phase(1 | 4, args))
-            if rc == 0:
-                side.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(side):
-                    sargs = args[:-1] + (_stream(),)
-                    rc = _timed("k1_bwd_wgrad", M, lambda: phase(2 | 4, sargs))
-                for t in (x1f, x2f, dyf, ws, pk_a.buf) + ((pk_g.buf,) if gate else ()) + ((act,) if act is not None else ()) \
-                        + ((yf,) if yf is not None else ()):
-                    t.record_stream(side)        # the caching allocator must not recycle them under the side stream
-        elif K1_BWD_PREVIOUS_SPLIT:
-            rc = _timed("k1_bwd_rows", M, lambda: phase(1 | 4, args))
-            if rc == 0:
-                rc = _timed("k1_bwd_wgrad", M, lambda: phase(2 | 4, args))
-        elif TIMER is None or not TIMER.wants("k1_bwd_rows"):
-            rc = phase(3, args)
-        elif not gate:
-            # adapter-only K1 (small / middle gate scripts): its two-pass form is taken for the WHOLE op only (csrc/api.hip ng2), so the
-            # bracketed path issues it as one call too -- split phases would time the round-2 row kernel instead of what ships
-            rc = TIMER.bracket("k1_bwd_rows", M, lambda: phase(3, args))
-        else:       # same work, its kernels bracketed separately
-            rc = TIMER.bracket("k1_bwd_rows", M, lambda: phase(1, args))
-            two_pass = act is not None and lib.vlpet_adapter_gate_bwd_form(M, d, pk_a.tiles, io) == 2
-            if rc == 0 and two_pass:        # (pass 2 and -- where the form has one -- the finalize launch of the column-parallel form)
-                rc = TIMER.bracket("k1_bwd_wgrad", M, lambda: phase(2 | 8, args))
-                if rc == 0 and (K1_BWD_FINALIZE_LAUNCH or lib.vlpet_adapter_gate_bwd_finalize_launch(M, d, pk_a.tiles, io) == 1):
-                    rc = TIMER.bracket("k1_bwd_fin", M, lambda: phase(16, args))
-            elif rc == 0:
-                rc = TIMER.bracket("k1_bwd_wgrad", M, lambda: phase(2, args))
-        ctx.act = None
+        rc = 0
+        for name, bits, on_side in k1_bwd_schedule(gate, act is not None, side is not None, K1_BWD_PREVIOUS_SPLIT, bracketed, form, fin):
+            if rc != 0:
+                break
+            if not on_side:
+                rc = step(name, bits)
+                continue
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                rc = step(name, bits)
+            for t in (x1f, x2f, dyf, ws, pk_a.buf) + ((pk_g.buf,) if gate else ()) + ((act,) if act is not None else ()) \
+                    + ((yf,) if yf is not None else ()):
+                t.record_stream(side)        # the caching allocator must not recycle them under the side stream
         _lib.check(rc, "vlpet_adapter_gate_bwd")
         if not gate:
             # without a gate the kernel returns the adapter-branch gradient only; add the residual path
             dx2 = dx2 + s2 * dyf
-        grads = slots[0].finish_heads(params[:n_heads]) + slots[1].finish_heads(params[n_heads:nh2]) + [s.finish() for s in slots[2:]]
-        gx1 = dx1.view(shp1) if gate else None
-        out_link, ctx.out_link = ctx.out_link, None
-        if out_link is not None:        # the dgrad GEMM of the sublayer's first projection accumulates onto it (_LinearAccFn)
-            out_link.park(gx1)
-            gx1 = None
+        grads = slots.finish(params, n_heads)
+        # (out_link: the dgrad GEMM of the sublayer's first projection accumulates onto d/dx1 -- _LinearAccFn)
+        gx1 = _park_or_return(ctx, "out_link", dx1.view(shp1)) if gate else None
         return (gx1, dx2.view(shp2), None, None, None, None, None, None, None, None, None, *grads)
 
 
@@ -814,17 +857,9 @@ class _ParallelAdapterFn(torch.autograd.Function):
         xf, yf = _flat(x, d), _flat(y, d)
         M = xf.shape[0]
         out = torch.empty_like(xf)
-        act = None
-        if SAVE_ACTIVATIONS and any(ctx.needs_input_grad):      # training: z / gelu'(pre) for the backward (see K1)
-            act = torch.empty(lib.vlpet_saved_bytes(M, pk.tiles, io), dtype=torch.uint8, device=xf.device)
-            rc = _timed("k2_fwd", M, lambda: lib.vlpet_parallel_adapter_fwd_save(
-                xf.data_ptr(), yf.data_ptr(), pk.buf.data_ptr(), out.data_ptr(), act.data_ptr(), M, d, pk.tiles,
-                float(scale), io, _stream()))
-        else:
-            rc = _timed("k2_fwd", M, lambda: lib.vlpet_parallel_adapter_fwd(
-                xf.data_ptr(), yf.data_ptr(), pk.buf.data_ptr(), out.data_ptr(), M, d, pk.tiles, float(scale), io, _stream()))
-        _lib.check(rc, "vlpet_parallel_adapter_fwd")
-        ctx.act = act
+        act = _saved_block(ctx, lambda: lib.vlpet_saved_bytes(M, pk.tiles, io), xf.device)      # (z / gelu'(pre) for the backward, see K1)
+        _block_call("vlpet_parallel_adapter_fwd", "_save", act, "k2_fwd", M, (xf.data_ptr(), yf.data_ptr(), pk.buf.data_ptr(), out.data_ptr()),
+                    (M, d, pk.tiles, float(scale), io))
         ctx.save_for_backward(xf, wd, bd, wu, bu)
         ctx.pk, ctx.scale, ctx.shape = pk, float(scale), x.shape
         return out.view(y.shape)
@@ -842,25 +877,13 @@ class _ParallelAdapterFn(torch.autograd.Function):
         dwd, dbd, dwu, dbu = (grad_slot(wd, (r, d)), grad_slot(bd, (r,)), grad_slot(wu, (d, r)),
                               grad_slot(bu, (d,)) if bu is not None else GradSlot.scratch((d,), xf.device))
         dx = torch.empty_like(xf)
-        nws = lib.vlpet_bwd_workspace_bytes(M, d, pk.tiles, 0, io)
-        ws = torch.empty(nws, dtype=torch.uint8, device=xf.device)
-        act = ctx.act
-        if act is not None:
-            rc = _timed("k2_bwd", M, lambda: lib.vlpet_parallel_adapter_bwd_saved(
-                dyf.data_ptr(), xf.data_ptr(), act.data_ptr(), pk.buf.data_ptr(), dx.data_ptr(), dwd.ptr, dbd.ptr,
-                dwu.ptr, dbu.ptr, r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io, _stream()))
-        else:
-            rc = _timed("k2_bwd", M, lambda: lib.vlpet_parallel_adapter_bwd(
-                dyf.data_ptr(), xf.data_ptr(), pk.buf.data_ptr(), dx.data_ptr(), dwd.ptr, dbd.ptr,
-                dwu.ptr, dbu.ptr, r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io, _stream()))
-        ctx.act = None
-        _lib.check(rc, "vlpet_parallel_adapter_bwd")
+        ws, nws = _bwd_workspace(lib, M, d, pk.tiles, False, io, xf.device)
+        act, ctx.act = ctx.act, None
+        _block_call("vlpet_parallel_adapter_bwd", "_saved", act, "k2_bwd", M, (dyf.data_ptr(), xf.data_ptr()),
+                    (pk.buf.data_ptr(), dx.data_ptr(), dwd.ptr, dbd.ptr, dwu.ptr, dbu.ptr, r, ws.data_ptr(), nws, M, d, pk.tiles, ctx.scale, io))
         grads = [s.finish() for s in (dwd, dbd, dwu, dbu)]
-        gx = dx.view(ctx.shape)
-        link, ctx.link = ctx.link, None
-        if link is not None:        # the projection that made `y` from the same `x` accumulates its dgrad onto dx (_LinearAccFn)
-            link.park(gx)
-            gx = None
+        # (link: the projection that made `y` from the same `x` accumulates its dgrad onto dx -- _LinearAccFn)
+        gx = _park_or_return(ctx, "link", dx.view(ctx.shape))
         return (gx, dy, None, None, None, *grads)
 
 
@@ -898,26 +921,14 @@ class _LoraDeltaFn(torch.autograd.Function):
             if kf.dtype != torch.uint8:
                 kf = kf.to(torch.uint8)
         mask = torch.empty(M, d, dtype=torch.uint8, device=xf.device) if (want_mask and p > 0) else None
-        act = None
-        train_form = SAVE_ACTIVATIONS and any(ctx.needs_input_grad)
+        head = (xf.data_ptr(), bf.data_ptr(), pk.buf.data_ptr(), _ptr(kf), float(p), int(seed), _ptr(mask), out.data_ptr())
+        act = _saved_block(ctx, lambda: lib.vlpet_lora_saved_bytes(M, d, pk.tiles, io), xf.device)     # (z = dropout(x) A^T, see K1 / K2)
         if LORA_R8_STREAMING and lib.vlpet_lora_r8_applies(M, d, pk.r, io):
             # rank <= 8: the streaming row kernel (csrc/lora8.hip) -- same pack, same masks, same saved block as the MFMA form
-            if train_form:
-                act = torch.empty(lib.vlpet_lora_saved_bytes(M, d, pk.tiles, io), dtype=torch.uint8, device=xf.device)
-            rc = _timed("k3_fwd", M, lambda: lib.vlpet_lora_delta_fwd_r8(
-                xf.data_ptr(), bf.data_ptr(), pk.buf.data_ptr(), _ptr(kf), float(p), int(seed), _ptr(mask), out.data_ptr(),
-                _ptr(act), M, d, pk.r, float(scaling), io, _stream()))
-        elif train_form:      # training: z = dropout(x) A^T for the backward (see K1 / K2)
-            act = torch.empty(lib.vlpet_lora_saved_bytes(M, d, pk.tiles, io), dtype=torch.uint8, device=xf.device)
-            rc = _timed("k3_fwd", M, lambda: lib.vlpet_lora_delta_fwd_save(
-                xf.data_ptr(), bf.data_ptr(), pk.buf.data_ptr(), _ptr(kf), float(p), int(seed), _ptr(mask), out.data_ptr(),
-                act.data_ptr(), M, d, pk.tiles, float(scaling), io, _stream()))
+            rc = _timed("k3_fwd", M, lambda: lib.vlpet_lora_delta_fwd_r8(*head, _ptr(act), M, d, pk.r, float(scaling), io, _stream()))
+            _lib.check(rc, "vlpet_lora_delta_fwd")
         else:
-            rc = _timed("k3_fwd", M, lambda: lib.vlpet_lora_delta_fwd(
-                xf.data_ptr(), bf.data_ptr(), pk.buf.data_ptr(), _ptr(kf), float(p), int(seed), _ptr(mask), out.data_ptr(),
-                M, d, pk.tiles, float(scaling), io, _stream()))
-        _lib.check(rc, "vlpet_lora_delta_fwd")
-        ctx.act = act
+            _block_call("vlpet_lora_delta_fwd", "_save", act, "k3_fwd", M, head, (M, d, pk.tiles, float(scaling), io))
         ctx.save_for_backward(xf, lora_a, lora_b)
         ctx.keep = kf
         ctx.cfg = (pk, float(scaling), float(p), int(seed), x.shape)
@@ -940,24 +951,11 @@ class _LoraDeltaFn(torch.autograd.Function):
         r = pk.r
         da, db = grad_slot(lora_a, (r, d)), grad_slot(lora_b, (d, r))
         dx = torch.empty_like(xf)
-        nws = lib.vlpet_bwd_workspace_bytes(M, d, pk.tiles, 0, io)
-        ws = torch.empty(nws, dtype=torch.uint8, device=xf.device)
-        act = ctx.act
-        if act is not None:
-            rc = _timed("k3_bwd", M, lambda: lib.vlpet_lora_delta_bwd_saved(
-                dyf.data_ptr(), xf.data_ptr(), act.data_ptr(), pk.buf.data_ptr(), _ptr(ctx.keep), p, seed, dx.data_ptr(),
-                da.ptr, db.ptr, r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io, _stream()))
-        else:
-            rc = _timed("k3_bwd", M, lambda: lib.vlpet_lora_delta_bwd(
-                dyf.data_ptr(), xf.data_ptr(), pk.buf.data_ptr(), _ptr(ctx.keep), p, seed, dx.data_ptr(), da.ptr,
-                db.ptr, r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io, _stream()))
-        ctx.act = None
-        _lib.check(rc, "vlpet_lora_delta_bwd")
-        gx = dx.view(shape)
-        link, ctx.link = ctx.link, None
-        if link is not None:
-            link.park(gx)
-            gx = None
+        ws, nws = _bwd_workspace(lib, M, d, pk.tiles, False, io, xf.device)
+        act, ctx.act = ctx.act, None
+        _block_call("vlpet_lora_delta_bwd", "_saved", act, "k3_bwd", M, (dyf.data_ptr(), xf.data_ptr()),
+                    (pk.buf.data_ptr(), _ptr(ctx.keep), p, seed, dx.data_ptr(), da.ptr, db.ptr, r, ws.data_ptr(), nws, M, d, pk.tiles, scaling, io))
+        gx = _park_or_return(ctx, "link", dx.view(shape))
         return (gx, dy, None, None, None, None, None, None, da.finish(), db.finish(), None)
 
 

@@ -17,7 +17,7 @@ import torch
 
 from . import _lib
 from . import functional as Fn
-from .functional import _flat, _grad_like, _io_dtype, _need_cuda, _param_dtype, _ptr, _stream, _timed, grad_slot
+from .functional import _flat, _grad_like, _io_dtype, _need_cuda, _param_dtype, _ptr, _stream, _timed
 
 
 class LowRankPack:
@@ -149,23 +149,15 @@ class _LowRankProjFn(torch.autograd.Function):
         # (ii) rows kernel (dh, dq, dpre from the saved activations) + weight gradients
         r = pk_a.r
         rg = pk_g.r if gated else 0
-        nh2 = 2 * n_heads
-        # down w (the heads stacked), down b, up w, up b, then the gate's four (None without a gate), as in functional._AdapterGateFn
-        slots = [grad_slot(params[0], (r, F_), block=True), grad_slot(params[n_heads], (r,), block=True),
-                 grad_slot(params[nh2], (d, r)), grad_slot(params[nh2 + 1], (d,))]
-        if gated:
-            slots += [grad_slot(params[nh2 + 2], (rg, F_)), grad_slot(params[nh2 + 3], (rg,)),
-                      grad_slot(params[nh2 + 4], (d, rg)), grad_slot(params[nh2 + 5], (d,))]
+        slots = Fn.AdapterSlots(params, n_heads, r, rg, d, d_in=F_)
         nws = lib.vlpet_lowrank_bwd_workspace_bytes(M, F_, d, pk_a.tiles, io)
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
         rc = _timed("f4_bwd", M, lambda: lib.vlpet_lowrank_gate_bwd(
             dfe.data_ptr(), ff.data_ptr(), act.data_ptr(), pk_a.buf.data_ptr(), pk_g.buf.data_ptr() if gated else None,
-            *(sl.ptr for sl in slots), *((None,) * (8 - len(slots))),
-            r, rg, ws.data_ptr(), nws, M, F_, d, pk_a.tiles, gate_residual, io, _stream()))
+            *slots.ptrs(), r, rg, ws.data_ptr(), nws, M, F_, d, pk_a.tiles, gate_residual, io, _stream()))
         ctx.act = None
         _lib.check(rc, "vlpet_lowrank_gate_bwd")
-        grads = slots[0].finish_heads(params[:n_heads]) + slots[1].finish_heads(params[n_heads:nh2]) + [sl.finish() for sl in slots[2:]]
-        grads += [_grad_like(s[0], params[-2]), _grad_like(s[1], params[-1])]
+        grads = slots.finish(params, n_heads) + [_grad_like(s[0], params[-2]), _grad_like(s[1], params[-1])]
         dR = dout.reshape(rshape).to(rdtype) if ctx.needs_input_grad[1] else None      # the residual joins after the norm
         return (None, dR, None, None, None, None, None, *grads)
 
