@@ -3,7 +3,7 @@
 around N back-to-back calls, at the configs[1] / configs[2] shapes: the encoder's self-attention of the four tasks, then the decoder's
 self- and cross-attention at the benchmark's target lengths (TARGET_LEN 5 / 5 / 2 / 20: one query block, csrc/attn_bwd_fewq.hip).
 tools/attnbench.py's "bwd" column is (fwd + bwd) - fwd of autograd.grad and bottoms out near 100 us of host time; this is the kernel.
-VLPET_LIB selects the build (vl-pet_amd/_lib.py); with the diagnosis library, VLPET_ATTN_FEWQ=0 keeps the decoder rows on attn_bwd_kernel."""
+VLPET_LIB selects the build (vl-pet_amd/_lib.py)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -41,25 +41,8 @@ def main():
                                                   M, d, tiles, 1, 1.0, 1.0, 1.0, io, st); assert rc == 0
         return f
     bwd_saved(1 | 4)()
-    if tag != "modes":
-        t = timeit(bwd_saved(2 | 4), iters=100, warm=10)
-        print(f"wgbench M={M} {tag}: wgrad+finalize {t:7.1f} us")
-        return
-    # experiment build (VLPET_LIB=..._exp.so): the mode switches are read at every launch, so one process / one set of buffers
-    modes = [("base", 0, 0), ("stream: no stores", 0, 1), ("stream: no products", 0, 2), ("stream: no products, no stores", 0, 3),
-             ("stream: X pieces only", 0, 3 + 4), ("stream: P pieces only", 0, 3 + 8)]
-    # reference: what plain streaming kernels reach on this box at the same footprint (4 x [M, 768] bf16 read)
-    big = torch.randn(4 * M, d, device=dev).to(dt); o2 = torch.empty(M, d, device=dev, dtype=dt)
-    t = timeit(lambda: big.sum(dtype=torch.float32), iters=30, warm=3)
-    print(f"reference: torch sum over {big.numel() * 2 / 1e6:.0f} MB: {t:7.1f} us = {big.numel() * 2 / t / 1e3:7.0f} GB/s read")
-    t = timeit(lambda: torch.add(x1, x2, out=o2), iters=30, warm=3)
-    print(f"reference: torch add, 3 x {x1.numel() * 2 / 1e6:.0f} MB: {t:7.1f} us = {3 * x1.numel() * 2 / t / 1e3:7.0f} GB/s read + write")
-    del big
-    for rep in range(2):
-        for name, fm, wm in modes:
-            os.environ["VLPET_FIN_MODE"] = str(fm); os.environ["VLPET_WGS_MODE"] = str(wm)
-            t = timeit(bwd_saved(2 | 4), iters=60, warm=5)
-            print(f"rep {rep} {name:48s} {t:7.1f} us")
+    t = timeit(bwd_saved(2 | 4), iters=100, warm=10)
+    print(f"wgbench M={M} {tag}: wgrad+finalize {t:7.1f} us")
 
 if __name__ == "__main__":
     main()

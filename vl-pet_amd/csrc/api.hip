@@ -172,7 +172,7 @@ extern "C" int vlpet_set_seed_counter(const uint64_t* device_counter) {
 // backward op 137.5 vs 138.9 us; at the per-rank sizes of an 8-GPU run (1,900-5,800 rows, replayed graph) 5.45 / 5.47 ms per step with it
 // against 5.43 / 5.43 without -- so small launches keep the finalize launch
 static bool k1_in_launch_reduce(int64_t M) {
-    return vlpet_tuning().cols_red != 0 && (vlpet_tuning().cols_red == 2 || M >= 8192);
+    return M >= 8192;
 }
 
 // p in [0, 1): explicit mask (keep_mask != NULL) or the in-kernel generator keyed by `seed`; p == 0: no dropout
@@ -247,7 +247,7 @@ static int run_fwd(const void* xa, const void* res, const void* xg, const void* 
     // training form, bf16: two passes with the weights resident in registers where that form is the faster one
     if (const int f2 = vlpet_tuning().fwd2p; f2 != 0 && k1_fwd2p_applies(a, io_dtype == VLPET_F32) && (f2 > 0 || k1_fwd2p_preferred(a)))
         return herr(launch_k1_fwd2p(a, f2 == 2 ? 1 : f2 == 3 ? 2 : 3, (hipStream_t)stream));
-    if ((flags & PET_GATE) && !(a.dbg & 64))      // two-chain gate forward: one wave per chain (VLPET_DBG=64: single-wave form)
+    if (flags & PET_GATE)      // two-chain gate forward: one wave per chain
         return herr(launch_pet_gate_fwd(a, io_dtype == VLPET_F32, (hipStream_t)stream));
     return herr(launch_pet_fwd(a, io_dtype == VLPET_F32, (hipStream_t)stream));
 }
@@ -456,7 +456,7 @@ static int run_bwd(const void* dy, const void* xa, const void* res, const void* 
     const bool rows2 = !two_pass && pet_gate_bwd2_applies(b);
     // without a gate (K2, adapter-only K1, K3 without dropout), bf16, saved activations, whole call: pass 1 (dpre) + the
     // column-parallel pass of pet_cols_ng.hip (dx and both weight gradients from one read of dy and x)
-    const bool ng2 = !gate && phases == 3 && vlpet_tuning().ng2 != 0 && ng_two_pass_applies(b, io_dtype == VLPET_F32);
+    const bool ng2 = !gate && phases == 3 && ng_two_pass_applies(b, io_dtype == VLPET_F32);
     // round 6: pass 2 sums its row-chunk partials inside the launch (cols_reduce.h) -- no finalize launch; `phases` bit 5 keeps the
     // round-3 two-launch form where other kernels may run beside the call (k1_in_launch_reduce; the results are bit-identical)
     const bool red4 = cols4 && !cols6 && !(phases & 32) && k1_in_launch_reduce(M);
@@ -483,7 +483,7 @@ static int run_bwd(const void* dy, const void* xa, const void* res, const void* 
     }
     if (phases & 1) {
         if (rows2) b.dxg_in = dx1_in;                   // the chain-split row kernel adds it in its epilogue
-        const bool dz2 = two_pass && vlpet_tuning().dz2 != 0 && k1_dz2_applies(b, io_dtype == VLPET_F32);
+        const bool dz2 = two_pass && k1_dz2_applies(b, io_dtype == VLPET_F32);
         if (dz2 && gate) {      // small M: feature blocks (their fp32 partial dz in the dh / dq area, which the two-pass form does not use)
             const int nfb = k1_dz2_feature_blocks(M, d);
             const size_t need = (size_t)nfb * (size_t)M * 2 * 32 * tiles * 4;
@@ -901,7 +901,7 @@ static void visproj_wgrad_plan(int64_t M, int feat_dim, int d_out, int* RT, int*
 // fp32 path needs a few MB.  The size is asked for per IO dtype; the dtype-less entry point returns the larger of the two.
 extern "C" size_t vlpet_visproj_wgrad_workspace_bytes_io(int64_t M, int feat_dim, int d_out, int io_dtype) {
     if (M <= 0 || feat_dim <= 0 || d_out <= 0 || !dtype_ok(io_dtype)) return 0;
-    if (vlpet_tuning().k4_wgrad2 != 0 && k4_wgrad2_applies(M, feat_dim, d_out, io_dtype == VLPET_F32))
+    if (k4_wgrad2_applies(M, feat_dim, d_out, io_dtype == VLPET_F32))
         return align256(k4_wgrad2_workspace_bytes(M, feat_dim, d_out));
     int RT, pcols, rc; int64_t rpc;
     visproj_wgrad_plan(M, feat_dim, d_out, &RT, &pcols, &rc, &rpc);
@@ -920,7 +920,7 @@ extern "C" int vlpet_visproj_wgrad(const void* dpre, const void* feats, float* d
     if (M <= 0 || d_out % 32 != 0 || feat_dim <= 0 || feat_dim % 64 != 0) return VLPET_E_SHAPE;
     if (!dtype_ok(io_dtype)) return VLPET_E_DTYPE;
     if (!aligned16(dpre) || !aligned16(feats) || !aligned16(workspace)) return VLPET_E_ALIGN;
-    if (vlpet_tuning().k4_wgrad2 != 0 && k4_wgrad2_applies(M, feat_dim, d_out, io_dtype == VLPET_F32)) {   // tiled split-K GEMM (round 3)
+    if (k4_wgrad2_applies(M, feat_dim, d_out, io_dtype == VLPET_F32)) {   // tiled split-K GEMM (round 3)
         if (workspace_bytes < k4_wgrad2_workspace_bytes(M, feat_dim, d_out)) return VLPET_E_WORKSPACE;
         return herr(launch_k4_wgrad2(dpre, feats, dw, db, workspace, M, feat_dim, d_out, (hipStream_t)stream));
     }

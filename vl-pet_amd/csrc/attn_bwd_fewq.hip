@@ -17,11 +17,9 @@
 //
 // The arithmetic is attn_bwd_kernel's, operation for operation (tests/attn_spec.py chain(rounded=True)): the same MFMA chains per output
 // element, the same elementwise expressions, delta summed in the same order.
-// attn_bwd_fewq_kernel<true> (diagnosis builds, VLPET_ATTN_FEWQ=2): dS for dQ from a second, swapped evaluation of the tile instead of the LDS pass.
 #include "common.h"
 #include "kernels.h"
 #include "attn_common.h"
-#include "tuning.h"
 
 #define AT_FQ 4                        // waves per workgroup: one (batch, head) pair each
 #define AT_DS_ROW 72                   // bytes per row of the dS tile: 32 queries as bf16 + 8 of padding (8-byte aligned; conflict-free 8-byte writes)
@@ -75,7 +73,6 @@ __device__ __forceinline__ void fewq_put_tile(uint8_t* Kt, bf16x8 (&vf)[4], cons
     for (int ks = 0; ks < 4; ++ks) vf[ks] = r.vf[ks];
 }
 
-template <bool TWICE>
 __global__ __launch_bounds__(AT_FQ * 64, 2) void attn_bwd_fewq_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -207,7 +204,7 @@ __global__ __launch_bounds__(AT_FQ * 64, 2) void attn_bwd_fewq_kernel(AttnArgs a
         }
         // ---- dQ^T += K^T dS: dS with lane = query
         bf16x8 qf[2];
-        if constexpr (!TWICE) {
+        {
             // registers 4 g .. 4 g + 3 of the lane's key = queries 8 g + 4 hh + {0..3}: eight bytes of row `key` of the [key][query] tile
             typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 #pragma unroll
@@ -218,34 +215,6 @@ __global__ __launch_bounds__(AT_FQ * 64, 2) void attn_bwd_fewq_kernel(AttnArgs a
             asm volatile("" ::: "memory");
 #pragma unroll
             for (int u = 0; u < 2; ++u) qf[u] = tr_ds_tile(dsT, 16 * u, lane);
-        } else {
-            // the swapped form (attn.hip bwd_q_unit): D[key][query], lane = query m, registers = keys 32 t + ir + 4 hh
-            f32x16 s2 = zero16(), dp2 = zero16();
-#pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                s2 = mfma32(nat_frag(Kt, m, ks, hh), nat_frag(Qs, m, ks, hh), s2);
-                dp2 = mfma32(vf[ks], nat_frag(Ds, m, ks, hh), dp2);
-            }
-            const float l2 = rowt[m], dl2 = rowt[32 + m];
-            const uint32_t kg0 = __float_as_uint(rowt[64 + m]) + (uint32_t)(32 * t + 4 * hh) * AT_GOLD;
-            const int ict = m + coff - 4 * hh - 32 * t;              // masked iff 32 t + ir + 4 hh > m + coff
-            const float* kvp = kval + 32 * t + 4 * hh;
-#pragma unroll
-            for (int q4 = 0; q4 < 4; ++q4) {
-                const f32x4 kv = *reinterpret_cast<const f32x4*>(kvp + 8 * q4);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const int r = 4 * q4 + e, ir = e + 8 * q4;
-                    float x = fmaf(s2[r], sc2, kv[e] - l2);
-                    x = ir > ict ? -INFINITY : x;
-                    const float p = fast_exp2(x);
-                    const bool kp = hash_elem(kg0 + (uint32_t)ir * AT_GOLD) >= thr;
-                    const float g = kp ? dp2[r] * inv_keep : 0.f;
-                    dp2[r] = p * (g - dl2) * scale;
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < 2; ++u) qf[u] = acc_frag(dp2, u);
         }
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
@@ -263,20 +232,12 @@ __global__ __launch_bounds__(AT_FQ * 64, 2) void attn_bwd_fewq_kernel(AttnArgs a
     store_rows_T(stg, dq0, dq1, a.dq + qoff, rq, 0, a.Lq, lane);
 }
 
-template <bool TWICE>
-static hipError_t launch_fewq(const AttnArgs& a, hipStream_t stream) {
-    auto kern = attn_bwd_fewq_kernel<TWICE>;
+hipError_t launch_attn_bwd_fewq(const AttnArgs& a, hipStream_t stream) {
+    if (a.Lq > 32 || a.Lk > 128 || a.bias != nullptr) return hipErrorInvalidValue;
+    auto kern = attn_bwd_fewq_kernel;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)FewqLds::bytes);
     if (e != hipSuccess) return e;
     const unsigned pairs = (unsigned)(a.B * a.H);
     hipLaunchKernelGGL(kern, dim3((pairs + AT_FQ - 1) / AT_FQ), dim3(AT_FQ * 64), FewqLds::bytes, stream, a);
     return hipGetLastError();
-}
-
-hipError_t launch_attn_bwd_fewq(const AttnArgs& a, hipStream_t stream) {
-    if (a.Lq > 32 || a.Lk > 128 || a.bias != nullptr) return hipErrorInvalidValue;
-#if VLPET_IS_DEBUG_BUILD
-    if (vlpet_tuning().attn_fewq == 2) return launch_fewq<true>(a, stream);
-#endif
-    return launch_fewq<false>(a, stream);
 }

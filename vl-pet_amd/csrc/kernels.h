@@ -53,7 +53,7 @@ struct PetFwdArgs {
     float gm, go;              // gate value = gm * sigmoid(.) + go  (gated: gm = 1, go = 1 with use_visual_projector_residual_connection
                                //   else 0; ungated projector: gm = 0, go = 1)
 };
-hipError_t launch_pet_fwd(const PetFwdArgs& a, int io_fp32, hipStream_t stream);
+hipError_t launch_pet_fwd(const PetFwdArgs& a, int io_fp32, hipStream_t stream);        // single chain (K2 / K3); PET_GATE: hipErrorInvalidValue
 hipError_t launch_pet_gate_fwd(const PetFwdArgs& a, int io_fp32, hipStream_t stream);   // PET_GATE only
 hipError_t launch_pet_lowrank_fwd(const PetFwdArgs& a, int io_fp32, hipStream_t stream);   // low-rank visual projector form (d_in != d)
 // gated K1 forward, training form, as two passes with the weights resident in registers (pet_fwd2p.hip; bf16, d = 768)

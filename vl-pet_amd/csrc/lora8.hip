@@ -30,11 +30,7 @@ typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
 typedef __attribute__((ext_vector_type(2))) unsigned int u32x2;
 
 __device__ __forceinline__ float dot2_bf16(uint32_t a, uint32_t b, float c) {
-#ifdef L8_NO_DOT2
-    return __uint_as_float(a << 16) * __uint_as_float(b << 16) + (__uint_as_float(a & 0xffff0000u) * __uint_as_float(b & 0xffff0000u) + c);
-#else
     return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2_t, a), __builtin_bit_cast(bf16x2_t, b), c, false);
-#endif
 }
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
     const bf16x2_t v = {(__bf16)lo, (__bf16)hi};
@@ -197,10 +193,7 @@ bool lora8_applies(int64_t M, int d, int r, int io_fp32) {
 template <int NCH>
 static hipError_t launch_lora8_n(const Lora8Args& a, hipStream_t stream) {
     const int blocks = tail_blocks(a.M);
-#ifndef VLPET_LORA8_GENERAL      // (-DVLPET_LORA8_GENERAL=1: every dropout launch on the any-source form, the round-4 behaviour, for A/B)
-#define VLPET_LORA8_GENERAL 0
-#endif
-    if (!VLPET_LORA8_GENERAL && drop_active(a.drop) && a.drop.keep == nullptr && a.drop.bits == nullptr)
+    if (drop_active(a.drop) && a.drop.keep == nullptr && a.drop.bits == nullptr)
         hipLaunchKernelGGL((lora8_fwd_kernel<NCH, 1>), dim3(blocks), dim3(L8_WAVES * 64), 0, stream, a);
     else if (drop_active(a.drop)) hipLaunchKernelGGL((lora8_fwd_kernel<NCH, 2>), dim3(blocks), dim3(L8_WAVES * 64), 0, stream, a);
     else hipLaunchKernelGGL((lora8_fwd_kernel<NCH, 0>), dim3(blocks), dim3(L8_WAVES * 64), 0, stream, a);

@@ -44,12 +44,9 @@ __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
 // the packed weights).  Measured here (profiles/r02_k1bench_nt_row_loads.txt, r02_bench_instep_nt_row_loads_ab.txt): with cold inputs
 // K1 forward 70.6 -> 57.9 us, backward rows 97.0 -> 85.5, weight gradients 84.6 -> 60.9 at M = 28,000 (warm, i.e. a microbenchmark
 // re-reading its own previous iteration from the Infinity Cache, 3-10 % slower); in the training step 23.3 k -> 23.7 k samples/s.
-// -DVLPET_ROW_AUX=0 builds the default-policy variant for A/B.
-#ifndef VLPET_ROW_AUX
-#define VLPET_ROW_AUX 2
-#endif
+constexpr int ROW_AUX = 2;
 __device__ __forceinline__ void glds16_row(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gmem_cv*)gsrc, (lmem_v*)lds_wave_base, 16, 0, VLPET_ROW_AUX);
+    __builtin_amdgcn_global_load_lds((gmem_cv*)gsrc, (lmem_v*)lds_wave_base, 16, 0, ROW_AUX);
 }
 
 // ---- row tiles: [rows][8 slots of 16 B]; slot = piece ^ swz(row), swizzle applied on the SOURCE side

@@ -43,14 +43,6 @@ struct BwdLds {
     static size_t bytes(int d) { return (size_t)BIAS_OFF + (size_t)2 * (32 * RT + d) * 4; }
 };
 
-#ifdef VLPET_STAMPS
-// diagnosis build only (-DVLPET_STAMPS): cycle stamps of wave 0 of workgroup 0, printed after the launch when VLPET_DBG & 16
-__device__ unsigned long long g_bwd_ts[64];
-#define BSTAMP(k) do { if (blockIdx.x == 0 && threadIdx.x == 0) g_bwd_ts[k] = __builtin_readcyclecounter(); } while (0)
-#else
-#define BSTAMP(k) do { } while (0)
-#endif
-
 template <typename IO, int RT, bool GATE, bool ACT_ID, bool DROP, int WAVES>
 __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
     using G = Geo4<IO>;
@@ -196,7 +188,6 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
     // with the forward's saved activations phase 1 (stages 0 .. S-1) does not exist
     const bool use_saved = a.saved != nullptr;      // (K3: z only -- the identity activation has no act'(pre) to save)
     const int S0 = use_saved ? S : 0;
-    BSTAMP(0);
     issue_w(S0);
     issue_rows(S0, S0);
     issue_rows(S0 + 1, S0);
@@ -251,12 +242,9 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
 
     // ---- phase 1: recompute the bottleneck pre-activations of both chains
     int s = S0;
-    BSTAMP(1);
     for (; s < S; ++s) {
-        if (s == 5) BSTAMP(8);
         const Plan pl = plan(s);
         emit(pl, 0, NPIECE);
-        if (s == 5) BSTAMP(9);
         const uint8_t* w = slot_w(s & 1);
         const uint8_t* ta = slot_t0(s % L::NR);
         const uint8_t* tg = slot_t1(s % L::NR);
@@ -305,13 +293,9 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
             }
             if constexpr (PIPE) { if (u + 1 < G::KU) cur = nxt; }
         }
-        if (s == 5) BSTAMP(10);
         wait_vm(rows_count(s + 2, s));
-        if (s == 5) BSTAMP(11);
         __builtin_amdgcn_s_barrier();
-        if (s == 5) BSTAMP(12);
     }
-    BSTAMP(2);
 
     // z = act(pre) as B fragments; accA / accG are overwritten with act'(pre)
     if (!use_saved) {
@@ -357,14 +341,11 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
 #pragma unroll
         for (int ct = 0; ct < RT; ++ct) dzG[ct] = zero16();
     }
-    BSTAMP(3);
     for (int su = 0; su < S; ++su) {
         Frag<NS> dfA[G::E4], dfG[G::E4];
         if constexpr (GATE) {
-            if (su == 5) BSTAMP(16);
             const Plan pl = plan(s);
         emit(pl, 0, NPIECE);
-            if (su == 5) BSTAMP(17);
             const uint8_t* w = slot_w(s & 1);
             uint8_t* t0 = slot_t0(s % L::NR);
             uint8_t* t1 = slot_t1(s % L::NR);
@@ -409,7 +390,6 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
                     if constexpr (PIPE) { if (ks + 1 < KT) cur = nxt; }
                 }
             }
-            if (su == 5) BSTAMP(18);
             // elementwise backward in fragment-sized steps (8 features): dh / dq are staged in place of the res / dy
             // rows of this wave and become the B fragments of the feature contraction (dh itself: the delta scale of
             // dz = sd * Wu^T dh is applied once to dz after the phase).  The multiplicative / additive forms are two
@@ -442,14 +422,10 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
                 }
             };
             if (gate_add) elementwise(BoolK<true>{}); else elementwise(BoolK<false>{});
-            if (su == 5) BSTAMP(19);
             store_rows4(DH, rl, su * 128, t0, wave, lane);
             store_rows4(DQ, rl, su * 128, t1, wave, lane);
-            if (su == 5) BSTAMP(20);
             wait_vm(rows_count(s + 2, s) + 2 * rl.n_inst);
-            if (su == 5) BSTAMP(21);
             __builtin_amdgcn_s_barrier();
-            if (su == 5) BSTAMP(22);
             ++s;
         }
         {
@@ -492,14 +468,11 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
                     if constexpr (PIPE) { if (e + 1 < G::E4) cur = nxt; }
                 }
             }
-            if (su == 5) BSTAMP(23);
             wait_vm(rows_count(s + 2, s));
             __builtin_amdgcn_s_barrier();
-            if (su == 5) BSTAMP(24);
             ++s;
         }
     }
-    BSTAMP(4);
 
     if constexpr (GATE) {
         // The dh rows of phase 3 are read back from the dh side product this wave stored itself: once those stores
@@ -555,9 +528,7 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
         // to know how many of those predicated stores this wave really issued)
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    BSTAMP(5);
     for (int su = 0; su < S; ++su, ++s) {
-        if (su == 5) BSTAMP(32);
         const Plan pl = plan(s);
         emit(pl, 0, NPIECE);
         const uint8_t* w = slot_w(s & 1);
@@ -596,7 +567,6 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
                 if constexpr (PIPE) { if (ks + 1 < KT) cur = nxt; }
             }
         }
-        if (su == 5) BSTAMP(33);
         uint32_t kp[4] = {0, 0, 0, 0};
         if constexpr (DROP) {
 #pragma unroll
@@ -620,12 +590,9 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
         }
         store_rows4(dxa, rl, su * 128, t0, wave, lane);
         if constexpr (GATE) store_rows4(dxg, rl, su * 128, t1, wave, lane);
-        if (su == 5) BSTAMP(34);
         wait_vm(rows_count(s + 2, s) + (GATE ? 2 : 1) * rl.n_inst);
         __builtin_amdgcn_s_barrier();
-        if (su == 5) BSTAMP(35);
     }
-    BSTAMP(6);
 }
 
 template <typename IO, int RT, bool GATE, bool ACT_ID, bool DROP, int WAVES>
@@ -639,18 +606,6 @@ static hipError_t launch_one(const PetBwdArgs& a, hipStream_t stream) {
     const int rows = WAVES * 32;
     const int blocks = (int)((a.M + rows - 1) / rows);
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(WAVES * 64), lds, stream, a);
-#ifdef VLPET_STAMPS
-    if ((vlpet_tuning().dbg & 16) && GATE) {
-        (void)hipDeviceSynchronize();
-        unsigned long long t[64];
-        (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_bwd_ts), sizeof(t));
-        auto d = [&](int i, int j) { return (long long)(t[j] - t[i]); };
-        fprintf(stderr, "[vlpet bwd ts] prologue=%lld phase1=%lld gelu=%lld phase2=%lld dpre=%lld phase3=%lld | p1 stage: issue=%lld mfma=%lld wait=%lld barrier=%lld | "
-                        "gate stage: issue=%lld mfma=%lld elementwise=%lld stores=%lld wait=%lld barrier=%lld contraction stage=%lld | p3 stage: issue=%lld mfma=%lld rest=%lld\n",
-                d(0, 1), d(1, 2), d(2, 3), d(3, 4), d(4, 5), d(5, 6), d(8, 9), d(9, 10), d(10, 11), d(11, 12),
-                d(16, 17), d(17, 18), d(18, 19), d(19, 20), d(20, 21), d(21, 22), d(22, 24), d(32, 33), d(33, 34), d(34, 35));
-    }
-#endif
     return hipGetLastError();
 }
 

@@ -43,16 +43,6 @@ template <int RT, bool HAS_IN = false> struct ColzGeo {
     static constexpr size_t lds(int nstg) { return (size_t)nstg * STG_B + 2 * 8192 + DQ_B + BIAS_B; }    // ring, dh (x2), dq, biases
 };
 
-#ifndef VLPET_COLS_GRP
-#define VLPET_COLS_GRP 6
-#endif
-#ifndef VLPET_COLS_WGBOTH
-#define VLPET_COLS_WGBOTH 1
-#endif
-#ifndef VLPET_COLS_EWAHEAD
-#define VLPET_COLS_EWAHEAD 1
-#endif
-
 template <int RT, int NSTG, bool ADD, bool HAS_IN>
 __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
     using GEO = ColzGeo<RT, HAS_IN>;
@@ -62,9 +52,9 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
     constexpr int NW = NX + RT;                         // global_load_lds instructions per wave and stage
     // LDS round trips are what a step's instruction stream waits for (a wave alone covers none of them), so operands are
     // requested in batches as large as the registers allow and each batch is waited for once:
-    constexpr int GRP = VLPET_COLS_GRP < KT ? (KT % VLPET_COLS_GRP == 0 ? VLPET_COLS_GRP : KT) : KT;   // B fragments per batch of a projection
-    constexpr bool WG_BOTH = VLPET_COLS_WGBOTH != 0;    // both 16-row k-steps of a weight-gradient job in one batch
-    constexpr bool EW_AHEAD = VLPET_COLS_EWAHEAD != 0;  // all dy / x2 pieces of the elementwise stage requested at once
+    constexpr int GRP = 6 < KT ? (KT % 6 == 0 ? 6 : KT) : KT;   // B fragments per batch of a projection: six where that divides the k-steps
+    constexpr bool WG_BOTH = true;                      // both 16-row k-steps of a weight-gradient job in one batch
+    constexpr bool EW_AHEAD = true;                     // all dy / x2 pieces of the elementwise stage requested at once
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     // ---- which (column block, row chunk): the column blocks of a row chunk share an XCD (they re-read the same bottleneck rows)
@@ -270,12 +260,6 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");          // weights in registers, biases in LDS (and the first stages landed)
 #pragma unroll
     for (int ks = 0; ks < KT; ++ks) { asm volatile("" : "+v"(wA[ks])); asm volatile("" : "+v"(wG[ks])); }   // (hipcc's own guard of these loads lands here, not in the first step)
-#ifdef VLPET_COLS_STAMPS      // diagnosis build: wall-clock time per phase, summed over the steps, printed by one wave of each side
-    uint64_t tacc[5] = {0, 0, 0, 0, 0}, tlast = wall_clock64();
-#define COLS_STAMP(k) { const uint64_t tn = wall_clock64(); tacc[k] += tn - tlast; tlast = tn; }
-#else
-#define COLS_STAMP(k)
-#endif
 
     // The only hand-off between the roles is the dh tile (U -> D, for dx2 = s2*dh + ..).  It is double-buffered OUTSIDE the
     // ring and consumed one step late: D finishes the input gradients of step s - 1 at the start of step s, so the one barrier
@@ -300,12 +284,7 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
             const int valid = (int)(r_end - (r_begin + 32 * (int64_t)s));
             const uint32_t sb = lds0 + (uint32_t)((s % NSTG) * STG_B);
             const uint32_t dh0 = lds0 + (uint32_t)(DH_OFF + (s & 1) * 8192);
-            COLS_STAMP(4)
             step_top(s, 0);
-            COLS_STAMP(0)
-#if defined(VLPET_COLS_ABL) && (VLPET_COLS_ABL & 8)
-            continue;                                                     // (timing ablation: the LDS-DMA stream + barriers alone)
-#endif
             // up projection of one chain, starting at its bias: the bias values and the first batch of B fragments are one LDS batch
             auto project_up = [&](auto TC, auto OC, const bf16x8* w, f32x16& acc) {
                 constexpr int T = decltype(TC)::value;
@@ -336,10 +315,6 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
                 f32x16 aA, aG;                                            // both up projections
                 project_up(I0{}, I0{}, wA, aA);
                 project_up(I1{}, std::integral_constant<int, 512>{}, wG, aG);
-#ifdef VLPET_COLS_STAMPS
-                asm volatile("s_nop 0" : "+v"(aA[15]), "+v"(aG[15]));
-#endif
-                COLS_STAMP(1)
                 const float gsr = m < valid ? a.gs : 0.f;                 // rows past the end: dh = dq = 0
                 u32x2 dyv[4], x2v[4];
                 if constexpr (EW_AHEAD) {                                 // (requested while the projections' MFMAs run)
@@ -349,10 +324,6 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
                     });
                     asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dyv[0]), "+v"(x2v[0]), "+v"(dyv[1]), "+v"(x2v[1]), "+v"(dyv[2]), "+v"(x2v[2]), "+v"(dyv[3]), "+v"(x2v[3]) :: "memory");
                 }
-#if defined(VLPET_COLS_ABL) && (VLPET_COLS_ABL & 4)
-                asm volatile("" :: "v"(aA[0]), "v"(aG[0]), "v"(dyv[0]), "v"(x2v[0]));
-                if (false)
-#endif
                 sfor<4>([&](auto C) {                                     // 4 columns at a time (a small live set): dy, x2 in, dh, dq out
                     constexpr int c = C.value;
                     if constexpr (!EW_AHEAD) {
@@ -387,11 +358,8 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
             }
             // this wave's own columns of dh, dq: its writes above are ordered before these reads by the waits in between
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            COLS_STAMP(2)
-#if !(defined(VLPET_COLS_ABL) && (VLPET_COLS_ABL & 1))
             wg_products(sb, I0{}, I0{}, dh0 + a_xtr[0], dh0 + a_xtr[1], accA, 0);
             wg_products(sb, I1{}, I0{}, dq0 + a_xtr[0], dq0 + a_xtr[1], accG, 1);
-#endif
             if (want_csp) {                                               // its own block (inside the products it would make every accumulator a phi)
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
@@ -408,16 +376,7 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // (every LDS access of this step is complete at the next barrier)
-#ifdef VLPET_COLS_STAMPS
-            asm volatile("s_nop 0" : "+v"(accA[RT - 1][15]), "+v"(accG[RT - 1][15]));
-#endif
-            COLS_STAMP(3)
         }
-#ifdef VLPET_COLS_STAMPS
-        if (lane == 0 && wave == 0 && (blockIdx.x == 0 || blockIdx.x == 101))
-            printf("cols stamps U blk %d (10 ns units, %d steps): top %llu up %llu ew %llu wgrad %llu other %llu\n", (int)blockIdx.x, nsteps,
-                   (unsigned long long)tacc[0], (unsigned long long)tacc[1], (unsigned long long)tacc[2], (unsigned long long)tacc[3], (unsigned long long)tacc[4]);
-#endif
         __builtin_amdgcn_s_barrier();                                     // the last dh tile is visible to role D
         if (a.red.slab != nullptr) {                                      // (in-launch reduce: write-through partials, cols_reduce.h)
             if (h == 0) {
@@ -498,40 +457,19 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
 #pragma unroll 1
         for (int s = 0; s < nsteps; ++s) {
             const uint32_t sb = lds0 + (uint32_t)((s % NSTG) * STG_B);
-            COLS_STAMP(4)
             step_top(s, s >= 2 ? 4 : 0);
-            COLS_STAMP(0)
-#if defined(VLPET_COLS_ABL) && (VLPET_COLS_ABL & 8)
-            continue;
-#endif
-#if !(defined(VLPET_COLS_ABL) && (VLPET_COLS_ABL & 2))
             if (s > 0) finish(s - 1, dinA, dinB);
-#endif
-            COLS_STAMP(1)
             if constexpr (HAS_IN) {
                 lds_read16<3 * 8192>(dinA, sb + a_xcl[0]); lds_read16<3 * 8192>(dinB, sb + a_xcl[1]);
                 lgkm_fence(dinA); lgkm_tie(dinB);
             }
             wg_products(sb, I2{}, X2O{}, sb + a_xtr[0], sb + a_xtr[1], accA, -1);
             wg_products(sb, I3{}, X1O{}, sb + a_xtr[0], sb + a_xtr[1], accG, -1);
-#ifdef VLPET_COLS_STAMPS
-            asm volatile("s_nop 0" : "+v"(accA[RT - 1][15]), "+v"(accG[RT - 1][15]));
-#endif
-            COLS_STAMP(2)
             p2 = zero16(); p1 = zero16();
             project(sb, I2{}, wA, p2);
             project(sb, I3{}, wG, p1);
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#ifdef VLPET_COLS_STAMPS
-            asm volatile("s_nop 0" : "+v"(p1[15]), "+v"(p2[15]));
-#endif
-            COLS_STAMP(3)
         }
-#ifdef VLPET_COLS_STAMPS
-        if (lane == 0 && wave == 4 && (blockIdx.x == 0 || blockIdx.x == 101))
-            printf("cols stamps D blk %d (10 ns units, %d steps): top %llu finish %llu wgrad %llu project %llu other %llu\n", (int)blockIdx.x, nsteps,
-                   (unsigned long long)tacc[0], (unsigned long long)tacc[1], (unsigned long long)tacc[2], (unsigned long long)tacc[3], (unsigned long long)tacc[4]);
-#endif
         __builtin_amdgcn_s_barrier();                                     // role U has written the last dh tile
         if (nsteps > 0) finish(nsteps - 1, dinA, dinB);
     }

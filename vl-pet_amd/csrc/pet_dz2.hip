@@ -20,23 +20,14 @@
 #include "cols_common.h"
 
 // Cache policy of pass 1's row loads (dy, x2).  Pass 2 reads both tensors again right after this launch: with the non-temporal policy
-// of the other row streams (aux 2) pass 1 discourages exactly the lines pass 2 is about to ask for; -DVLPET_P1_AUX=0 = default policy.
-#ifndef VLPET_P1_AUX
-#define VLPET_P1_AUX 2
-#endif
+// of the other row streams (aux 2) pass 1 discourages exactly the lines pass 2 is about to ask for.
+constexpr int P1_AUX = 2;
 __device__ __forceinline__ void glds16_p1(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gmem_cv*)gsrc, (lmem_v*)lds_wave_base, 16, 0, VLPET_P1_AUX);
+    __builtin_amdgcn_global_load_lds((gmem_cv*)gsrc, (lmem_v*)lds_wave_base, 16, 0, P1_AUX);
 }
 
-#ifndef VLPET_DZ2_AW1
-#define VLPET_DZ2_AW1 2     // stages the weight / row requests run ahead at RT = 1 (LDS allows it); RT = 3: 1 / 1
-#define VLPET_DZ2_AX1 2
-#endif
-#ifndef VLPET_DZ2_SPREAD
-#define VLPET_DZ2_SPREAD 1
-#endif
 template <int RT> struct Dz2Geo {
-    static constexpr int AW = RT == 1 ? VLPET_DZ2_AW1 : 1, AX = RT == 1 ? VLPET_DZ2_AX1 : 1;
+    static constexpr int AW = RT == 1 ? 2 : 1, AX = RT == 1 ? 2 : 1;   // stages the weight / row requests run ahead: two at RT = 1 (LDS allows it)
     static constexpr int NWS = AW + 2, NXS = AX + 1;   // slots (a stage's weight image is used for two steps)
     static constexpr int PB = 64 * RT;                 // bytes of a weight row
     static constexpr int NPS = PB / 16;                // its 16-byte slots
@@ -62,7 +53,7 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
     constexpr int KT = 2 * RT;
     constexpr int PB = GEO::PB, NPS = GEO::NPS, WT_B = GEO::WT_B, XT_B = GEO::XT_B, WS_B = GEO::WS_B, XS_B = GEO::XS_B;
     constexpr int X_OFF = GEO::X_OFF, AW = GEO::AW, AX = GEO::AX, NWS = GEO::NWS, NXS = GEO::NXS;
-    constexpr bool SPREAD = VLPET_DZ2_SPREAD != 0;
+    constexpr bool SPREAD = true;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -151,12 +142,6 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
     for (int ct = 0; ct < RT; ++ct) { dzA[ct] = zero16(); dzG[ct] = zero16(); }
     const float s2 = a.s2, sd = a.sd, gs = a.gs;
 
-#ifdef VLPET_DZ2_STAMPS
-    uint64_t tacc[6] = {0, 0, 0, 0, 0, 0}, tlast = wall_clock64();
-#define DZ2_STAMP(k) { const uint64_t tn = wall_clock64(); tacc[k] += tn - tlast; tlast = tn; }
-#else
-#define DZ2_STAMP(k)
-#endif
     // ---- the pieces of a step
     // up projection of one chain over this wave's 32 features, starting at the bias
     auto project_up = [&](uint32_t sb, auto TC, const bf16x8* z, f32x16& acc, int bias_off) {
@@ -184,10 +169,6 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
         if (SPREAD && s + AX < S) issue_x1(s + AX, 0);     // the row requests of the stage ahead are spread over the step: up front,
         project_up(sb, std::integral_constant<int, 1>{}, zG, aG, (d + s * 64) * 4);
         if (SPREAD && s + AX < S) issue_x1(s + AX, 1);     // all 56 pieces of a workgroup queue at the texture path at once (~1 k cycles of blocked issue)
-#ifdef VLPET_DZ2_STAMPS
-        asm volatile("s_nop 0" : "+v"(aG[15]));
-#endif
-        DZ2_STAMP(2)
         u32x2 dyv[4], x2v[4];
         sfor<4>([&](auto Q) {
             lds_read8<0>(dyv[Q.value], xb + a_row[Q.value]);
@@ -224,10 +205,6 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
             bh[2 * q] = uh[0]; bh[2 * q + 1] = uh[1];
             bq[2 * q] = uq[0]; bq[2 * q + 1] = uq[1];
         });
-#ifdef VLPET_DZ2_STAMPS
-        asm volatile("s_nop 0" : "+v"(bq[7]), "+v"(bh[7]));
-#endif
-        DZ2_STAMP(3)
     };
     // contraction over this wave's 32 features of stage s: dz[ct] += W^T (transpose reads of the same image) . dh / dq
     auto contract1 = [&](uint32_t sb, auto TC, const uint32_t* bw, f32x16* dz) {
@@ -253,10 +230,6 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
         const uint32_t sb = lds0 + (uint32_t)((s % NWS) * WS_B);
         contract1(sb, std::integral_constant<int, 0>{}, bh, dzA);
         contract1(sb, std::integral_constant<int, 1>{}, bq, dzG);
-#ifdef VLPET_DZ2_STAMPS
-        asm volatile("s_nop 0" : "+v"(dzG[RT - 1][15]), "+v"(dzA[RT - 1][15]));
-#endif
-        DZ2_STAMP(4)
     };
     // the frame of a step: everything this wave requested for stage s has landed (nothing younger is in flight), barrier (stage s is
     // complete for every wave; the weight slot of stage s - 2 and the row slot of stage s - 1 are free), request stage s + 1
@@ -266,11 +239,8 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
         int n = (AW <= AX && AW < AX && s - AW + AX < S) ? 4 : 0;
 #pragma unroll
         for (int t = 1; t < AM; ++t) n += (s - t + AW < S ? RT : 0) + (s - t + AX < S ? 4 : 0);
-        DZ2_STAMP(5)
         vm_wait(n);
-        DZ2_STAMP(0)
         __builtin_amdgcn_s_barrier();
-        DZ2_STAMP(1)
         if (s + AW < S) issue_w(s + AW);
         if (!SPREAD && s + AX < S) issue_x(s + AX);
     };
@@ -339,12 +309,6 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
         contract(S - 1, bh, bq);
     }
 
-#ifdef VLPET_DZ2_STAMPS
-    if (lane == 0 && (blockIdx.x == 0 || blockIdx.x == 100) && (wave == 0 || wave == 4))
-        printf("dz2 stamps blk %d wave %d (10 ns units): vmwait %llu barrier %llu up %llu ew %llu contract %llu other %llu\n", (int)blockIdx.x, wave,
-               (unsigned long long)tacc[0], (unsigned long long)tacc[1], (unsigned long long)tacc[2], (unsigned long long)tacc[3],
-               (unsigned long long)tacc[4], (unsigned long long)tacc[5]);
-#endif
     // ---- the two feature halves of a row group meet: fh = 0 finishes chain A, fh = 1 chain G
     typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
     bf16x4 gpv[RT][4];                                                    // act'(pre) of the chain this wave finishes (requested now, used last)
@@ -433,7 +397,6 @@ hipError_t launch_k1_dz_reduce(const PetBwdArgs& a, int PR, hipStream_t stream) 
 // feature blocks of pass 1 by shape: the kernel is a chain of d / 64 stages whatever its rows, and below 8,192 rows fewer than 64 of
 // the 256 CUs have a workgroup -- four feature blocks give each a quarter of the chain (profiles/r04_k1bench_small_m.txt)
 int k1_dz2_feature_blocks(int64_t M, int d) {
-    if (const int f = vlpet_tuning().dz2_fsplit; f >= 1) return ((d >> 6) % f == 0) ? f : 1;
     return (M <= 8192 && (d >> 6) % 4 == 0) ? 4 : 1;
 }
 

@@ -17,25 +17,15 @@
 #include "cols_common.h"
 
 // Cache policy of pass 1's row loads (dy, x2).  Pass 2 reads both tensors again right after this launch: with the non-temporal policy
-// of the other row streams (aux 2) pass 1 discourages exactly the lines pass 2 is about to ask for; -DVLPET_P1_AUX=0 = default policy.
-#ifndef VLPET_P1_AUX
-#define VLPET_P1_AUX 2
-#endif
+// of the other row streams (aux 2) pass 1 discourages exactly the lines pass 2 is about to ask for.
+constexpr int P1_AUX = 2;
 __device__ __forceinline__ void glds16_p1(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gmem_cv*)gsrc, (lmem_v*)lds_wave_base, 16, 0, VLPET_P1_AUX);
+    __builtin_amdgcn_global_load_lds((gmem_cv*)gsrc, (lmem_v*)lds_wave_base, 16, 0, P1_AUX);
 }
 
-// A/B switches of the round-5 changes (tools/gpu/r5_q.sh builds the variants): first requests after the z / bias wait (rounds 4 order),
-// no use of the z registers at the wait, the epilogue's act' loads one at a time
-#ifndef VLPET_DZ6_LATE_ISSUE
-#define VLPET_DZ6_LATE_ISSUE 0
-#endif
-#ifndef VLPET_DZ6_PIN_Z
-#define VLPET_DZ6_PIN_Z 1
-#endif
-#ifndef VLPET_DZ6_EPI_SERIAL
-#define VLPET_DZ6_EPI_SERIAL 3      // 3 = act' rows through LDS (below); 1 = the rounds 4 form, one load at a time; 0 = all 48 act' loads first (measured SLOWER: 69.9 vs 62.1 us at 18,250 rows -- 96 more live registers cost the loop more
-#endif                              //     than the batched loads save; profiles/r05_k1bench_dz6_variants.txt); 2 = no act' loads at all (diagnosis: a lower bound)
+// Round 5 (profiles/r05_k1bench_dz6_variants.txt): the first requests go out before the z / bias wait, the z registers are pinned at the
+// wait, and the epilogue's act' rows come through LDS (all 48 act' loads first measured SLOWER: 69.9 vs 62.1 us at 18,250 rows -- 96 more
+// live registers cost the loop more than the batched loads save).
 template <int RT> struct Dz6Geo {
     static constexpr int PB = 64 * RT;                 // bytes of a weight row (one feature, all bottleneck columns)
     static constexpr int NPS = PB / 16;
@@ -191,10 +181,8 @@ __global__ __launch_bounds__(256) void k1_dz6_kernel(PetBwdArgs a) {
     };
 
     // the first half-stage's requests go out before this wave fetches its own z rows and the biases (see k1_dz2_kernel)
-#if !VLPET_DZ6_LATE_ISSUE
     issue_w(2 * S0);
     issue_x(S0);
-#endif
     // up-side biases -> LDS (fp32): [bu_a (d) | bu_g (d)]
     {
         float* sbias = reinterpret_cast<float*>(smem + GEO::BIAS_OFF);
@@ -215,17 +203,11 @@ __global__ __launch_bounds__(256) void k1_dz6_kernel(PetBwdArgs a) {
     }
 
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");          // z in registers, biases in LDS (and the first half-stage landed)
-#if VLPET_DZ6_PIN_Z
 #pragma unroll
     for (int ks = 0; ks < KT; ++ks) {                  // (a use here: hipcc's own guard of the z loads lands on the wait above, see k1_dz2_kernel)
         if constexpr (NEED_A) asm volatile("" : "+v"(zA[ks]));
         asm volatile("" : "+v"(zG[ks]));
     }
-#endif
-#if VLPET_DZ6_LATE_ISSUE
-    issue_w(2 * S0);
-    issue_x(S0);
-#endif
 
     // request order per step (what the counted waits rely on): half-stage (s, 0): W(2s + 1), X(s + 1); half-stage (s, 1): W(2s + 2)
 #pragma unroll 1
@@ -307,7 +289,6 @@ __global__ __launch_bounds__(256) void k1_dz6_kernel(PetBwdArgs a) {
     // every load behind the previous store (gp and out may alias for all it knows) -- 48 dependent memory round trips at the end of
     // every workgroup (round 5: found in the ISA, 48 x "global_load_dwordx2; s_waitcnt vmcnt(0)").
     typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-#if VLPET_DZ6_EPI_SERIAL == 3
     // The act' rows of a wave's 32 rows are 2 x 12 KiB of CONTIGUOUS memory ([M, 192] bf16): they come in by LDS-DMA -- no registers, one
     // memory latency for all of them -- into the (now free) stage rings, 24 KiB per wave, and are read back per piece.  16-byte chunk c of
     // row r sits at slot (c + r) mod 24 of the row (the DMA's LDS side is fixed per lane, so the rotation is applied to the SOURCE address):
@@ -361,57 +342,6 @@ __global__ __launch_bounds__(256) void k1_dz6_kernel(PetBwdArgs a) {
             }
         }
     }
-#elif VLPET_DZ6_EPI_SERIAL
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const uint8_t* sv = reinterpret_cast<const uint8_t*>(a.saved) + (t == 0 ? 1 : 3) * a.saved_stride;
-        const __bf16* gp = reinterpret_cast<const __bf16*>(sv) + grow * (int64_t)(32 * RT) + 4 * h;
-        __bf16* out = reinterpret_cast<__bf16*>(t == 0 ? a.dp_a : a.dp_g) + grow * (int64_t)(32 * RT) + 4 * h;
-        const float sc = t == 0 ? sd : 1.0f;
-#pragma unroll
-        for (int ct = 0; ct < RT; ++ct)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-#if VLPET_DZ6_EPI_SERIAL == 2
-                const bf16x4 g1 = {(__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f, (__bf16)1.0f};
-#else
-                const bf16x4 g1 = *reinterpret_cast<const bf16x4*>(gp + 32 * ct + 8 * q);
-#endif
-                bf16x4 r4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) r4[j] = (__bf16)(sc * (t == 0 ? dzA[ct][4 * q + j] : dzG[ct][4 * q + j]) * (float)g1[j]);
-                if (row_ok) *reinterpret_cast<bf16x4*>(out + 32 * ct + 8 * q) = r4;
-            }
-    }
-#else
-    bf16x4 gpv[2][RT][4];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const uint8_t* sv = reinterpret_cast<const uint8_t*>(a.saved) + (t == 0 ? 1 : 3) * a.saved_stride;
-        const __bf16* gp = reinterpret_cast<const __bf16*>(sv) + grow * (int64_t)(32 * RT) + 4 * h;
-#pragma unroll
-        for (int ct = 0; ct < RT; ++ct)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) gpv[t][ct][q] = __builtin_nontemporal_load(reinterpret_cast<const bf16x4*>(gp + 32 * ct + 8 * q));
-    }
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        __bf16* out = reinterpret_cast<__bf16*>(t == 0 ? a.dp_a : a.dp_g) + grow * (int64_t)(32 * RT) + 4 * h;
-        const float sc = t == 0 ? sd : 1.0f;
-#pragma unroll
-        for (int ct = 0; ct < RT; ++ct)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {               // columns 32 ct + 8 q + 4 h .. + 3
-                bf16x4 r4;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const float mine = t == 0 ? dzA[ct][4 * q + j] : dzG[ct][4 * q + j];
-                    r4[j] = (__bf16)(sc * mine * (float)gpv[t][ct][q][j]);
-                }
-                if (row_ok) *reinterpret_cast<bf16x4*>(out + 32 * ct + 8 * q) = r4;
-            }
-    }
-#endif
 }
 
 // ---- chain-split form (round 5, second session): two waves per SIMD.
@@ -419,7 +349,6 @@ __global__ __launch_bounds__(256) void k1_dz6_kernel(PetBwdArgs a) {
 //  65.2 vs 58.3 us at 18,250 rows, profiles/r05_k1bench_dz6c_ab.txt; removed in round 6.)
 
 int k1_dz6_feature_blocks(int64_t M, int d) {
-    if (const int f = vlpet_tuning().dz2_fsplit; f >= 1) return ((d >> 6) % f == 0) ? f : 1;
     // six blocks while the grid still fits one round of the chip (26.1 / 29.1 / 31.1 us at 1,100 / 2,128 / 3,500 rows against 27.5 / 30.8 / 32.9 with
     // four; 47 row blocks x 6 at 6,000 rows is two rounds: 52 us -- profiles/r05_k1bench_fsplit_small_m.txt), four up to 8,192 rows
     if (M <= 8192 && (d >> 6) % 6 == 0 && ((M + 127) / 128) * 6 <= 256) return 6;

@@ -45,17 +45,6 @@ constexpr int F2_D = 768;
 constexpr int F2_G = F2_D / 16;          // MFMA k-steps of the down projection
 constexpr int F2_NST = F2_D / 64;         // 64-feature stages of a row
 
-// diagnosis build (-DVLPET_F2_STAMPS): shader-clock time per phase of one wave of a few workgroups, summed over its steps
-#ifdef VLPET_F2_STAMPS
-#define F2_STAMP_DECL unsigned long long f2_acc[4] = {0, 0, 0, 0}, f2_last = __builtin_readcyclecounter(); const unsigned long long f2_t0 = f2_last;
-#define F2_STAMP(k) { const unsigned long long tn = __builtin_readcyclecounter(); f2_acc[k] += tn - f2_last; f2_last = tn; }
-#define F2_STAMP_PRINT(tag, fmt) if (lane == 0 && (wave == 0 || wave == (int)(blockDim.x >> 6) - 1) && (blockIdx.x == 0 || blockIdx.x == 101 || blockIdx.x == 303)) \
-    printf("f2 stamps " tag " blk %d wave %d (cycles, total %llu): " fmt "\n", (int)blockIdx.x, wave, __builtin_readcyclecounter() - f2_t0, f2_acc[0], f2_acc[1], f2_acc[2]);
-#else
-#define F2_STAMP_DECL
-#define F2_STAMP(k)
-#define F2_STAMP_PRINT(tag, fmt)
-#endif
 
 template <int N> __device__ __forceinline__ void vmw() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 
@@ -149,7 +138,6 @@ __global__ __launch_bounds__((RT + (RT == 6 ? 2 : 1)) * 64, 2) void k1_down_kern
 #pragma unroll
         for (int i = 0; i < NSLOT - 1; ++i)
             if (i < nss) issue(i);
-        F2_STAMP_DECL
         for (int i = 0; i < nss; ++i) {
             int ahead = nss - 1 - i;                                      // sub-steps already requested beyond i
             if (ahead > NSLOT - 2) ahead = NSLOT - 2;
@@ -161,14 +149,10 @@ __global__ __launch_bounds__((RT + (RT == 6 ? 2 : 1)) * 64, 2) void k1_down_kern
                 case 3: vmw<(3 * NI <= 63 ? 3 * NI : 63)>(); break;
                 default: vmw<(4 * NI <= 63 ? 4 * NI : 63)>(); break;
             }
-            F2_STAMP(0)
             __builtin_amdgcn_s_barrier();                                 // sub-step i has landed; the slot of sub-step i - 1 is free
-            F2_STAMP(1)
             if (i + NSLOT - 1 < nss) issue(i + NSLOT - 1);
-            F2_STAMP(2)
         }
         __builtin_amdgcn_s_barrier();                                     // (the compute waves' hand-over of the last staged tile)
-        F2_STAMP_PRINT("down loader", "vmcnt wait %llu  barrier %llu  issue %llu")
         return;
     }
 
@@ -199,9 +183,6 @@ __global__ __launch_bounds__((RT + (RT == 6 ? 2 : 1)) * 64, 2) void k1_down_kern
     const uint32_t a_stg = lds0 + (uint32_t)(GEO::STG_OFF + m * PB + (32 * ct + 8 * h) * 2);
     const int nchunk = write_grad ? 4 : 2;              // chunks of this wave: c = wave + RT k; tensor c / (2 RT), piece c % (2 RT)
     auto store_out = [&](int t) {
-#ifdef VLPET_F2_ABL
-        if (VLPET_F2_ABL & 4) return;
-#endif
         const int64_t row0 = r_begin + 32 * (int64_t)t;
         const int valid = (int)(r_end - row0);
         sfor<2>([&](auto H) {                             // two chunks at a time (the resident weights leave few registers)
@@ -229,17 +210,12 @@ __global__ __launch_bounds__((RT + (RT == 6 ? 2 : 1)) * 64, 2) void k1_down_kern
     };
 
     f32x16 acc = zero16();
-    F2_STAMP_DECL
     int t = 0;
     auto substep = [&](int i, auto PART) {
         constexpr int hf = decltype(PART)::value;
         __builtin_amdgcn_s_barrier();
-        F2_STAMP(0)
         if constexpr (hf == 0) { if (t > 0) store_out(t - 1); }
         const uint32_t sb = (uint32_t)((i % NSLOT) * SUB_B);
-#ifdef VLPET_F2_ABL
-        if (!(VLPET_F2_ABL & 1))
-#endif
         sfor<SSN>([&](auto ST) {
             constexpr int st = ST.value;
             uint32_t kw = 0;
@@ -268,18 +244,11 @@ __global__ __launch_bounds__((RT + (RT == 6 ? 2 : 1)) * 64, 2) void k1_down_kern
                 }
             });
         });
-#ifdef VLPET_F2_STAMPS
-        asm volatile("s_nop 0" : "+v"(acc[15]));
-#endif
-        F2_STAMP(1)
     };
 #pragma unroll 1
     for (; t < ntiles; ++t) {
         sfor<NPT>([&](auto P) { substep(NPT * t + P.value, P); });
         // bias + gelu_new (+ derivative): register 8*sh + j of the tile <-> c = 32ct + 16sh + 8h + j
-#ifdef VLPET_F2_ABL
-        if (!(VLPET_F2_ABL & 2))
-#endif
 #pragma unroll
         for (int sh = 0; sh < 2; ++sh) {
             u32x4 b0, b1;
@@ -306,11 +275,9 @@ __global__ __launch_bounds__((RT + (RT == 6 ? 2 : 1)) * 64, 2) void k1_down_kern
         }
         acc = zero16();
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");                // the staged pieces are in LDS at the next barrier
-        F2_STAMP(2)
     }
     __builtin_amdgcn_s_barrier();
     store_out(ntiles - 1);
-    F2_STAMP_PRINT("down compute", "barrier %llu  reads+mfma %llu  epilogue %llu")
 }
 
 // ------------------------------------------------------------------------------------------------ pass B
@@ -355,7 +322,6 @@ __global__ __launch_bounds__(512, WPE) void k1_up_kernel(PetFwdArgs a, int row_c
     const int nsteps = r_end > r_begin ? (int)((r_end - r_begin + 31) >> 5) : 0;
     const PackGeom pg = pack_geom(RT, F2_D, 1);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)smem;
-    F2_STAMP_DECL
 
     // up biases of the workgroup's columns -> LDS: [bu_A (32 NW) | bu_G (32 NW)]
     {
@@ -451,7 +417,6 @@ __global__ __launch_bounds__(512, WPE) void k1_up_kernel(PetFwdArgs a, int row_c
         // stores of step s - 1
         vm_wait((s + NX - 2 < nsteps ? 2 : 0) + (s > 0 ? 2 : 0));
         __builtin_amdgcn_s_barrier();                                     // step s has landed for every wave; the slots of step s - 1 are free
-        F2_STAMP(0)
         if (s + 1 < nsteps) issue_z(s + 1);
         if (s + NX - 1 < nsteps) issue_x(s + NX - 1);
         const uint32_t sbx = lds0 + (uint32_t)((s % NX) * X_B);
@@ -483,9 +448,6 @@ __global__ __launch_bounds__(512, WPE) void k1_up_kernel(PetFwdArgs a, int row_c
             });
         };
         f32x16 aA, aG;
-#ifdef VLPET_F2_ABL
-        if (VLPET_F2_ABL & 1) { aA = zero16(); aG = zero16(); } else
-#endif
         {
         if constexpr (GATE) project_up(std::integral_constant<int, 1>{}, std::integral_constant<int, 32 * NW * 4>{}, wG, aG);
         project_up(std::integral_constant<int, 0>{}, std::integral_constant<int, 0>{}, wA, aA);
@@ -494,7 +456,6 @@ __global__ __launch_bounds__(512, WPE) void k1_up_kernel(PetFwdArgs a, int row_c
         lds_read16<0>(xv[0], sbx + a_xcl[0]);
         lds_read16<0>(xv[1], sbx + a_xcl[1]);
         asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(xv[0]), "+v"(xv[1]) :: "memory");
-        F2_STAMP(1)
         // outputs: staged in place over the wave's own x2 columns, read back as 4 lanes per row and stored as 64 contiguous bytes
         // of 16 rows per instruction (the accumulator layout would store 16-byte pieces of 32 rows: twice the memory transactions)
 #pragma unroll
@@ -507,9 +468,6 @@ __global__ __launch_bounds__(512, WPE) void k1_up_kernel(PetFwdArgs a, int row_c
                 if constexpr (GATE) {
                     const float gt = sigm(aG[e]);
                     o[j] = ADD ? lin + gs * gt : lin * gt;
-#ifdef VLPET_F2_ABL
-                    if (VLPET_F2_ABL & 2) o[j] = aG[e] + aA[e];
-#endif
                 } else o[j] = lin;
             }
             lds_write16<0>(sbx + a_xcl[k], pack8(o));
@@ -523,14 +481,9 @@ __global__ __launch_bounds__(512, WPE) void k1_up_kernel(PetFwdArgs a, int row_c
             const int64_t row0 = r_begin + 32 * (int64_t)s + (lane >> 2);
 #pragma unroll
             for (int j = 0; j < 2; ++j)
-#ifdef VLPET_F2_ABL
-                if (!(VLPET_F2_ABL & 4))
-#endif
                 if (row0 + 16 * j < r_end) *reinterpret_cast<u32x4*>(outp + (row0 + 16 * j) * (F2_D * 2)) = ov[j];
         }
-        F2_STAMP(2)
     }
-    F2_STAMP_PRINT("up", "top(wait+barrier) %llu  issue+proj %llu  ew+store %llu")
 }
 
 // ------------------------------------------------------------------------------------------------ K3's keep flags

@@ -46,14 +46,6 @@ struct Bwd2Lds {
 
 template <bool B> struct Bool2 { static constexpr bool value = B; };
 
-#ifdef VLPET_STAMPS
-// diagnosis build only: cycle stamps of one wave of workgroup 0 (VLPET_DBG & 128: the chain-G wave), printed after the launch
-__device__ unsigned long long g_b2_ts[64];
-#define B2STAMP(k) do { if (blockIdx.x == 0 && threadIdx.x == stamp_tid) g_b2_ts[k] = __builtin_readcyclecounter(); } while (0)
-#else
-#define B2STAMP(k) do { } while (0)
-#endif
-
 // LR = low-rank visual projector form (LowRankVisualEmbedding, autograd of src/modeling_bart.py:278-295): d is the OUTPUT
 // width; no residual term (res is never read), gate value sigmoid(.) + go, and no input gradients -- the features are data --
 // so the kernel ends after dpre (the weight-gradient kernel then contracts dpre with the [M, d_in] features itself).
@@ -143,10 +135,6 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
         return n;
     };
 
-#ifdef VLPET_STAMPS
-    const int stamp_tid = (a.flags & (1 << 20)) ? RG * 64 : 0;
-#endif
-    B2STAMP(0);
     // ---- prologue: weights of stage 0, rows of block 0, biases, saved activations
     issue_w(0, false);
     issue_mid_rows(0, false);
@@ -174,7 +162,6 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
     }
     __syncthreads();
 
-    B2STAMP(1);
     // ---- middle phase
     const float* bu = sb + (isA ? 0 : nb) + 32 * RT + G::LW * h;
     const float s2 = a.s2, sd_ = a.sd, gs = a.gs;
@@ -191,10 +178,8 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
         // ================= stage a: recompute this chain's up projection, exchange the other half
         f32x16 au[G::NV];
         {
-            if (su == 5) B2STAMP(8);
             int nrows = rl.n_inst;                  // chain G: only its dq stores of the previous block may still be in flight
             if (isA) { issue_w(st + 1, true); nrows = issue_mid_rows(su + 1, true); }
-            if (su == 5) B2STAMP(9);
             const uint8_t* w = slot_w(st & 1);
 #pragma unroll
             for (int v = 0; v < G::NV; ++v) {
@@ -216,7 +201,6 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
 #pragma unroll
                 for (int v = 0; v < G::NV; ++v) au[v] = mfma_ns<NS>(wf[v * KT + ks], z[ks], au[v]);
             }
-            if (su == 5) B2STAMP(10);
             // the half the partner works on: lane feature i <-> au[i >> 4][i & 15]; A keeps i < LW/2, G keeps i >= LW/2
             {
                 uint8_t* xb = xslot(chain);
@@ -229,11 +213,8 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
                     *reinterpret_cast<f32x4*>(xb + (size_t)q * 1024 + lane16) = t;
                 }
             }
-            if (su == 5) B2STAMP(11);
             wait_vm(nrows);
-            if (su == 5) B2STAMP(12);
             __builtin_amdgcn_s_barrier();
-            if (su == 5) B2STAMP(13);
             ++st;
         }
         // ================= stage b: elementwise backward of the own half, then the contraction over features
@@ -286,15 +267,11 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
                     stage_lane_vals8<IO>(t1, trow, h, e, dq8);
                 }
             };
-            if (su == 5) B2STAMP(14);
             if (gate_add) elementwise(Bool2<true>{}); else elementwise(Bool2<false>{});
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            if (su == 5) B2STAMP(15);
             __builtin_amdgcn_s_barrier();           // both halves of the dh / dq tiles of this row group are complete
-            if (su == 5) B2STAMP(16);
             uint8_t* mine = isA ? t0 : t1;
             store_rows4(isA ? DH : DQ, rl, su * 128, mine, rg, lane);
-            if (su == 5) B2STAMP(17);
             Frag<NS> df[G::E4], wf[G::E4 * RT];
 #pragma unroll
             for (int e = 0; e < G::E4; ++e) {
@@ -310,15 +287,11 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
 #pragma unroll
                 for (int ct = 0; ct < RT; ++ct) dz[ct] = mfma_ns<NS>(wf[e * RT + ct], df[e], dz[ct]);
             }
-            if (su == 5) B2STAMP(18);
             wait_vm(rl.n_inst);
-            if (su == 5) B2STAMP(19);
             __builtin_amdgcn_s_barrier();
-            if (su == 5) B2STAMP(20);
             ++st;
         }
     }
-    B2STAMP(2);
 
     // ---- the dh rows of the last phase: this wave's own stores must have completed; start their stream, then dpre
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -347,14 +320,11 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();                   // (slot 2 was the exchange buffer: every wave is past its last read)
 
-    B2STAMP(3);
     // ---- last phase: input gradients
     uint8_t* dxo = reinterpret_cast<uint8_t*>(isA ? a.dxa : a.dxg);
     for (int su = 0; su < S; ++su, ++st) {
-        if (su == 5) B2STAMP(24);
         int nrows = 0;
         if (!isA) { issue_w(st + 1, true); nrows = issue_last_rows(su + 2, true); }
-        if (su == 5) B2STAMP(25);
         const uint8_t* w = slot_w(st & 1);
         uint8_t* tile = isA ? slot_t0(su % 3) : slot_t1(su % 3);
         f32x16 ax[G::NV];
@@ -374,7 +344,6 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
                 for (int v = 0; v < G::NV; ++v) ax[v] = mfma_ns<NS>(wf[v * KT + ks], dp[ks], ax[v]);
             }
         }
-        if (su == 5) B2STAMP(26);
 #pragma unroll
         for (int e = 0; e < G::E4; ++e) {
             float o8[8], dh8[8];
@@ -390,15 +359,10 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
             }
             stage_lane_vals8<IO>(tile, trow, h, e, o8);
         }
-        if (su == 5) B2STAMP(27);
         store_rows4(dxo, rl, su * 128, tile, rg, lane);
-        if (su == 5) B2STAMP(28);
         wait_vm(nrows + rl.n_inst);
-        if (su == 5) B2STAMP(29);
         __builtin_amdgcn_s_barrier();
-        if (su == 5) B2STAMP(30);
     }
-    B2STAMP(4);
 }
 
 template <typename IO, int RT, int RG, bool LR = false>
@@ -411,24 +375,7 @@ static hipError_t launch_one(const PetBwdArgs& a, hipStream_t stream) {
     if (e != hipSuccess) return e;
     const int rows = RG * 32;
     const int blocks = (int)((a.M + rows - 1) / rows);
-#ifdef VLPET_STAMPS
-    PetBwdArgs b = a;
-    if (vlpet_tuning().dbg & 128) b.flags |= 1 << 20;
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(RG * 128), lds, stream, b);
-    if (vlpet_tuning().dbg & 16) {
-        (void)hipDeviceSynchronize();
-        unsigned long long t[64];
-        (void)hipMemcpyFromSymbol(t, HIP_SYMBOL(g_b2_ts), sizeof(t));
-        auto dd = [&](int i, int j) { return (long long)(t[j] - t[i]); };
-        fprintf(stderr, "[vlpet bwd2 ts] prologue=%lld middle=%lld dpre=%lld last=%lld | stage a: issue=%lld reads+mfma=%lld xwrite=%lld wait=%lld barrier=%lld | "
-                        "stage b: issue=%lld elementwise=%lld barrier1=%lld store=%lld reads+mfma=%lld wait=%lld barrier2=%lld | last: issue=%lld mfma=%lld epilogue=%lld store=%lld wait=%lld barrier=%lld\n",
-                dd(0, 1), dd(1, 2), dd(2, 3), dd(3, 4), dd(8, 9), dd(9, 10), dd(10, 11), dd(11, 12), dd(12, 13),
-                dd(13, 14), dd(14, 15), dd(15, 16), dd(16, 17), dd(17, 18), dd(18, 19), dd(19, 20),
-                dd(24, 25), dd(25, 26), dd(26, 27), dd(27, 28), dd(28, 29), dd(29, 30));
-    }
-#else
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(RG * 128), lds, stream, a);
-#endif
     return hipGetLastError();
 }
 
@@ -443,7 +390,6 @@ static hipError_t launch_rt(const PetBwdArgs& a, hipStream_t stream) {
 
 // true when this form applies: gated K1, saved activations, r <= 96, every dimension it was written for
 bool pet_gate_bwd2_applies(const PetBwdArgs& a) {
-    if (vlpet_tuning().bwd2 == 0) return false;
     return (a.flags & PET_GATE) && a.saved != nullptr && !drop_active(a.drop) && (a.RT == 1 || a.RT == 3);
 }
 

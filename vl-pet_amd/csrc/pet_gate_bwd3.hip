@@ -348,9 +348,8 @@ __device__ __forceinline__ Frag<NS> zero_frag() {
 
 // NRG = row groups (32 rows) per workgroup: 2 for r <= 96 (8 waves, two per SIMD, 256 registers each); 1 for r = 192
 // (4 waves, one per SIMD: the 192 accumulator registers of a role need the whole register file of a SIMD lane)
-// NBUF = row-tile buffers (tiles are requested NBUF - 1 iterations ahead); PPF = the P rows of the next iteration are
-// requested at the top of the current one into a second register set (needs the registers: NRG = 1)
-template <typename IO, int RT, int NRG, int NBUF, bool PPF>
+// NBUF = row-tile buffers (tiles are requested NBUF - 1 iterations ahead)
+template <typename IO, int RT, int NRG, int NBUF>
 __global__ __launch_bounds__(NRG * 256) void pet_gate_cols_kernel(ColsArgs a) {
     using G = Geo4<IO>;
     using L = ColsLds<IO, NRG, NBUF>;
@@ -466,14 +465,13 @@ __global__ __launch_bounds__(NRG * 256) void pet_gate_cols_kernel(ColsArgs a) {
         return rl.n_inst;
     };
     Frag<NS> pn[KT];                                                 // this role's P rows, natural fragments
-    Frag<NS> pnn[PPF ? KT : 1];                                      // ... of the next iteration (PPF)
     constexpr int NPL = KT * (int)(sizeof(IO) / 2);                  // global loads of one load_p
-    auto load_p = [&](int it, Frag<NS>* dst) {                       // (rows past the end: clamped address, zeroed at use)
+    auto load_p = [&](int it) {                                      // (rows past the end: clamped address, zeroed at use)
         int64_t row = r_begin + (int64_t)it * IR + 32 * rg + m;
         if (row >= a.M) row = a.M - 1;
         const IO* pr = Psrc + row * (int64_t)PR + 8 * h;
 #pragma unroll
-        for (int ks = 0; ks < KT; ++ks) dst[ks] = load_frag8(pr + 16 * ks);
+        for (int ks = 0; ks < KT; ++ks) pn[ks] = load_frag8(pr + 16 * ks);
     };
     // accumulate  Out[c, n] += sum_m P[m, c] X[m, n]  for this wave's 32 rows (P = pn, X = the NV natural-fragment pairs)
     // (scheduling fences between the sub-steps: without them hipcc interleaves all transposes and keeps every intermediate
@@ -539,7 +537,7 @@ __global__ __launch_bounds__(NRG * 256) void pet_gate_cols_kernel(ColsArgs a) {
 
 #pragma unroll
     for (int k = 0; k < NBUF - 1; ++k) issue_tile(k);
-    load_p(0, pn);
+    load_p(0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 
@@ -548,7 +546,6 @@ __global__ __launch_bounds__(NRG * 256) void pet_gate_cols_kernel(ColsArgs a) {
         const int bf = it % NBUF;
         const int64_t row0 = r_begin + (int64_t)it * IR + 32 * rg;
         const bool valid = row0 + m < r_end;
-        if constexpr (PPF) load_p(it + 1, pnn);                      // requested first: the end-of-iteration wait covers it
         const int n_tile = issue_tile(it + NBUF - 1);                // in flight during this (and the next NBUF - 2) iterations
         if (row0 + 32 > r_end) {                                     // ragged end of the last chunk (wave-uniform branch)
 #pragma unroll
@@ -672,17 +669,11 @@ __global__ __launch_bounds__(NRG * 256) void pet_gate_cols_kernel(ColsArgs a) {
             tile_frags(role == 1 ? Tdh : Tdq, valid, xn);
             accumulate(xn);
         }
-        // Vector-memory operations retire in order.  Issued this iteration, oldest first: [P rows of it+1 (PPF)], the tile of
-        // it+NBUF-1, the output stores, [P rows of it+1 (!PPF)].  The next iteration needs the tile of it+1 (this
-        // iteration's when NBUF = 2, the previous one's otherwise) and the P rows; the stores may stay in flight.
-        if constexpr (PPF) {
-            wait_vm((NBUF > 2 ? n_tile : 0) + n_store);
-#pragma unroll
-            for (int ks = 0; ks < KT; ++ks) pn[ks] = pnn[ks];
-        } else {
-            load_p(it + 1, pn);                                      // (consumed at the top of the next iteration: the compiler's wait)
-            wait_vm(NPL + n_store + (NBUF > 2 ? n_tile : 0));
-        }
+        // Vector-memory operations retire in order.  Issued this iteration, oldest first: the tile of it+NBUF-1, the output
+        // stores, the P rows of it+1.  The next iteration needs the tile of it+1 (this iteration's when NBUF = 2, the
+        // previous one's otherwise) and the P rows; the stores may stay in flight.
+        load_p(it + 1);                                              // (consumed at the top of the next iteration: the compiler's wait)
+        wait_vm(NPL + n_store + (NBUF > 2 ? n_tile : 0));
         __builtin_amdgcn_s_barrier();                                // B3: next tiles landed; dh / dq / exchange free again
     }
 
@@ -1152,8 +1143,7 @@ void gate_bwd3_plan(int64_t M, int d, int io_fp32, int* row_chunks, int64_t* row
     for (int g = 1; g <= 8 && g <= S; ++g) if (S % g == 0) gs = g;   // feature blocks that share an XCD's L2
     const int ng = S / gs;
     // one workgroup (512 threads, ~130 KiB of LDS) per CU and 32 CUs per XCD: floor(32 / gs) groups per XCD
-    const int target_units = vlpet_tuning().bwd3_units;
-    const int units = target_units > 0 ? target_units : 8 * (32 / gs);
+    const int units = 8 * (32 / gs);
     int64_t rc = units / ng;
     if (rc < 1) rc = 1;
     const int64_t blocks64 = (M + 63) / 64;
@@ -1167,14 +1157,11 @@ static inline bool bwd3_rt_ok(int RT) { return RT == 1 || RT == 3 || RT == 6; }
 // Where the two-pass form is the default: r = 192, whose one-kernel row pass (pet_bwd_kernel<.., 6, gate>) spills 350
 // registers (two-pass 358 us vs 451 us at M = 16,800).  For r <= 96 the previous split (pet_gate_bwd2 + wgrad) is faster on
 // MI355X despite its 11 units of traffic (164 us vs 234 us at M = 28,000): pass 2 is latency-chain bound (see launch_cols_one).
-// VLPET_BWD3 = 1 / 0 forces it on / off for every supported rank.
 bool pet_gate_bwd3_applies(const PetBwdArgs& a) {
-    const int force = vlpet_tuning().bwd3;
-    if (force == 0) return false;
     if (!((a.flags & PET_GATE) && a.saved != nullptr && !drop_active(a.drop) && bwd3_rt_ok(a.RT))) return false;
     // small M (a strong-scaled rank: a few thousand rows): both forms are latency chains of a handful of workgroups, and the
     // two-pass one is the shorter (M = 3,500: 79 vs 88 us; M = 512: 74 vs 79 us; profiles/r02_kbench_two_pass_ab.txt)
-    return force == 1 || a.RT == 6 || a.M <= 4096;
+    return a.RT == 6 || a.M <= 4096;
 }
 
 template <typename IO, int RT, int RG>
@@ -1207,10 +1194,10 @@ hipError_t launch_pet_gate_dz(const PetBwdArgs& a, int io_fp32, hipStream_t stre
     return hipErrorInvalidValue;
 }
 
-template <typename IO, int RT, int NRG, int NBUF, bool PPF>
+template <typename IO, int RT, int NRG, int NBUF>
 static hipError_t launch_cols_cfg(const ColsArgs& c, hipStream_t stream) {
     const size_t lds = ColsLds<IO, NRG, NBUF>::bytes(RT);
-    auto kern = pet_gate_cols_kernel<IO, RT, NRG, NBUF, PPF>;
+    auto kern = pet_gate_cols_kernel<IO, RT, NRG, NBUF>;
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     const int units = c.NG * c.wg.row_chunks;
@@ -1238,19 +1225,14 @@ static hipError_t launch_cols2_cfg(const ColsArgs& c, hipStream_t stream) {
 
 template <typename IO, int RT>
 static hipError_t launch_cols_one(const ColsArgs& c, hipStream_t stream) {
-    // VLPET_BWD3_FORM: 0 = four roles per row group (4 waves, one tile at a time); 1 (default for r <= 96) = two waves per row
-    // group, two row groups per workgroup (198.8 -> 137.2 us at M = 28 k, 58.9 -> 55.0 at 3.5 k; profiles/r02_kbench_pass2_forms.txt)
-    const int form = vlpet_tuning().bwd3_form;
+    // three tiles: two waves per row group, two row groups per workgroup, instead of four roles per row group (4 waves, one tile
+    // at a time): 198.8 -> 137.2 us at M = 28 k, 58.9 -> 55.0 at 3.5 k; profiles/r02_kbench_pass2_forms.txt
     if constexpr (RT == 3) {
-        if (form == 1) return launch_cols2_cfg<IO, RT, 2, 2>(c, stream);
-        if (form == 2) return launch_cols2_cfg<IO, RT, 2, 3>(c, stream);
-    }
-    if constexpr (RT == 6) {
-        return launch_cols_cfg<IO, RT, 1, 2, false>(c, stream);     // 96 KiB of weight fragments: room for two tile buffers
-    } else if constexpr (RT == 1) {
-        return launch_cols_cfg<IO, RT, 2, 2, false>(c, stream);
+        return launch_cols2_cfg<IO, RT, 2, 2>(c, stream);
+    } else if constexpr (RT == 6) {
+        return launch_cols_cfg<IO, RT, 1, 2>(c, stream);     // 96 KiB of weight fragments: room for two tile buffers
     } else {
-        return launch_cols_cfg<IO, RT, 1, 3, true>(c, stream);
+        return launch_cols_cfg<IO, RT, 2, 2>(c, stream);
     }
 }
 

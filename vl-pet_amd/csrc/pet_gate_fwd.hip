@@ -123,16 +123,8 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
         return 0;
     };
 
-    // debug timestamps (build with -DVLPET_STAMPS, run with VLPET_DBG & 16; lane 0 of the first chain-A wave -- or, with
-    // VLPET_DBG & 128, the first chain-G wave -- of every block).  Compiled out by default: an s_memtime anywhere in a
-    // loop makes hipcc fall back to s_waitcnt lgkmcnt(0) for every LDS read in it (scalar-memory returns are unordered).
-    auto stamp = [&](int k) {
-#ifdef VLPET_STAMPS
-        if ((a.dbg & 16) && tid == ((a.dbg & 128) ? RG * 64 : 0) && blockIdx.x < 4096) a.dbg_ts[blockIdx.x * 8 + k] = __builtin_readcyclecounter();
-#else
-        (void)k;
-#endif
-    };
+    // (no cycle stamps in this kernel: an s_memtime anywhere in a loop makes hipcc fall back to s_waitcnt lgkmcnt(0) for every LDS
+    // read in it -- scalar-memory returns are unordered)
     if constexpr (LD) {
         // ---- loader waves (one per row group, so one per SIMD): every global_load_lds of the workgroup.  A wave that is
         // waiting for the memory pipe to accept its next piece costs no issue slots, so the compute waves never stall on
@@ -183,7 +175,6 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
             return;
         }
     }
-    stamp(0);
     if constexpr (!LD) {
         issue_w(0);
         glds_rows4(xin, rl, 0, slot_d(0), rg);
@@ -194,7 +185,6 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
         copy_bias<NW * 64>(sb + nb, reinterpret_cast<const float*>(a.pk_g + pg.bias_off), nb, tid);
     }
     __syncthreads();
-    stamp(1);
 
     // ---- down projection of this wave's chain: register 8*sh + j of c-tile ct <-> c = 32ct + 16sh + 8h + j
     f32x16 acc[RT];
@@ -202,7 +192,6 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
     for (int ct = 0; ct < RT; ++ct) acc[ct] = zero16();
     int t = 0;
     for (; t < S; ++t) {
-        if (t == 5 && !(a.dbg & 32)) stamp(5);
         issue_w(t + 1);
         const int nrows = issue_rows(t);
         const uint8_t* w = slot_w(t & 1) + (isA ? 0 : L::SEG_KB * 1024);
@@ -235,12 +224,9 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
                 for (int ct = 0; ct < RT; ++ct) acc[ct] = mfma_ns<NS>(wf[ct], b, acc[ct]);
             }
         }
-        if (t == 5 && !(a.dbg & 32)) stamp(6);
         wait_vm(nrows);
         __builtin_amdgcn_s_barrier();
-        if (t == 5 && !(a.dbg & 32)) stamp(7);
     }
-    stamp(2);
 
     // ---- bias + gelu_new -> B fragments of the up projection (k-step 2ct+sh holds c = 32ct+16sh+8h+j)
     Frag<NS> z[KT];
@@ -274,7 +260,6 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
         }
     }
 
-    stamp(3);
     // ---- up phase
     const float* bu = sb + (isA ? 0 : nb) + 32 * RT + G::LW * h;
     const float gs = a.gs;
@@ -282,7 +267,6 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
     float gm = 1.f, go = 0.f;
     if constexpr (LR) { gm = a.gm; go = a.go; }
     for (; t <= S + SU; ++t) {
-        if (t == S + 5 && (a.dbg & 32)) stamp(5);      // VLPET_DBG & 32: stage stamps from the up phase instead
         issue_w(t + 1);
         const int nrows = issue_rows(t);
         (void)nrows;
@@ -371,12 +355,9 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
                 n_after = rl.n_inst;
             }
         }
-        if (t == S + 5 && (a.dbg & 32)) stamp(6);
         wait_vm(n_after);
         __builtin_amdgcn_s_barrier();
-        if (t == S + 5 && (a.dbg & 32)) stamp(7);
     }
-    stamp(4);
 }
 
 template <typename IO, int RT, bool GATE_ADD, int RG, bool LD, bool LR = false>

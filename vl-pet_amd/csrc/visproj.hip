@@ -216,23 +216,15 @@ __global__ __launch_bounds__(WAVES * 64) void visproj_fwd_kernel(VisprojArgs a) 
 // ---------------------------------------------------------------------------------------------------------------
 // Column-split form for d_out = 768 (the real shape): 8 waves = 4 row groups x 2 column halves.
 //
-// The 4-wave kernel above keeps all d_out / 32 = 24 accumulator tiles of its 32 rows in one wave: 384 of the 512
-// registers a lane of a SIMD has, and hipcc spills an accumulator tile INSIDE the sub-stage loop (75-180 registers in
+// The 4-wave kernel above (d_out = 64 / 128) would keep all d_out / 32 = 24 accumulator tiles of its 32 rows in one wave: 384 of
+// the 512 registers a lane of a SIMD has, and hipcc spilled an accumulator tile INSIDE the sub-stage loop (75-180 registers in
 // all).  Scratch traffic retires in order with the LDS-DMA prefetches on vmcnt, so every reload waited for the weight
 // stream just requested: 1.9 us per 16-feature sub-stage against 0.37 us of MFMA issue -- 241 us per launch at
 // M = 18.7k, 10 % of the MFMA peak.  Here a wave owns 12 tiles (192 registers, two waves per SIMD, nothing spilled):
 // same rows per workgroup, same weight bytes per MFMA (the fragment stream is shared by the eight waves, the row
 // tile by the two halves of a row group), the LayerNorm statistics cross the two halves through LDS (two exchanges:
 // mean, then centred variance -- the reference's two-pass order).
-#ifndef VLPET_K4_GB
-#define VLPET_K4_GB 3
-#endif
-#ifndef VLPET_K4_ABL
-#define VLPET_K4_ABL 0
-#endif
-#ifndef VLPET_K4_SPLIT_ISSUE
-#define VLPET_K4_SPLIT_ISSUE 0
-#endif
+constexpr int K4_GB = 3;          // A fragments per LDS burst where that divides a wave's tiles
 template <typename IO, int NCT>
 struct VisLds2 {
     static constexpr int NS = Geo4<IO>::NS;
@@ -257,7 +249,7 @@ __global__ __launch_bounds__(512) void visproj_fwd2_kernel(VisprojArgs a) {
     constexpr int NS = G::NS;
     constexpr int WAVES = L::WAVES, RGN = L::RGN;
     constexpr int NCW = NCT / L::CH;             // accumulator tiles per wave
-    constexpr int GB = NCW % VLPET_K4_GB == 0 ? VLPET_K4_GB : 1;      // A fragments per LDS burst (double-buffered)
+    constexpr int GB = NCW % K4_GB == 0 ? K4_GB : 1;      // A fragments per LDS burst (double-buffered)
     static_assert(NCW % GB == 0, "burst must divide the tiles of a wave");
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
@@ -285,14 +277,7 @@ __global__ __launch_bounds__(512) void visproj_fwd2_kernel(VisprojArgs a) {
         if (q1 >= Q) return;
         const uint8_t* src0 = a.pk + (int64_t)q1 * L::WSUB_B;
         uint8_t* dst = slot_w(q1 % L::NW);
-        if constexpr (L::NW >= 4 && VLPET_K4_SPLIT_ISSUE) {
-            // the weight pieces are requested by the column-half-1 waves only, the row pieces by the column-half-0 waves: the two
-            // waves of a SIMD then stall in their requests at different times instead of together (the matrix pipe idled through both)
-            if (ch == 1)
-                for (int k = rgi; k < KBW; k += RGN) glds16(src0 + (size_t)k * 1024 + lane16, dst + (size_t)k * 1024);
-        } else {
-            for (int k = wave; k < KBW; k += WAVES) glds16(src0 + (size_t)k * 1024 + lane16, dst + (size_t)k * 1024);
-        }
+        for (int k = wave; k < KBW; k += WAVES) glds16(src0 + (size_t)k * 1024 + lane16, dst + (size_t)k * 1024);
     };
     const int npw = wave < KBW ? (KBW - wave + WAVES - 1) / WAVES : 0;     // weight pieces this wave issues per sub-stage
     const int nrow = ch == 0 ? 4 : 0;                                        // row pieces this wave issues per stage
@@ -327,19 +312,14 @@ __global__ __launch_bounds__(512) void visproj_fwd2_kernel(VisprojArgs a) {
     if constexpr (PAIRS) {
     for (int q = 0; q < Q; q += 2) {
         const int s = q / G::KU, u = q % G::KU;
-#if VLPET_K4_ABL != 2          // (ablation builds: 1 = the stream without the products, 2 = the products without the stream)
         issue_w(q + 2);
         issue_w(q + 3);
-#endif
         const bool rows_now = u == 0 && s + 2 < S;
-#if VLPET_K4_ABL != 2
         if (u == 0) issue_rows(s + 2);
-#endif
         const uint8_t* w0 = slot_w(q % L::NW);
         const uint8_t* w1 = slot_w((q + 1) % L::NW);
         const Frag<NS> b0 = tile_bfrag4<IO>(slot_t(s % 3), trow, h, u);
         const Frag<NS> b1 = tile_bfrag4<IO>(slot_t(s % 3), trow, h, u + 1);
-#if VLPET_K4_ABL != 1
         {
             Frag<NS> wa[2][GB];
 #pragma unroll
@@ -357,9 +337,6 @@ __global__ __launch_bounds__(512) void visproj_fwd2_kernel(VisprojArgs a) {
                 __builtin_amdgcn_sched_barrier(0);
             }
         }
-#else
-        acc[0][0] += (float)b0.p[0][0] + (float)b1.p[0][0] + (float)w0[lane] + (float)w1[lane];
-#endif
         // this wave's requests in program order: W(q+2) W(q+3) [rows(s+2)]: the next pair's weights must have landed; the
         // rows of the stage after next may stay in flight
         wait_vm(rows_now ? nrow : 0);
@@ -502,10 +479,7 @@ static hipError_t launch_io(const VisprojArgs& a, hipStream_t stream) {
     switch (a.d_out) {
         case 64: return launch_nct<IO, 2>(a, stream);
         case 128: return launch_nct<IO, 4>(a, stream);
-        case 768: {
-            const bool old_form = vlpet_tuning().k4_waves4 != 0;
-            return old_form ? launch_nct<IO, 24>(a, stream) : launch_nct2<IO, 24>(a, stream);      // (VLPET_K4_WAVES4=1: A/B)
-        }
+        case 768: return launch_nct2<IO, 24>(a, stream);
         default: return hipErrorInvalidValue;
     }
 }

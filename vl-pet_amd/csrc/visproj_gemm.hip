@@ -39,9 +39,7 @@
 
 #define VISG_MAX_SPIN (1u << 20)
 #define VISG_FLAGS_B 65536       // give-up flags of the tiles: one fixed-size area (see visproj_gemm_workspace_bytes)
-#ifndef VISG_DEFAULT_FORM
-#define VISG_DEFAULT_FORM 4      // BK 64, two slots, spread requests: profiles/r05_k4bench.txt
-#endif
+constexpr int VISG_DEFAULT_FORM = 4;      // BK 64, two slots, spread requests: profiles/r05_k4bench.txt
 
 template <int N, int RTN>
 __device__ __forceinline__ void visg_frag_wait(u32x4 (&w)[2], u32x4 (&x)[RTN]) {

@@ -22,12 +22,11 @@ size_t wgrad_workspace_bytes(int njobs, int RT, int xcols_max, int row_chunks) {
 
 void wgrad_plan(int64_t M, int njobs, int xcols_max, int* row_chunks, int64_t* rows_per_chunk) {
     // The streaming kernel's workgroups are (job, 256-column slab, row chunk); the row chunks are what the partial-sum
-    // workspace (and the finalize pass) scales with, so the plan takes as few as fill the chip: by default one workgroup
-    // per CU (VLPET_WGRAD_WGS overrides; the 64-column-slice kernels of the fp32 / masked paths get 4x as many workgroups
-    // from the same plan).
+    // workspace (and the finalize pass) scales with, so the plan takes as few as fill the chip: one workgroup per CU (the
+    // 64-column-slice kernels of the fp32 / masked paths get 4x as many workgroups from the same plan).
     const int slabs = (xcols_max + 255) / 256;
     int64_t blocks128 = (M + 127) / 128;
-    const int64_t target = vlpet_tuning().wgrad_wgs > 0 ? vlpet_tuning().wgrad_wgs : 256;
+    const int64_t target = 256;
     int64_t rc = (target + (int64_t)slabs * njobs / 2) / ((int64_t)slabs * njobs);
     if (rc < 1) rc = 1;
     // ... and never more row chunks than put ONE workgroup on every CU of an XCD: the grid is numbered XCD-aware (wg_grid:
@@ -35,13 +34,9 @@ void wgrad_plan(int64_t M, int njobs, int xcols_max, int* row_chunks, int64_t* r
     // slabs 21 chunks are 84 groups = 33 workgroups on four of the 32-CU XCDs, and the CU that carries two of them finishes
     // late: cold-input timings (tools/k1bench.py K1BENCH_COLD=1, profiles/r02_wgrad_cold_crossover.txt) jump by 25-40 %
     // exactly where the plan says 21 (M = 24,000: 94.6 us, 31,616: 116.9) against 20 (28,000: 82.9, 33,200: 93.4).
-    // Applies to the default target only (an explicit VLPET_WGRAD_WGS is taken as given).
-    const bool explicit_target = vlpet_tuning().wgrad_wgs > 0;
-    if (!explicit_target) {
-        const int64_t per_xcd = 32 / (slabs < 32 ? slabs : 32);              // (job, chunk) groups per XCD at one workgroup per CU
-        const int64_t rc_max = per_xcd > 0 ? (8 * per_xcd) / njobs : 1;
-        if (rc_max >= 1 && rc > rc_max) rc = rc_max;
-    }
+    const int64_t per_xcd = 32 / (slabs < 32 ? slabs : 32);              // (job, chunk) groups per XCD at one workgroup per CU
+    const int64_t rc_max = per_xcd > 0 ? (8 * per_xcd) / njobs : 1;
+    if (rc_max >= 1 && rc > rc_max) rc = rc_max;
     if (rc > blocks128) rc = blocks128;
     int64_t per = (blocks128 + rc - 1) / rc;          // 128-row blocks per chunk
     rc = (blocks128 + per - 1) / per;
@@ -285,199 +280,6 @@ __global__ __launch_bounds__(VLPET_THREADS) void wgrad_kernel(WgradArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------
-// bf16 fast path: the m-contraction operands come from gfx950's LDS transpose read.
-//
-// Each wave stages its own 32 rows (P: 32 x 64RT bytes, X: 32 x 128 bytes; coalesced 16-byte global loads, one block
-// ahead in registers) into a PRIVATE double-buffered row-major LDS tile -- same-wave LDS accesses are ordered, so the
-// row loop has no barrier.  ds_read_b64_tr_b16 then hands every lane four consecutive ROWS of its own column
-// (measured mapping, tools/tr_probe.hip: within a 16-lane group, out(lane t, elem j) = in(lane 4j + (t >> 2), elem t & 3);
-// with lane s of a group addressing row (s >> 2), columns 4(s & 3).. of a [4 rows x 16 cols] block, lane t receives
-// column t of the four rows), i.e. exactly the 32x32x16 MFMA operand of a contraction over rows: two reads per
-// operand, no identity-MFMA transposes, no fp32 -> bf16 re-conversion, no AGPR shuffling.  Bias gradients (column
-// sums) are one extra MFMA against an all-ones A fragment.
-typedef short v4s16 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ bf16x8 tr_operand(const uint8_t* tile, int row_stride, int kb, int cb, int lane) {
-    // operand of k-step rows kb .. kb+15 and columns cb .. cb+31: lane (i = lane & 31, h = lane >> 5) gets rows kb+8h .. +7 of column cb+i
-    const int g = lane >> 4, sl = lane & 15;
-    const uint8_t* p = tile + (size_t)(kb + 8 * (g >> 1) + (sl >> 2)) * row_stride + (cb + 16 * (g & 1) + 4 * (sl & 3)) * 2;
-    typedef __attribute__((address_space(3))) v4s16 lds_v4;
-    const v4s16 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(p));
-    const v4s16 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_v4*)(p + 4 * row_stride));
-    typedef short v8s16 __attribute__((ext_vector_type(8)));
-    const v8s16 r = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-    return __builtin_bit_cast(bf16x8, r);
-}
-
-template <int RT>
-__global__ __launch_bounds__(VLPET_THREADS) void wgrad_tr_kernel(WgradArgs a) {
-    constexpr int PR = 32 * RT;
-    constexpr int PB = PR * 2;                       // bytes of a P row in the tile
-    constexpr int XB = 128;                          // bytes of an X row (64-column slice)
-    constexpr int NPP = PB * 32 / 16 / 64;           // 16-byte pieces per lane of a 32-row P block (= 2 RT)
-    constexpr int NPR = PB / 16;                     // pieces per P row
-    constexpr int BUF = 32 * (PB + XB);              // one buffer of a wave
-    constexpr int NV = RT * 2 * 16 + RT + 2;         // per-lane values reduced across the 4 waves (as wgrad_kernel)
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-
-    const WgId wg = wg_decode(a, a.nslice);
-    if (!wg.ok) return;
-    const int jb = wg.job;
-    const uint8_t* P = reinterpret_cast<const uint8_t*>(a.job[jb].P);
-    const uint8_t* X = reinterpret_cast<const uint8_t*>(a.job[jb].X);
-    const int ldp = a.job[jb].ldp, ldx = a.job[jb].ldx, xc = a.job[jb].xcols;
-    const int n0 = wg.slice * 64;
-    if (n0 >= xc) return;
-    const int rc = wg.rc;
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: scalar registers and scalar branches for everything derived from it
-    const int m = lane & 31, h = lane >> 5;
-    const int64_t r_begin = (int64_t)rc * a.rows_per_chunk;
-    int64_t r_end = r_begin + a.rows_per_chunk;
-    if (r_end > a.M) r_end = a.M;
-    uint8_t* mine = smem + (size_t)wave * 2 * BUF;
-    const bool want_csp = wg.slice == 0;
-
-    f32x16 acc[RT][2];
-    // column sums: A fragment "row t all ones" puts sum_k B[k][j] into row t of ONE accumulator, so the RT P tiles
-    // (and the two X tiles) share a single f32x16 each: D[t][j] -- lane (j, h = 0), register t
-    f32x16 sx = zero16(), sp = zero16();
-#pragma unroll
-    for (int ct = 0; ct < RT; ++ct) { acc[ct][0] = zero16(); acc[ct][1] = zero16(); }
-    bf16x8 erow[RT > 2 ? RT : 2];
-#pragma unroll
-    for (int t = 0; t < (RT > 2 ? RT : 2); ++t)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) erow[t][j] = (m == t) ? (__bf16)1.0f : (__bf16)0.0f;
-
-    u32x4 rp[NPP], rx[4];
-    auto load_block = [&](int64_t rb) {              // unconditional (rows clamped): exact vmcnt bookkeeping by hipcc
-#pragma unroll
-        for (int i = 0; i < NPP; ++i) {
-            const int q = lane + 64 * i;
-            int64_t row = rb + q / NPR;
-            if (row >= r_end) row = r_end - 1;
-            rp[i] = *reinterpret_cast<const u32x4*>(P + row * ldp * 2 + (q % NPR) * 16);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            int64_t row = rb + 8 * i + (lane >> 3);
-            if (row >= r_end) row = r_end - 1;
-            rx[i] = *reinterpret_cast<const u32x4*>(X + (row * ldx + n0) * 2 + (lane & 7) * 16);
-        }
-    };
-    auto store_block = [&](int64_t rb, int buf) {    // registers -> the wave's tile; rows past the end become zeros
-        uint8_t* tp = mine + (size_t)buf * BUF;
-        uint8_t* tx = tp + 32 * PB;
-        const u32x4 z = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < NPP; ++i) {
-            const int q = lane + 64 * i;
-            const bool ok = rb + q / NPR < r_end;
-            *reinterpret_cast<u32x4*>(tp + (size_t)q * 16) = ok ? rp[i] : z;
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            const bool ok = rb + 8 * i + (lane >> 3) < r_end;
-            *reinterpret_cast<u32x4*>(tx + (size_t)(8 * i + (lane >> 3)) * XB + (lane & 7) * 16) = ok ? rx[i] : z;
-        }
-    };
-
-    int64_t rb = r_begin + 32 * wave;
-    int it = 0;
-    if (rb < r_end) {
-        load_block(rb);
-        store_block(rb, 0);
-        load_block(rb + 128);
-    }
-#pragma unroll 1
-    for (; rb < r_end; rb += 128, ++it) {
-        const uint8_t* tp = mine + (size_t)(it & 1) * BUF;
-        const uint8_t* tx = tp + 32 * PB;
-#pragma unroll
-        for (int ks = 0; ks < 2; ++ks) {
-            bf16x8 bx[2];
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt) {
-                bx[nt] = tr_operand(tx, XB, 16 * ks, 32 * nt, lane);
-                sx = mfma32(erow[nt], bx[nt], sx);
-            }
-#pragma unroll
-            for (int ct = 0; ct < RT; ++ct) {
-                const bf16x8 ap = tr_operand(tp, PB, 16 * ks, 32 * ct, lane);
-                acc[ct][0] = mfma32(ap, bx[0], acc[ct][0]);
-                acc[ct][1] = mfma32(ap, bx[1], acc[ct][1]);
-                if (want_csp) sp = mfma32(erow[ct], ap, sp);
-            }
-        }
-        // next block: registers (loaded during the previous iteration) -> the other buffer; request the block after it
-        store_block(rb + 128, (it + 1) & 1);
-        load_block(rb + 256);
-    }
-
-    // ---- reduce the four waves (fixed order) and emit this chunk's partial: identical layout to wgrad_kernel
-    float csp[RT], csx[2];
-#pragma unroll
-    for (int ct = 0; ct < RT; ++ct) csp[ct] = h == 0 ? sp[ct] : 0.f;          // row ct of the shared accumulator
-    csx[0] = h == 0 ? sx[0] : 0.f;
-    csx[1] = h == 0 ? sx[1] : 0.f;
-    float* red = reinterpret_cast<float*>(smem);
-    __syncthreads();                                 // the row tiles are dead: the reduction buffer aliases them
-    if (wave > 0) {
-        float* dst = red + (size_t)(wave - 1) * NV * 64;
-        int k = 0;
-#pragma unroll
-        for (int ct = 0; ct < RT; ++ct)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) dst[(k++) * 64 + lane] = acc[ct][nt][i];
-#pragma unroll
-        for (int ct = 0; ct < RT; ++ct) dst[(k++) * 64 + lane] = csp[ct];
-        dst[(k++) * 64 + lane] = csx[0];
-        dst[(k++) * 64 + lane] = csx[1];
-    }
-    __syncthreads();
-    if (wave == 0) {
-        for (int w = 0; w < 3; ++w) {
-            const float* src = red + (size_t)w * NV * 64;
-            int k = 0;
-#pragma unroll
-            for (int ct = 0; ct < RT; ++ct)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                    for (int i = 0; i < 16; ++i) acc[ct][nt][i] += src[(k++) * 64 + lane];
-#pragma unroll
-            for (int ct = 0; ct < RT; ++ct) csp[ct] += src[(k++) * 64 + lane];
-            csx[0] += src[(k++) * 64 + lane];
-            csx[1] += src[(k++) * 64 + lane];
-        }
-        const WgradLayout L = wgrad_layout(a);
-        float* part = a.partial + L.off[jb];
-        float* tile = part + (int64_t)rc * PR * xc;
-#pragma unroll
-        for (int ct = 0; ct < RT; ++ct)
-#pragma unroll
-            for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) {
-                    const int crow = 32 * ct + (i & 3) + 8 * (i >> 2) + 4 * h;
-                    tile[(int64_t)crow * xc + n0 + 32 * nt + m] = acc[ct][nt][i];
-                }
-        float* psx = part + (int64_t)a.row_chunks * PR * xc + (int64_t)rc * xc;
-#pragma unroll
-        for (int nt = 0; nt < 2; ++nt)
-            if (h == 0) psx[n0 + 32 * nt + m] = csx[nt];
-        if (want_csp) {
-            float* psp = part + (int64_t)a.row_chunks * PR * xc + (int64_t)a.row_chunks * xc + (int64_t)rc * PR;
-#pragma unroll
-            for (int ct = 0; ct < RT; ++ct)
-                if (h == 0) psp[32 * ct + m] = csp[ct];
-        }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------
 // bf16 streaming form (round 3): the op is a split-K GEMM with a 4-byte-per-flop appetite -- at M = 28 k the four jobs of
 // a K1 call read 172 MB and do 16.5 GFLOP, i.e. HBM-bound by a factor of 4 -- so the kernel is built as a stream:
 //   * a workgroup owns (job, 256-column slab of X, row chunk); wave w owns 64 columns of the slab and ALL 32*RT columns of
@@ -485,7 +287,10 @@ __global__ __launch_bounds__(VLPET_THREADS) void wgrad_tr_kernel(WgradArgs a) {
 //     of the 64-column slices above), X rows arrive as 512 contiguous bytes per row;
 //   * every tile travels global -> LDS by global_load_lds (no staging registers) into an NSTG-deep ring, NSTG - 1 steps
 //     of 32 rows in flight per wave (counted vmcnt; one s_barrier per step for the shared P tile);
-//   * operands come out of the row-major tiles with ds_read_b64_tr_b16 (tr_operand above).  The 128-byte rows of the X
+//   * operands come out of the row-major tiles with ds_read_b64_tr_b16 (tr_read, cols_common.h): it hands every lane four
+//     consecutive ROWS of its own column (measured mapping, tools/tr_probe.hip: within a 16-lane group, out(lane t, elem j) =
+//     in(lane 4j + (t >> 2), elem t & 3)), i.e. the 32x32x16 MFMA operand of a contraction over rows: no identity-MFMA
+//     transposes, no fp32 -> bf16 re-conversion; the bias gradients are one more MFMA against a one-hot A fragment.  The 128-byte rows of the X
 //     sub-tiles are swizzled on the SOURCE side (16-byte slot ^= 4 for rows with bit 1 set) so that the four rows a
 //     32-lane group reads fall into four different 64-byte bank windows; the 64 / 192-byte rows of P do so natively,
 //     the 128 / 384-byte ones (even RT) get the same swizzle.
@@ -569,9 +374,6 @@ __global__ __launch_bounds__(VLPET_THREADS, (RT <= 3 ? 2 : 1)) void wgrad_stream
             if (row >= r_end) row = r_end - 1;
             __builtin_amdgcn_global_load_lds((gmem_cv*)(mbits + row * ldm + msrc), (lmem_v*)(st + GEO::STG_B + wave * 256), 4, 0, 0);
         }
-#ifdef VLPET_WGRAD_EXP
-        if (!(a.RT & 0x400))
-#endif
 #pragma unroll
         for (int j = 0; j < PPW; ++j) {
             int64_t row = rb + prow[j];
@@ -579,9 +381,6 @@ __global__ __launch_bounds__(VLPET_THREADS, (RT <= 3 ? 2 : 1)) void wgrad_stream
             glds16(P + row * ldpb + psrc[j], st + (size_t)(wave + 4 * j) * 1024);
         }
         uint8_t* sx_ = st + GEO::PT_B + (size_t)wave * GEO::XT_B;
-#ifdef VLPET_WGRAD_EXP
-        if (!(a.RT & 0x800))
-#endif
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             int64_t row = rb + 8 * i + xrow;
@@ -665,9 +464,6 @@ __global__ __launch_bounds__(VLPET_THREADS, (RT <= 3 ? 2 : 1)) void wgrad_stream
                 if (q / NPR >= valid) *reinterpret_cast<u32x4*>(st + (size_t)q * 16) = z;
             __syncthreads();
         }
-#ifdef VLPET_WGRAD_EXP
-        if (a.RT & 0x200) continue;                  // experiment: the stream without the products
-#endif
         if (active) {
             const uint32_t sb = lds0 + (uint32_t)((s % NSTG) * STG);
             TrOp bx[2][2], ap[2][RT];
@@ -711,10 +507,6 @@ __global__ __launch_bounds__(VLPET_THREADS, (RT <= 3 ? 2 : 1)) void wgrad_stream
     }
 
     if (!active) return;
-#ifdef VLPET_WGRAD_EXP
-    if ((a.RT & 0x100) && acc[0][0][0] != 123.456f) return;      // experiment: no partial stores
-    a.RT &= 0xff;
-#endif
     const WgradLayout L = wgrad_layout(a);
     float* part = a.partial + L.off[jb];
     float* tile = part + (int64_t)rc * PR * xc;
@@ -769,16 +561,7 @@ struct FinArgs {
 };
 
 // the partials are read once, by one workgroup; non-temporal loads measured no faster here (K1 backward pass 2 + finalize 75.1 / 75.7 us
-// with them against 73.8 / 74.4 us without at M = 28,000, same box: profiles/r04_finalize_ab.txt), unlike for the row streams (pet16.h;
-// -DVLPET_FIN_NT=1 builds the non-temporal variant for A/B)
-#ifndef VLPET_FIN_NT
-#define VLPET_FIN_NT 0
-#endif
-#if VLPET_FIN_NT
-#define VLPET_FIN_LOAD(p) __builtin_nontemporal_load(p)
-#else
-#define VLPET_FIN_LOAD(p) (*(p))
-#endif
+// with them against 73.8 / 74.4 us without at M = 28,000, same box: profiles/r04_finalize_ab.txt), unlike for the row streams (pet16.h)
 __device__ __forceinline__ void finalize_body(const FinArgs& a, float (*tile)[65]) {
     const FinJob J = a.job[blockIdx.y];
     const int PR = a.PR, RC = a.RC;
@@ -802,7 +585,7 @@ __device__ __forceinline__ void finalize_body(const FinArgs& a, float (*tile)[65
 #pragma unroll
             for (int q = 0; q < N; ++q) {
                 const int r2 = rc0 + q < RC ? rc0 + q : RC - 1;
-                v[q] = VLPET_FIN_LOAD(reinterpret_cast<const f32x4*>(p0 + r2 * cstride));
+                v[q] = *reinterpret_cast<const f32x4*>(p0 + r2 * cstride);
             }
             __builtin_amdgcn_sched_barrier(0);                           // (every request before the first add)
             const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
@@ -903,62 +686,33 @@ template <typename IO, int RT>
 static hipError_t launch_one(const WgradArgs& a, hipStream_t stream) {
     constexpr int NV = RT * 2 * 16 + RT + 2;
     int xmax = 0, rmax = 0;
-    bool plain = true;                       // no dropout mask on X, 16-byte aligned rows: the transpose-read path applies
-    bool streamable = true, masked = false;  // the streaming kernel also takes a mask if it is the forward's packed one
+    bool streamable = true, masked = false;  // 16-byte aligned rows; a dropout mask on X only if it is the forward's packed one
     for (int j = 0; j < a.njobs; ++j) {
         const WgradJob& J = a.job[j];
         if (J.xcols > xmax) xmax = J.xcols;
         if (J.out_rows > rmax) rmax = J.out_rows;
-        if (J.ldp % 8 != 0 || J.ldx % 8 != 0) plain = streamable = false;
+        if (J.ldp % 8 != 0 || J.ldx % 8 != 0) streamable = false;
         if (J.has_drop) {
-            plain = false;
             masked = true;
             if (J.drop.bits == nullptr || J.drop.keep != nullptr || J.colsum_x != nullptr || J.ldx % 64 != 0) streamable = false;
         }
     }
-    // bf16, r <= 96, no dropout mask: the LDS transpose-read kernel (ds_read_b64_tr_b16 operands, no identity-MFMA
-    // transposes, no fp32 -> bf16 re-conversion).  Round 2, after the XCD-aware numbering: 83.0 vs 86.7 us at M = 28 k,
-    // and in the bench 96.6 vs 104.3 us per K1 call, 235 vs 279 us for the K4 weight gradient (16,415 vs 16,319 samples/s;
-    // profiles/r02_kbench_wgrad_variants.txt).  VLPET_WGRAD_TR=0 selects the identity-transpose kernel.
-    const bool use_tr = vlpet_tuning().wgrad_tr != 0;
     hipError_t e;
-    // bf16, no dropout mask: the streaming kernel (256-column slabs, LDS-DMA ring).  VLPET_WGRAD_STREAM=0 falls back to the
-    // per-wave transpose-read kernel below (A/B).
-    const bool use_stream = vlpet_tuning().wgrad_stream != 0;
+    // bf16, 16-byte aligned rows, no dropout mask or the forward's packed one: the streaming kernel (256-column slabs, LDS-DMA ring
+    // of 3 stages: 72 KiB at RT = 3, two workgroups per CU)
     if constexpr (std::is_same<IO, __bf16>::value) {
-        if (streamable && use_stream) {
-            // ring depth: 3 stages (72 KiB at RT = 3: two workgroups per CU); VLPET_WGRAD_NSTG=4 for A/B (one per CU, one more stage in flight)
-            const int nstg = vlpet_tuning().wgrad_nstg;
+        if (streamable) {
             WgradArgs b = a; b.nslice = (xmax + 255) / 256;
-#ifdef VLPET_WGRAD_EXP
-            b.RT |= vlpet_tuning().wgs_mode << 8;
-#endif
-            auto go = [&](auto kern, int NSTG) -> hipError_t {
-                const size_t lds = (size_t)NSTG * (WgsGeo<RT>::STG_B + (masked ? 1024 : 0));
+            auto go = [&](auto kern) -> hipError_t {
+                const size_t lds = (size_t)3 * (WgsGeo<RT>::STG_B + (masked ? 1024 : 0));
                 hipError_t e2 = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
                 if (e2 != hipSuccess) return e2;
                 hipLaunchKernelGGL(kern, dim3(wg_grid(b, b.nslice)), dim3(VLPET_THREADS), lds, stream, b);
                 return hipGetLastError();
             };
-            if (masked) e = go(wgrad_stream_kernel<RT, 3, true>, 3);
-            else e = nstg == 4 ? go(wgrad_stream_kernel<RT, 4, false>, 4) : go(wgrad_stream_kernel<RT, 3, false>, 3);
+            e = masked ? go(wgrad_stream_kernel<RT, 3, true>) : go(wgrad_stream_kernel<RT, 3, false>);
             if (e != hipSuccess) return e;
             return launch_finalize(a, RT, xmax, rmax, stream, masked);
-        }
-    }
-    if constexpr (std::is_same<IO, __bf16>::value && RT <= 3) {
-        if (plain && use_tr) {
-            const size_t tiles = (size_t)4 * 2 * 32 * (64 * RT + 128);
-            const size_t redb = (size_t)3 * NV * 64 * sizeof(float);
-            const size_t lds = tiles > redb ? tiles : redb;
-            auto kern = wgrad_tr_kernel<RT>;
-            e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-            if (e != hipSuccess) return e;
-            WgradArgs b = a; b.nslice = xmax / 64;
-            hipLaunchKernelGGL(kern, dim3(wg_grid(b, b.nslice)), dim3(VLPET_THREADS), lds, stream, b);
-            e = hipGetLastError();
-            if (e != hipSuccess) return e;
-            return launch_finalize(a, RT, xmax, rmax, stream);
         }
     }
     const size_t lds = (size_t)3 * NV * 64 * sizeof(float);
