@@ -32,7 +32,7 @@ def test_form_query():
     lib = _lib.load()
     assert lib.vlpet_adapter_gate_bwd_form(28000, 768, 3, _lib.VLPET_BF16) == 2       # column-parallel pass
     assert lib.vlpet_adapter_gate_bwd_form(28000, 768, 1, _lib.VLPET_BF16) == 2
-    assert lib.vlpet_adapter_gate_bwd_form(28000, 768, 6, _lib.VLPET_BF16) == 2       # r = 192: pet_cols6.hip
+    assert lib.vlpet_adapter_gate_bwd_form(28000, 768, 6, _lib.VLPET_BF16) == 2       # r = 192: pet_cols6y.hip
     assert lib.vlpet_adapter_gate_bwd_form(28000, 768, 3, _lib.VLPET_F32) == 0        # fp32 (parity mode): rows + weight gradients
     assert lib.vlpet_adapter_gate_bwd_form(28000, 64, 3, _lib.VLPET_BF16) != 2        # d % 128 != 0
     assert lib.vlpet_adapter_gate_bwd_form(0, 768, 3, _lib.VLPET_BF16) < 0
@@ -44,7 +44,7 @@ def test_form_query():
     dict(M=8232), dict(M=28000), dict(M=31616),
     # workgroup boundaries of pass 1 (128 rows) and of a pass-2 step (32 rows), one row, other widths (one / eight column blocks)
     dict(M=1), dict(M=127), dict(M=129), dict(M=257, d=128, r=16, rg=16, nh=4), dict(M=5000, d=1024), dict(M=3000, d=1024, r=192, rg=192, nh=4, gate_scale=0.3),
-    # six tiles (csrc/pet_cols6.hip): the T5 script's r = r_g = 192 with its scales, unequal ranks, the additive gate
+    # six tiles (csrc/pet_cols6y.hip): the T5 script's r = r_g = 192 with its scales, unequal ranks, the additive gate
     dict(M=32, r=192, rg=192, nh=4, delta_scale=4.0, x2_scale=0.5, gate_scale=0.3), dict(M=1000, r=192, rg=192, nh=4, delta_scale=4.0, x2_scale=0.5, gate_scale=0.3),
     dict(M=999, r=192, rg=192, nh=4, gate_mode=2, gate_scale=0.3), dict(M=1000, r=192, rg=128, nh=4), dict(M=1000, r=128, rg=192, nh=4),
     dict(M=4321, r=160, rg=192, nh=4),
@@ -106,7 +106,7 @@ def _abi_case(M, dtype=torch.bfloat16, seed=11, gate_mode=1, r=96):
 @pytest.mark.parametrize("M,r", [(96, 96), (8232, 96), (28000, 96), (8232, 192), (16800, 192)])
 def test_incoming_dx1_travels_with_the_stage(M, r):
     """vlpet_adapter_gate_bwd_saved_acc on the column-parallel pass: dx1 = dx1_in + gate-branch gradient; the other nine
-    outputs are bit-identical to the plain call (M >= 8232: several steps per row chunk, ragged last step; r = 192: pet_cols6)."""
+    outputs are bit-identical to the plain call (M >= 8232: several steps per row chunk, ragged last step; r = 192: pet_cols6y)."""
     run, dxin = _abi_case(M, r=r)
     plain, acc = run([3], False), run([3], True)
     ref = plain[0] + dxin.float()

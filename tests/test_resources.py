@@ -13,11 +13,11 @@ BUILD = os.path.join(ROOT, "vl-pet_amd", "build")
 
 # (regex on the demangled name, why it is allowed to spill)
 ALLOWED = [
-    (r"^void pet_bwd_kernel<.*, 6, ", "r = 192 recompute-form row kernel: superseded by pet_dz6 + pet_cols6 (saved activations); fp32 = parity mode"),
+    (r"^void pet_bwd_kernel<.*, 6, ", "r = 192 recompute-form row kernel: superseded by pet_dz6 + pet_cols6y (saved activations); fp32 = parity mode"),
     (r"^void wgrad_kernel<.*, 6>", "register-tile weight gradients at six tiles: superseded by the streaming / column-parallel kernels"),
     (r"^void wgrad_stream_kernel<6, ", "six-tile streaming weight gradients: only the recompute / explicit-mask forms at r > 96 reach it (the training form runs pet_cols_ng)"),
     (r"^void pet_gate_bwd2_kernel<float, ", "fp32 IO = parity mode"),
-    (r"^void pet_gate_cols2?_kernel<", "round-2 two-pass backward (ABI phases bit 2 / debug switches): the default is pet_dz2 / pet_dz6 + pet_cols / pet_cols6"),
+    (r"^void pet_gate_cols2?_kernel<", "round-2 two-pass backward (ABI phases bit 2 / debug switches): the default is pet_dz2 / pet_dz6 + pet_cols / pet_cols6y"),
     (r"^void visproj_fwd2_kernel<float, ", "fp32 IO = parity mode"),
     (r"^void visproj_fwd2_kernel<__bf16, 24>", "round-2 fused K4 forward: superseded by visproj_gemm_kernel (round 5) wherever d_model is a multiple of 256 (both backbones); left for other widths and for visproj.K4_FORM = \"fused\" A/Bs"),
 ]

@@ -1,5 +1,10 @@
-// Helpers shared by the column-parallel K1 backward kernels (pet_cols.hip, pet_cols6.hip): compile-time loops, inline-asm LDS
-// accesses with hand-placed waits (see trread.h for why), counted vmcnt waits, bf16 packing, and the LDS swizzles.
+// The device header of the column-parallel and two-pass kernels (pet_cols.hip, pet_cols6y.hip, pet_cols_ng.hip, pet_dz2.hip,
+// pet_dz6.hip, pet_fwd2p.hip, visproj_gemm.hip, visproj_wgrad.hip, the streaming half of wgrad.hip).  First the tools: compile-time
+// loops, inline-asm LDS accesses with hand-placed waits (see trread.h for why), counted vmcnt waits, bf16 packing, the LDS swizzles,
+// the workgroup -> (group, member) map.  Then the pieces of a step that more than one kernel runs, one definition each ("pieces
+// of a step" below).  A piece is here only if no parameter tells it which caller it serves: compile-time geometry (RT, KT, PB,
+// PT_B, GRP, offsets) is a parameter, a flag for a caller is not -- and only if every kernel still compiles to the listing it had
+// (tools/same_code.py).  DESIGN.md section 4 lists what is shared and what stays apart for either reason.
 #pragma once
 #include <type_traits>
 #include <utility>
@@ -86,4 +91,76 @@ __host__ __device__ inline unsigned cols_grid(int U, int ngroups) {
     const int G = 32 / U;
     if (ngroups <= 8 * G) return 8u * (unsigned)U * (unsigned)((ngroups + 7) / 8);
     return 8u * (unsigned)(U * G + ((ngroups - 8 * G) * U + 7) / 8);
+}
+// Row-chunk plan of a column-parallel pass: at most groups_max chunks (one group of workgroups each, cols_groups_max), a chunk a
+// multiple of 32 rows, the chunks as even as that allows: no round quantisation.  cols_plan_groups: the groups of a pass whose
+// workgroups own 128 columns ((d / 128) column blocks per row chunk; at most 32 workgroups -- one per CU, the ring takes the LDS --
+// on an XCD).  (d < 128: the forms do not apply; the plan only sizes workspaces.)
+inline void cols_row_chunks(int64_t M, int groups_max, int* row_chunks, int64_t* rows_per_chunk) {
+    int64_t rc = groups_max;
+    const int64_t blocks32 = (M + 31) / 32;
+    if (rc > blocks32) rc = blocks32;
+    if (rc < 1) rc = 1;
+    const int64_t per = (blocks32 + rc - 1) / rc;
+    rc = (blocks32 + per - 1) / per;
+    *row_chunks = (int)rc;
+    *rows_per_chunk = per * 32;
+}
+inline int cols_plan_groups(int d) { const int ncb = d >= 128 ? d / 128 : 1; return cols_groups_max(ncb < 32 ? ncb : 32); }
+
+// ================================================================================================== pieces of a step
+// A wave-uniform pointer that the compiler must treat as a fresh scalar.  Every stream's address is sbase(row base) + a per-lane
+// 32-bit offset: with the base rebuilt from two readfirstlanes the per-lane part stays a 32-bit loop invariant (otherwise hipcc
+// hoists one 64-bit per-lane address per stream out of the loop and spills them).
+__device__ __forceinline__ const uint8_t* sbase(const uint8_t* p) {
+    const uint64_t u = reinterpret_cast<uint64_t>(p);
+    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
+    return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
+}
+// The ring tail.  The last step of a row chunk may have fewer than 32 rows: a lane whose row lies past the last valid one re-reads
+// that one (cols_rows_back = how many rows its source address steps back), and the bottleneck rows past the end are zeroed in LDS
+// after they landed, so that their products vanish (NT bottleneck tiles [32 rows x PB bytes] from `pt`; the caller's barrier follows).
+__device__ __forceinline__ uint32_t cols_rows_back(int row, int last) { return (uint32_t)(row > last ? row - last : 0); }
+template <int NT, int PB>
+__device__ __forceinline__ void cols_zero_tail(uint8_t* pt, int tid, int valid) {
+    const u32x4 z = {0u, 0u, 0u, 0u};
+    for (int q = tid; q < NT * 32 * (PB / 16); q += 512) {
+        const int rr = (q / (PB / 16)) & 31;
+        if (rr >= valid) *reinterpret_cast<u32x4*>(pt + (size_t)q * 16) = z;
+    }
+}
+// A fragment whose row (slot k = MFMA row (k & 3) + 8 (k >> 2) = register k of the lanes h = 0) is all ones: D[row][n] = column
+// sums of the B operand.  m = lane & 31.  Rebuilt at every use (the empty asm): as loop invariants the fragments cost four
+// registers per slot.
+__device__ __forceinline__ bf16x8 ones_row(int m, int k) {
+    int mm = m;
+    asm volatile("" : "+v"(mm));
+    const uint32_t w = (mm == (k & 3) + 8 * (k >> 2)) ? 0x3f803f80u : 0u;
+    const u32x4 v = {w, w, w, w};
+    return __builtin_bit_cast(bf16x8, v);
+}
+// The gate's elementwise backward of one element: (dh, dq) = the gradients at h and at the gate's pre-activation, from
+//     y = gs * h * g (ADD: gs * (h + g)),   g = sigmoid(bgu + Wgu z_g) = gt,   h = s2 * x2 + sd * (bu + Wu z_a)
+// in its three forms:
+//     plain:  dh = gs dy g,   dq = dh h (1 - g)        hy = h, recomputed by the caller from x2 and the adapter chain
+//     YF:     dh = gs dy g,   dq = dy y (1 - g)        hy = the forward's output y (= gs h g, so dy y (1 - g) = dh h (1 - g))
+//     ADD:    dh = gs dy,     dq = dh g (1 - g)        hy is not read
+// The caller forms the two scaled copies of dy, in this order and before hy: dys = gs * v * dy and (read by YF only) dyl = v * dy,
+// v = the row-validity factor, 1 or 0 -- rows past the end of a chunk give dh = dq = 0.  (pet_cols.hip folds gs * v into `gsr`,
+// pet_cols6y.hip keeps v as `live` next to it; the row kernels of pass 1 clamp their rows instead: dys = gs * dy, dyl = dy.)  The
+// order of the products is part of the contract: the results are rounded to bf16 for the matrix cores, and every kernel is held
+// to the code it compiled to before the four copies of this became one (the scaling of dy inside this function changed operand
+// orders in k1_cols_kernel, which is why it stays with the callers).
+template <bool ADD, bool YF>
+__device__ __forceinline__ void gate_bwd_ew(float dys, float dyl, float gt, float hy, float& dh, float& dq) {
+    if constexpr (ADD) {
+        dh = dys;
+        dq = dys * gt * (1.0f - gt);
+    } else if constexpr (YF) {
+        dh = dys * gt;
+        dq = dyl * hy * (1.0f - gt);
+    } else {
+        dh = dys * gt;
+        dq = dh * hy * (1.0f - gt);
+    }
 }

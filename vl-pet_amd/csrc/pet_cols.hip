@@ -53,8 +53,7 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
     // LDS round trips are what a step's instruction stream waits for (a wave alone covers none of them), so operands are
     // requested in batches as large as the registers allow and each batch is waited for once:
     constexpr int GRP = 6 < KT ? (KT % 6 == 0 ? 6 : KT) : KT;   // B fragments per batch of a projection: six where that divides the k-steps
-    constexpr bool WG_BOTH = true;                      // both 16-row k-steps of a weight-gradient job in one batch
-    constexpr bool EW_AHEAD = true;                     // all dy / x2 pieces of the elementwise stage requested at once
+    // (a weight-gradient job: both 16-row k-steps in one batch; the elementwise stage: all dy / x2 pieces requested at once)
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     // ---- which (column block, row chunk): the column blocks of a row chunk share an XCD (they re-read the same bottleneck rows)
@@ -97,13 +96,6 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
         poff[j] = (uint32_t)(prow[j] * PB + ((sig % (PB / 16)) ^ gsw(prow[j])) * 16);
         pdst[j] = (uint32_t)(X_B + t * PT_B + piece * 1024);
     }
-    // a wave-uniform pointer the compiler must treat as a fresh scalar: keeps the per-lane part of an address a 32-bit loop
-    // invariant (otherwise hipcc hoists one 64-bit per-lane address per stream out of the loop and spills them)
-    auto sbase = [](const uint8_t* p) {
-        const uint64_t u = reinterpret_cast<uint64_t>(p);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-        return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
-    };
     auto issue = [&](int s) {
         const int64_t rb = r_begin + 32 * (int64_t)s;
         uint8_t* st = smem + (size_t)(s % NSTG) * STG_B;
@@ -114,12 +106,12 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
             for (int j = 0; j < RT; ++j) glds16(sbase(pbase[j] + rb * PB) + poff[j], st + pdst[j]);
         } else {                                        // last step of the chunk: rows past the end re-read the last row
             const int last = (int)(r_end - rb) - 1;
-            const uint32_t xo = xoff - (uint32_t)(xrow > last ? xrow - last : 0) * (uint32_t)ld2;
+            const uint32_t xo = xoff - cols_rows_back(xrow, last) * (uint32_t)ld2;
 #pragma unroll
             for (int t = 0; t < NX; ++t) glds16_row(sbase(xbase[t] + rb * ld2) + xo, st + xdst[t]);
 #pragma unroll
             for (int j = 0; j < RT; ++j)
-                glds16(sbase(pbase[j] + rb * PB) + poff[j] - (uint32_t)(prow[j] > last ? prow[j] - last : 0) * PB, st + pdst[j]);
+                glds16(sbase(pbase[j] + rb * PB) + poff[j] - cols_rows_back(prow[j], last) * PB, st + pdst[j]);
         }
     };
 
@@ -142,13 +134,6 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
             a_pbf[k] = (uint32_t)(X_B + m * PB + (((2 * k + h) ^ gsw(m)) * 16));                         // B fragment of row m, k-step 2j + k (+ 64 j)
         }
     }
-    auto ones_row = [&](int k) {          // A fragment whose row (slot k) is all ones: D[row][n] = column sums of the B operand
-        int mm = m;
-        asm volatile("" : "+v"(mm));      // (rebuilt at every use: as loop invariants the fragments cost four registers per slot)
-        const uint32_t w = (mm == (k & 3) + 8 * (k >> 2)) ? 0x3f803f80u : 0u;
-        const u32x4 v = {w, w, w, w};
-        return __builtin_bit_cast(bf16x8, v);
-    };
     const int RC = a.row_chunks;
     const int col = c0 + m;
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
@@ -172,13 +157,8 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
         __builtin_amdgcn_s_barrier();                                     // stage s has landed for every wave; stage s - 1 is free
         if (s + NSTG - 1 < nsteps) issue(s + NSTG - 1);
         const int valid = (int)(r_end - (r_begin + 32 * (int64_t)s));
-        if (valid < 32) {                                                 // zero the bottleneck rows past the end (their products must vanish)
-            const u32x4 z = {0u, 0u, 0u, 0u};
-            uint8_t* pt = smem + (size_t)(s % NSTG) * STG_B + X_B;
-            for (int q = tid; q < 4 * 32 * (PB / 16); q += 512) {
-                const int rr = (q / (PB / 16)) & 31;
-                if (rr >= valid) *reinterpret_cast<u32x4*>(pt + (size_t)q * 16) = z;
-            }
+        if (valid < 32) {
+            cols_zero_tail<4, PB>(smem + (size_t)(s % NSTG) * STG_B + X_B, tid, valid);
             __syncthreads();
         }
     };
@@ -196,38 +176,24 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
             for (int k = 0; k < GRP; ++k) { if (k) lgkm_tie(bf[k]); acc = mfma32(w[G.value * GRP + k], as_bf(bf[k]), acc); }
         });
     };
-    // weight-gradient products of one job: acc[ct] += P^T (tile TP) . X (row tile at xlo / xhi + XO); one 16-row k-step at a
-    // time (4 operands = 16 registers in flight)
+    // weight-gradient products of one job: acc[ct] += P^T (tile TP) . X (row tile at xlo / xhi + XO); both 16-row k-steps
+    // in one batch (4 + 4 RT operands in flight)
     auto wg_products = [&](uint32_t sb, auto TPC, auto XOC, uint32_t xlo, uint32_t xhi, f32x16* acc, int slot) {
         constexpr int TP = decltype(TPC)::value, XO = decltype(XOC)::value;
-        if constexpr (WG_BOTH) {
-            TrOp bx[2], ap[2][RT];
-            sfor<2>([&](auto KS) {
-                constexpr int ks = KS.value;
-                tr_read2<XO + ks * 16 * 128>(bx[ks], xlo, xhi);
-                sfor<RT>([&](auto CT) { tr_read2<TP * PT_B + 64 * CT.value + ks * 16 * PB>(ap[ks][CT.value], sb + a_ptr[0], sb + a_ptr[1]); });
-            });
-            tr_fence(bx[0]);
+        TrOp bx[2], ap[2][RT];
+        sfor<2>([&](auto KS) {
+            constexpr int ks = KS.value;
+            tr_read2<XO + ks * 16 * 128>(bx[ks], xlo, xhi);
+            sfor<RT>([&](auto CT) { tr_read2<TP * PT_B + 64 * CT.value + ks * 16 * PB>(ap[ks][CT.value], sb + a_ptr[0], sb + a_ptr[1]); });
+        });
+        tr_fence(bx[0]);
 #pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
-                if (ks) tr_tie(bx[ks]);
-                const bf16x8 vx = tr_val(bx[ks]);
-                if (slot >= 0) sx = mfma32(ones_row(slot), vx, sx);
+        for (int ks = 0; ks < 2; ++ks) {
+            if (ks) tr_tie(bx[ks]);
+            const bf16x8 vx = tr_val(bx[ks]);
+            if (slot >= 0) sx = mfma32(ones_row(m, slot), vx, sx);
 #pragma unroll
-                for (int ct = 0; ct < RT; ++ct) { tr_tie(ap[ks][ct]); acc[ct] = mfma32(tr_val(ap[ks][ct]), vx, acc[ct]); }
-            }
-        } else {
-            sfor<2>([&](auto KS) {
-                constexpr int ks = KS.value;
-                TrOp bx, ap[RT];
-                tr_read2<XO + ks * 16 * 128>(bx, xlo, xhi);
-                sfor<RT>([&](auto CT) { tr_read2<TP * PT_B + 64 * CT.value + ks * 16 * PB>(ap[CT.value], sb + a_ptr[0], sb + a_ptr[1]); });
-                tr_fence(bx);
-                const bf16x8 vx = tr_val(bx);
-                if (slot >= 0) sx = mfma32(ones_row(slot), vx, sx);
-#pragma unroll
-                for (int ct = 0; ct < RT; ++ct) { tr_tie(ap[ct]); acc[ct] = mfma32(tr_val(ap[ct]), vx, acc[ct]); }
-            });
+            for (int ct = 0; ct < RT; ++ct) { tr_tie(ap[ks][ct]); acc[ct] = mfma32(tr_val(ap[ks][ct]), vx, acc[ct]); }
         }
     };
 
@@ -317,37 +283,24 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
                 project_up(I1{}, std::integral_constant<int, 512>{}, wG, aG);
                 const float gsr = m < valid ? a.gs : 0.f;                 // rows past the end: dh = dq = 0
                 u32x2 dyv[4], x2v[4];
-                if constexpr (EW_AHEAD) {                                 // (requested while the projections' MFMAs run)
-                    sfor<4>([&](auto C) {
-                        lds_read8<8 * (C.value & 1)>(dyv[C.value], sb + a_xcl[C.value >> 1]);
-                        lds_read8<8192 + 8 * (C.value & 1)>(x2v[C.value], sb + a_xcl[C.value >> 1]);
-                    });
-                    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dyv[0]), "+v"(x2v[0]), "+v"(dyv[1]), "+v"(x2v[1]), "+v"(dyv[2]), "+v"(x2v[2]), "+v"(dyv[3]), "+v"(x2v[3]) :: "memory");
-                }
+                sfor<4>([&](auto C) {                                     // (requested while the projections' MFMAs run)
+                    lds_read8<8 * (C.value & 1)>(dyv[C.value], sb + a_xcl[C.value >> 1]);
+                    lds_read8<8192 + 8 * (C.value & 1)>(x2v[C.value], sb + a_xcl[C.value >> 1]);
+                });
+                asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dyv[0]), "+v"(x2v[0]), "+v"(dyv[1]), "+v"(x2v[1]), "+v"(dyv[2]), "+v"(x2v[2]), "+v"(dyv[3]), "+v"(x2v[3]) :: "memory");
                 sfor<4>([&](auto C) {                                     // 4 columns at a time (a small live set): dy, x2 in, dh, dq out
                     constexpr int c = C.value;
-                    if constexpr (!EW_AHEAD) {
-                        lds_read8<8 * (c & 1)>(dyv[c], sb + a_xcl[c >> 1]);
-                        lds_read8<8192 + 8 * (c & 1)>(x2v[c], sb + a_xcl[c >> 1]);
-                    }
                     // (the statement also pins this chunk's share of the projections behind the previous chunk's stores: hipcc would
                     //  otherwise start all 16 sigmoids at once and keep their temporaries live)
-                    if constexpr (EW_AHEAD) asm volatile("" : "+v"(dyv[c]), "+v"(x2v[c]), "+v"(aG[4 * c]), "+v"(aG[4 * c + 1]), "+v"(aG[4 * c + 2]), "+v"(aG[4 * c + 3]) :: "memory");
-                    else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dyv[c]), "+v"(x2v[c]), "+v"(aG[4 * c]), "+v"(aG[4 * c + 1]), "+v"(aG[4 * c + 2]), "+v"(aG[4 * c + 3]) :: "memory");
+                    asm volatile("" : "+v"(dyv[c]), "+v"(x2v[c]), "+v"(aG[4 * c]), "+v"(aG[4 * c + 1]), "+v"(aG[4 * c + 2]), "+v"(aG[4 * c + 3]) :: "memory");
                     float dh[4], dq[4];
 #pragma unroll
                     for (int j = 0; j < 4; ++j) {
                         const int e = 4 * c + j;
                         const float gt = sigm(aG[e]);
                         const float dyp = gsr * ((j & 1) ? bf_hi(dyv[c][j >> 1]) : bf_lo(dyv[c][j >> 1]));
-                        if constexpr (ADD) {
-                            dh[j] = dyp;
-                            dq[j] = dyp * gt * (1.0f - gt);
-                        } else {
-                            const float hv = s2 * ((j & 1) ? bf_hi(x2v[c][j >> 1]) : bf_lo(x2v[c][j >> 1])) + sd * aA[e];
-                            dh[j] = dyp * gt;
-                            dq[j] = dh[j] * hv * (1.0f - gt);
-                        }
+                        const float hv = ADD ? 0.f : s2 * ((j & 1) ? bf_hi(x2v[c][j >> 1]) : bf_lo(x2v[c][j >> 1])) + sd * aA[e];
+                        gate_bwd_ew<ADD, false>(dyp, 0.f, gt, hv, dh[j], dq[j]);
                     }
                     typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
                     const bf16x4 th = {(__bf16)dh[0], (__bf16)dh[1], (__bf16)dh[2], (__bf16)dh[3]};
@@ -370,9 +323,9 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
                     tr_read2<0>(ap[0], sb + a_ptr[0] + off, sb + a_ptr[1] + off);
                     tr_read2<16 * PB>(ap[1], sb + a_ptr[0] + off, sb + a_ptr[1] + off);
                     tr_fence(ap[0]);
-                    sx = mfma32(ones_row(2 + j), tr_val(ap[0]), sx);
+                    sx = mfma32(ones_row(m, 2 + j), tr_val(ap[0]), sx);
                     tr_tie(ap[1]);
-                    sx = mfma32(ones_row(2 + j), tr_val(ap[1]), sx);
+                    sx = mfma32(ones_row(m, 2 + j), tr_val(ap[1]), sx);
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");           // (every LDS access of this step is complete at the next barrier)
@@ -506,19 +459,8 @@ __global__ __launch_bounds__(512, 2) void k1_cols_kernel(ColzArgs a) {
     }
 }
 
-// Row chunks: (d / 128) column blocks x chunks workgroups, at most 32 per XCD (one per CU: the ring takes the LDS), i.e. at most
-// 8 * floor(32 / NCB) chunks; a chunk is a multiple of 32 rows.
-void k1_cols_plan(int64_t M, int d, int* row_chunks, int64_t* rows_per_chunk) {
-    const int ncb = d >= 128 ? d / 128 : 1;             // (d < 128: the form does not apply; the plan only sizes workspaces)
-    int64_t rc = cols_groups_max(ncb < 32 ? ncb : 32);
-    const int64_t blocks32 = (M + 31) / 32;
-    if (rc > blocks32) rc = blocks32;
-    if (rc < 1) rc = 1;
-    const int64_t per = (blocks32 + rc - 1) / rc;
-    rc = (blocks32 + per - 1) / per;
-    *row_chunks = (int)rc;
-    *rows_per_chunk = per * 32;
-}
+// Row chunks: (d / 128) column blocks x chunks workgroups, one group per row chunk (cols_common.h)
+void k1_cols_plan(int64_t M, int d, int* row_chunks, int64_t* rows_per_chunk) { cols_row_chunks(M, cols_plan_groups(d), row_chunks, rows_per_chunk); }
 
 bool k1_cols_applies(const PetBwdArgs& a, int io_fp32) {
     return !io_fp32 && (a.flags & PET_GATE) && a.saved != nullptr && !drop_active(a.drop) && (a.RT == 1 || a.RT == 3) &&

@@ -1,16 +1,29 @@
-// K1 backward, column-parallel pass 2 for SIX bottleneck tiles (r = r_g = 192), second form (round 5): the up-side weight gradients run ONE
-// STEP LATE and the up-side elementwise block starts from the forward's output.  Autograd of my_transformers/modeling_t5.py:366-390, 782-806
-// (the T5 script, scripts/image-text/T5-VL-PET-large.sh:41-59).  Read pet_cols6.hip first: same decomposition (four roles UE / UW / DE / DW
-// per column quarter, 64-column workgroups, 32-row steps), same partial-sum layout, same XCD placement.
+// K1 backward, column-parallel pass 2 for SIX bottleneck tiles (r = r_g = 192: the T5 script, scripts/image-text/T5-VL-PET-large.sh:41-59;
+// autograd of my_transformers/modeling_t5.py:366-390, 782-806).  Memory system (LDS-DMA rings, source-side swizzles, transpose reads) and
+// partial-sum layout are those of pet_cols.hip (read its header first); what changes is the register arithmetic, and with it the roles.
 //
-// What bounded pet_cols6.hip: a step was a CHAIN.  UW contracts this step's dh / dq (written by UE) with this step's z tiles, so a step had two
-// barriers -- stage hand-over, then the dh / dq hand-over -- and every other wave stood at the next stage barrier while UW ran its 24
-// MFMAs behind UE's projections and elementwise block: 3.8 us per 32 rows, 107-113 us at 18,250 rows for a pass whose MFMA pipes are
-// 17 % busy.  Here UW works on the PREVIOUS step's dh / dq / z while UE produces this step's: one barrier per step, the two halves of the
-// chain overlap.  The price is a third slot for the z tiles (they are read by UE in step s and by UW in step s + 1) -- 24 KiB that the
-// 160 KiB of LDS do not have next to two full stages -- and it is paid by taking out of LDS what only ONE wave reads:
-//   * dy and -- new -- y: a UE lane needs exactly the 16 contiguous columns of its row (32 bytes) of each; it loads them itself, one step
-//     ahead, into registers.  With y = gs * h * g the elementwise block is dh = gs * dy * g, dq = dy * y * (1 - g) (pet_dz2.hip's note):
+// The decomposition.  At r = 192 a wave's slice of ONE weight gradient ([192 x 32] fp32) is 96 registers and its slice of one weight 48, so
+// the two roles per column quarter of pet_cols.hip (48 + 48 weights, 96 + 96 accumulators) are FOUR here, two per SIMD:
+//     UE: Wgu resident (48);  the gate's up projection, elementwise dh / dq -> LDS tiles          UW: dWu, dWgu (192) + every bias sum
+//     DE: Wd^T, Wgd^T resident (96);  dx2 = s2*dh + p2, dx1 = p1 (+ dx1_in), the output stores     DW: dWd, dWgd (192)
+// The E roles hold weights and no accumulators, the W roles accumulators and no weights; UE and UW share a SIMD, so does the pair DE / DW.
+// A workgroup (8 waves = 2 column quarters x 4 roles) covers 64 columns and a row chunk, in 32-row steps.  The narrower workgroup has a
+// price: the four [M, 192] bottleneck tensors (1.5 KiB per row, as much as a row tensor) are re-read by d / 64 column blocks.  So the
+// column blocks come in two halves, and a GROUP = (row chunk, half) keeps its d / 128 workgroups on one XCD (block b runs on XCD b % 8:
+// cols_decode), sharing that L2's copies of the bottleneck rows; the two halves of a row chunk may sit on two XCDs.  An XCD takes at most
+// 32 workgroups (one per CU), hence half as many row chunks as pet_cols.hip has (k1_cols6_plan).  Every W wave leaves its row chunk's
+// sums in wgrad.hip's workspace layout -- job j's [RC x 32 RT x d] blocks, then the column sums of dh / dq [RC x d], then those of
+// dpre_a / dpre_g [RC x 32 RT] -- and wgrad_finalize_kernel adds the row chunks in order (deterministic).
+//
+// The schedule: the up-side weight gradients run ONE STEP LATE, and the up-side elementwise block starts from the forward's output.  UW
+// contracts dh / dq (written by UE) with the z tiles of the same rows.  In the same step that is a CHAIN -- stage hand-over, UE's
+// projections and elementwise block, a second barrier for the dh / dq hand-over, then UW's 24 MFMAs while every other wave stands at the
+// next stage barrier: 3.8 us per 32 rows, 107-113 us at 18,250 rows for a pass whose MFMA pipes are 17 % busy.  Here UW works on the
+// PREVIOUS step's dh / dq / z while UE produces this step's: one barrier per step, the two halves of the chain overlap.  The price is a
+// third slot for the z tiles (they are read by UE in step s and by UW in step s + 1) -- 24 KiB that the 160 KiB of LDS do not have next
+// to two full stages -- and it is paid by taking out of LDS what only ONE wave reads:
+//   * dy and y: a UE lane needs exactly the 16 contiguous columns of its row (32 bytes) of each; it loads them itself, one step ahead,
+//     into registers.  With y = gs * h * g the elementwise block is dh = gs * dy * g, dq = dy * y * (1 - g) (cols_common.h gate_bwd_ew):
 //     no adapter-chain projection in UE at all (12 MFMAs, 12 fragment reads, 48 weight registers less), no x2 read by UE;
 //   * dx1_in: the same 32 bytes per DE lane.
 // LDS: z ring 3 x [z_a | z_g] 72 KiB, dpre ring 2 x [dp_a | dp_g] 48 KiB, row ring 2 x [x2 | x1] 16 KiB (only the W waves' transpose reads
@@ -42,7 +55,8 @@ __global__ __launch_bounds__(512, 2) void k1_cols6y_kernel(ColzArgs a) {
     constexpr int GRP = 6;                              // B fragments per batch of a projection
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
-    // ---- which (column block, row chunk): as in pet_cols6.hip
+    // ---- which (column block, row chunk).  Groups = (row chunk, half of the column blocks): the column blocks of a group share an XCD
+    // (block b runs on XCD b % 8) and with it the L2 copies of the bottleneck rows they all re-read
     const int d = a.d, NCB = d >> 6, CBH = NCB >> 1;
     int grp, mem;
     cols_decode((int)blockIdx.x, CBH, grp, mem);
@@ -79,11 +93,6 @@ __global__ __launch_bounds__(512, 2) void k1_cols6y_kernel(ColzArgs a) {
     const int xrow = 8 * (wave & 3) + (lane >> 3);
     const uint32_t xoff = (uint32_t)xrow * (uint32_t)ld2 + (uint32_t)(64 * cb * 2 + (((lane & 7) ^ fsw(xrow)) * 16));
     const uint8_t* xbase[2] = {reinterpret_cast<const uint8_t*>(a.x2), reinterpret_cast<const uint8_t*>(a.x1)};
-    auto sbase = [](const uint8_t* p) {                 // a wave-uniform pointer as a fresh scalar (see pet_cols.hip)
-        const uint64_t u = reinterpret_cast<uint64_t>(p);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-        return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
-    };
     auto issue_p = [&](int s) {                         // (E waves)
         const int64_t rb = r_begin + 32 * (int64_t)s;
         uint8_t* zs = smem + Z_OFF + (size_t)(s % GEO::NZ) * (2 * PT_B);
@@ -92,14 +101,14 @@ __global__ __launch_bounds__(512, 2) void k1_cols6y_kernel(ColzArgs a) {
 #pragma unroll
         for (int j = 0; j < NPW; ++j) {
             const int pr = (int)(poff[j] / PB);
-            glds16(sbase(pbase[j] + rb * PB) + poff[j] - (uint32_t)(pr > last ? pr - last : 0) * PB, (j < NPW / 2 ? zs : ds) + pdst[j]);
+            glds16(sbase(pbase[j] + rb * PB) + poff[j] - cols_rows_back(pr, last) * PB, (j < NPW / 2 ? zs : ds) + pdst[j]);
         }
     };
     auto issue_x = [&](int s) {                         // (W waves)
         const int64_t rb = r_begin + 32 * (int64_t)s;
         uint8_t* st = smem + XR_OFF + (size_t)(s % GEO::NXS) * XR_B;
         const int last = (int)(r_end - rb) - 1;
-        const uint32_t xo = xoff - (uint32_t)(xrow > last ? xrow - last : 0) * (uint32_t)ld2;
+        const uint32_t xo = xoff - cols_rows_back(xrow, last) * (uint32_t)ld2;
 #pragma unroll
         for (int t = 0; t < 2; ++t) glds16_row(sbase(xbase[t] + rb * ld2) + xo, st + t * 4096 + (wave & 3) * 1024);
     };
@@ -133,13 +142,6 @@ __global__ __launch_bounds__(512, 2) void k1_cols6y_kernel(ColzArgs a) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) a_pbf[k] = (uint32_t)(m * PB + (((2 * k + h) ^ fsw(m)) * 16));             // B fragment, k-step 4j + k (+ 128 j)
     }
-    auto ones_row = [&](int k) {
-        int mm = m;
-        asm volatile("" : "+v"(mm));
-        const uint32_t w = (mm == (k & 3) + 8 * (k >> 2)) ? 0x3f803f80u : 0u;
-        const u32x4 v = {w, w, w, w};
-        return __builtin_bit_cast(bf16x8, v);
-    };
     const int RC = a.row_chunks;
     const int col = c0 + m;
     using I0 = std::integral_constant<int, 0>; using I1 = std::integral_constant<int, 1>;
@@ -251,13 +253,7 @@ __global__ __launch_bounds__(512, 2) void k1_cols6y_kernel(ColzArgs a) {
                         const int e = 4 * c + j;
                         const float gt = sigm(aG[e]);
                         const float dyr = bf_at(cdy[e >> 3], e & 7);
-                        if constexpr (ADD) {
-                            dh[j] = gsr * dyr;
-                            dq[j] = dh[j] * gt * (1.0f - gt);
-                        } else {
-                            dh[j] = gsr * dyr * gt;
-                            dq[j] = live * dyr * bf_at(cy[e >> 3], e & 7) * (1.0f - gt);
-                        }
+                        gate_bwd_ew<ADD, !ADD>(gsr * dyr, live * dyr, gt, ADD ? 0.f : bf_at(cy[e >> 3], e & 7), dh[j], dq[j]);
                     }
                     typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
                     const bf16x4 th = {(__bf16)dh[0], (__bf16)dh[1], (__bf16)dh[2], (__bf16)dh[3]};
@@ -336,7 +332,7 @@ __global__ __launch_bounds__(512, 2) void k1_cols6y_kernel(ColzArgs a) {
                     tr_fence(ap[0]);
                     if constexpr (CG.value == 0) tr_tie(bx);
                     const bf16x8 vx = tr_val(bx);
-                    if constexpr (SLOT >= 0 && CG.value == 0) sx = mfma32(ones_row(SLOT), vx, sx);
+                    if constexpr (SLOT >= 0 && CG.value == 0) sx = mfma32(ones_row(m, SLOT), vx, sx);
 #pragma unroll
                     for (int c3 = 0; c3 < 3; ++c3) {
                         if (c3) tr_tie(ap[c3]);
@@ -376,7 +372,7 @@ __global__ __launch_bounds__(512, 2) void k1_cols6y_kernel(ColzArgs a) {
 #pragma unroll
                                 for (int c3 = 0; c3 < 3; ++c3) {
                                     if (c3) tr_tie(ap[c3]);
-                                    sx = mfma32(ones_row(2 + TT.value * RT + CG.value * 3 + c3), tr_val(ap[c3]), sx);
+                                    sx = mfma32(ones_row(m, 2 + TT.value * RT + CG.value * 3 + c3), tr_val(ap[c3]), sx);
                                 }
                             });
                         });
@@ -414,23 +410,12 @@ __global__ __launch_bounds__(512, 2) void k1_cols6y_kernel(ColzArgs a) {
     }
 }
 
-// Row chunks: (d / 64) column blocks in two halves; a group = (row chunk, half) keeps its d / 128 workgroups on one XCD, at
-// most 32 workgroups (one per CU) there: 8 * floor(32 / (d / 128)) groups = half as many row chunks.
-void k1_cols6_plan(int64_t M, int d, int* row_chunks, int64_t* rows_per_chunk) {
-    const int cbh = d >= 128 ? d / 128 : 1;
-    int64_t rc = cols_groups_max(cbh < 32 ? cbh : 32) / 2;
-    const int64_t blocks32 = (M + 31) / 32;
-    if (rc > blocks32) rc = blocks32;
-    if (rc < 1) rc = 1;
-    const int64_t per = (blocks32 + rc - 1) / rc;
-    rc = (blocks32 + per - 1) / per;
-    *row_chunks = (int)rc;
-    *rows_per_chunk = per * 32;
-}
+// Row chunks: two groups (the halves of the column blocks) per row chunk = half as many row chunks as groups (cols_common.h)
+void k1_cols6_plan(int64_t M, int d, int* row_chunks, int64_t* rows_per_chunk) { cols_row_chunks(M, cols_plan_groups(d) / 2, row_chunks, rows_per_chunk); }
 
 // six tiles, bf16, saved activations -- and what the elementwise block of this kernel starts from: the forward's output y, or the additive
-// gate (which needs neither h nor y).  (pet_cols6.hip, the round-3 form that recomputed h from x2, was removed in round 6: without y the
-// six-tile backward takes the older two-pass form of pet_gate_bwd3.hip.)
+// gate (which needs neither h nor y).  (There is no six-tile form that recomputes h from x2: without y the six-tile backward takes the
+// older two-pass form of pet_gate_bwd3.hip.)
 bool k1_cols6_applies(const PetBwdArgs& a, int io_fp32) {
     return !io_fp32 && (a.flags & PET_GATE) && a.saved != nullptr && !drop_active(a.drop) && a.RT == 6 &&
            a.d % 128 == 0 && a.d / 128 <= 32 && ((a.flags & PET_GATE_ADD) != 0 || a.y != nullptr) && Colz6yGeo<6>::lds() <= (size_t)160 * 1024;

@@ -74,11 +74,6 @@ __global__ __launch_bounds__(512, 2) void ng_dz_kernel(NgArgs a) {
         woff[j] = (uint32_t)((v * 2 * RT + (sl >> 1)) * 1024 + ((sl & 1) * 32 + i) * 16);
         if (piece < 4 * RT) nww = j + 1;
     }
-    auto sbase = [](const uint8_t* p) {
-        const uint64_t u = reinterpret_cast<uint64_t>(p);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-        return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
-    };
     const uint8_t* dyp = reinterpret_cast<const uint8_t*>(a.dy) + row0 * ld2;
     const uint8_t* wp = a.pk + pg.pack_bytes;
     auto issue = [&](int s) {
@@ -240,25 +235,20 @@ __global__ __launch_bounds__(512, 2) void ng_cols_kernel(NgArgs a) {
     }
     const bool mask_wave = DROP && wave == 7;
     const int NW = 2 + npj + (mask_wave ? 1 : 0);
-    auto sbase = [](const uint8_t* p) {
-        const uint64_t u = reinterpret_cast<uint64_t>(p);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-        return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
-    };
     const uint8_t* dyb = reinterpret_cast<const uint8_t*>(a.dy);
     const uint8_t* xb_ = reinterpret_cast<const uint8_t*>(a.x);
     auto issue = [&](int s) {
         const int64_t rb = r_begin + 32 * (int64_t)s;
         uint8_t* st = smem + (size_t)(s % NSTG) * STG_B;
         const int last = (int)(r_end - rb) - 1;         // rows past the end re-read the last row
-        const uint32_t xo = xoff - (uint32_t)(xrow > last ? xrow - last : 0) * (uint32_t)ld2;
+        const uint32_t xo = xoff - cols_rows_back(xrow, last) * (uint32_t)ld2;
         // row pieces: this wave brings rows 8 (wave & 3) .. of pair (wave >> 2) & 1 of BOTH tensors
         glds16_row(sbase(dyb + rb * ld2) + xo, st + (0 * 2 + ((wave >> 2) & 1)) * 4096 + (wave & 3) * 1024);
         glds16_row(sbase(xb_ + rb * ld2) + xo, st + (1 * 2 + ((wave >> 2) & 1)) * 4096 + (wave & 3) * 1024);
 #pragma unroll
         for (int j = 0; j < NPJ; ++j)
             if (j < npj)
-                glds16(sbase(pbase[j] + rb * PB) + poff[j] - (uint32_t)(prow[j] > last ? prow[j] - last : 0) * PB, st + pdst[j]);
+                glds16(sbase(pbase[j] + rb * PB) + poff[j] - cols_rows_back(prow[j], last) * PB, st + pdst[j]);
         if constexpr (DROP) {
             if (mask_wave) {                            // lane -> row lane & 31 (both halves of the wave bring the same 512 bytes)
                 const int mr = (lane & 31) > last ? last : (lane & 31);
@@ -283,13 +273,6 @@ __global__ __launch_bounds__(512, 2) void ng_cols_kernel(NgArgs a) {
 #pragma unroll
         for (int k = 0; k < 2; ++k) a_pbf[k] = (uint32_t)(X_B + PT_B + m * PB + (((2 * k + h) ^ gsw(m)) * 16));   // B fragment of dpre row m
     }
-    auto ones_row = [&](int k) {
-        int mm = m;
-        asm volatile("" : "+v"(mm));
-        const uint32_t w = (mm == (k & 3) + 8 * (k >> 2)) ? 0x3f803f80u : 0u;
-        const u32x4 v = {w, w, w, w};
-        return __builtin_bit_cast(bf16x8, v);
-    };
     const int RC = a.row_chunks;
     const int col = c0 + m;
 
@@ -311,13 +294,9 @@ __global__ __launch_bounds__(512, 2) void ng_cols_kernel(NgArgs a) {
         __builtin_amdgcn_s_barrier();
         if (s + NSTG - 1 < nsteps) issue(s + NSTG - 1);
         const int valid = (int)(r_end - (r_begin + 32 * (int64_t)s));
-        if (valid < 32) {                               // zero the bottleneck rows past the end (their products must vanish)
+        if (valid < 32) {
             const u32x4 z = {0u, 0u, 0u, 0u};
-            uint8_t* pt = smem + (size_t)(s % NSTG) * STG_B + X_B;
-            for (int q = tid; q < 2 * 32 * (PB / 16); q += 512) {
-                const int rr = (q / (PB / 16)) & 31;
-                if (rr >= valid) *reinterpret_cast<u32x4*>(pt + (size_t)q * 16) = z;
-            }
+            cols_zero_tail<2, PB>(smem + (size_t)(s % NSTG) * STG_B + X_B, tid, valid);
             // ... and the dy rows past the end (re-reads of the last row): they would count in the column sums of dy
             if (((tid >> 3) & 31) >= valid) *reinterpret_cast<u32x4*>(smem + (size_t)(s % NSTG) * STG_B + (size_t)tid * 16) = z;
             __syncthreads();
@@ -337,7 +316,7 @@ __global__ __launch_bounds__(512, 2) void ng_cols_kernel(NgArgs a) {
         for (int ks = 0; ks < 2; ++ks) {
             if (ks) tr_tie(bx[ks]);
             const bf16x8 vx = tr_val(bx[ks]);
-            if (slot >= 0) sx = mfma32(ones_row(slot), vx, sx);
+            if (slot >= 0) sx = mfma32(ones_row(m, slot), vx, sx);
 #pragma unroll
             for (int ct = 0; ct < RT; ++ct) { tr_tie(ap[ks][ct]); acc[ct] = mfma32(tr_val(ap[ks][ct]), vx, acc[ct]); }
         }
@@ -366,9 +345,9 @@ __global__ __launch_bounds__(512, 2) void ng_cols_kernel(NgArgs a) {
                     tr_read2<0>(ap[0], sb + a_ptr[0] + off, sb + a_ptr[1] + off);
                     tr_read2<16 * PB>(ap[1], sb + a_ptr[0] + off, sb + a_ptr[1] + off);
                     tr_fence(ap[0]);
-                    sx = mfma32(ones_row(2 + j), tr_val(ap[0]), sx);
+                    sx = mfma32(ones_row(m, 2 + j), tr_val(ap[0]), sx);
                     tr_tie(ap[1]);
-                    sx = mfma32(ones_row(2 + j), tr_val(ap[1]), sx);
+                    sx = mfma32(ones_row(m, 2 + j), tr_val(ap[1]), sx);
                 }
             }
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -463,16 +442,7 @@ bool ng_two_pass_applies(const PetBwdArgs& a, int io_fp32) {
     if (!(a.RT == 1 || a.RT == 3 || a.RT == 6) || a.d % 128 != 0 || a.d / 128 > 32) return false;
     return true;
 }
-void ng_cols_plan(int64_t M, int d, int* row_chunks, int64_t* rows_per_chunk) {
-    const int ncb = d >= 128 ? d / 128 : 1;
-    int64_t rc = cols_groups_max(ncb < 32 ? ncb : 32);
-    const int64_t blocks32 = (M + 31) / 32;
-    if (rc > blocks32) rc = blocks32;
-    if (rc < 1) rc = 1;
-    const int64_t per = (blocks32 + rc - 1) / rc;
-    rc = (blocks32 + per - 1) / per;
-    *row_chunks = (int)rc; *rows_per_chunk = per * 32;
-}
+void ng_cols_plan(int64_t M, int d, int* row_chunks, int64_t* rows_per_chunk) { cols_row_chunks(M, cols_plan_groups(d), row_chunks, rows_per_chunk); }
 
 template <int RT>
 static hipError_t launch_ng_rt(const NgArgs& a, int passes, hipStream_t stream) {

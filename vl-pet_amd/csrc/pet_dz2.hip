@@ -53,7 +53,6 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
     constexpr int KT = 2 * RT;
     constexpr int PB = GEO::PB, NPS = GEO::NPS, WT_B = GEO::WT_B, XT_B = GEO::XT_B, WS_B = GEO::WS_B, XS_B = GEO::XS_B;
     constexpr int X_OFF = GEO::X_OFF, AW = GEO::AW, AX = GEO::AX, NWS = GEO::NWS, NXS = GEO::NXS;
-    constexpr bool SPREAD = true;
     extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -96,11 +95,6 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
         woff[j] = (uint32_t)((v * KT + (sl >> 1)) * 1024 + ((sl & 1) * 32 + i) * 16);
         wdst[j] = (uint32_t)(t * WT_B + piece * 1024);
     }
-    auto sbase = [](const uint8_t* p) {     // a wave-uniform pointer as a fresh scalar (keeps the per-lane part a 32-bit loop invariant)
-        const uint64_t u = reinterpret_cast<uint64_t>(p);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-        return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
-    };
     const uint8_t* dyp = reinterpret_cast<const uint8_t*>(a.dy) + row0 * ld2;
     const uint8_t* x2p = reinterpret_cast<const uint8_t*>(YF ? a.y : a.res) + row0 * ld2;
     auto issue_w = [&](int s) {
@@ -166,9 +160,9 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
         const uint32_t xb = lds0 + (uint32_t)(X_OFF + (s % NXS) * XS_B);
         f32x16 aA, aG;
         if constexpr (NEED_A) project_up(sb, std::integral_constant<int, 0>{}, zA, aA, (s * 64) * 4);
-        if (SPREAD && s + AX < S) issue_x1(s + AX, 0);     // the row requests of the stage ahead are spread over the step: up front,
+        if (s + AX < S) issue_x1(s + AX, 0);    // the row requests of the stage ahead are spread over the step: up front,
         project_up(sb, std::integral_constant<int, 1>{}, zG, aG, (d + s * 64) * 4);
-        if (SPREAD && s + AX < S) issue_x1(s + AX, 1);     // all 56 pieces of a workgroup queue at the texture path at once (~1 k cycles of blocked issue)
+        if (s + AX < S) issue_x1(s + AX, 1);    // all 56 pieces of a workgroup queue at the texture path at once (~1 k cycles of blocked issue)
         u32x2 dyv[4], x2v[4];
         sfor<4>([&](auto Q) {
             lds_read8<0>(dyv[Q.value], xb + a_row[Q.value]);
@@ -185,18 +179,8 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
                 const float gt = sigm(aG[e]);
                 const float dyr = (j & 1) ? bf_hi(dyv[q][j >> 1]) : bf_lo(dyv[q][j >> 1]);
                 const float dy_ = gs * dyr;
-                if constexpr (ADD) {
-                    dh[j] = dy_;
-                    dq[j] = dy_ * gt * (1.0f - gt);
-                } else if constexpr (YF) {      // (the row ring's second tile is y)
-                    const float yv = (j & 1) ? bf_hi(x2v[q][j >> 1]) : bf_lo(x2v[q][j >> 1]);
-                    dh[j] = dy_ * gt;
-                    dq[j] = dyr * yv * (1.0f - gt);
-                } else {
-                    const float hv = s2 * ((j & 1) ? bf_hi(x2v[q][j >> 1]) : bf_lo(x2v[q][j >> 1])) + sd * aA[e];
-                    dh[j] = dy_ * gt;
-                    dq[j] = dh[j] * hv * (1.0f - gt);
-                }
+                const float x2r = (j & 1) ? bf_hi(x2v[q][j >> 1]) : bf_lo(x2v[q][j >> 1]);       // x2, or (YF: the row ring's second tile) y
+                gate_bwd_ew<ADD, YF>(dy_, dyr, gt, ADD ? 0.f : YF ? x2r : s2 * x2r + sd * aA[e], dh[j], dq[j]);
             }
             typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
             const bf16x4 th = {(__bf16)dh[0], (__bf16)dh[1], (__bf16)dh[2], (__bf16)dh[3]};
@@ -232,7 +216,8 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
         contract1(sb, std::integral_constant<int, 1>{}, bq, dzG);
     };
     // the frame of a step: everything this wave requested for stage s has landed (nothing younger is in flight), barrier (stage s is
-    // complete for every wave; the weight slot of stage s - 2 and the row slot of stage s - 1 are free), request stage s + 1
+    // complete for every wave; the weight slot of stage s - 2 and the row slot of stage s - 1 are free), request the weights of the
+    // stage ahead (its row requests are spread over the step: up_ew)
     auto step_top = [&](int s) {
         // requests of this wave younger than the last one stage s needs (program order per step: W(t + AW), X(t + AX))
         constexpr int AM = AW < AX ? AW : AX;
@@ -242,7 +227,6 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
         vm_wait(n);
         __builtin_amdgcn_s_barrier();
         if (s + AW < S) issue_w(s + AW);
-        if (!SPREAD && s + AX < S) issue_x(s + AX);
     };
 
     // The first stages' requests go out BEFORE this wave fetches its own z rows and the biases (round 5): the two used to be serial -- z and

@@ -90,11 +90,6 @@ __global__ __launch_bounds__(256) void k1_dz6_kernel(PetBwdArgs a) {
         woff[j] = (uint32_t)((v * KT + (sl >> 1)) * 1024 + ((sl & 1) * 32 + i) * 16);       // (+ 64 fh: the pack lane's 4 fh term)
         wdst[j] = (uint32_t)(t * WT_B + piece * 1024);
     }
-    auto sbase = [](const uint8_t* p) {     // a wave-uniform pointer as a fresh scalar (keeps the per-lane part a 32-bit loop invariant)
-        const uint64_t u = reinterpret_cast<uint64_t>(p);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-        return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
-    };
     const uint8_t* dyp = reinterpret_cast<const uint8_t*>(a.dy) + row0 * ld2;
     const uint8_t* x2p = reinterpret_cast<const uint8_t*>(YF ? a.y : a.res) + row0 * ld2;
     const uint8_t* wpa = a.pk_a + pg.pack_bytes;
@@ -242,18 +237,8 @@ __global__ __launch_bounds__(256) void k1_dz6_kernel(PetBwdArgs a) {
                     const float gt = sigm(aG[e]);
                     const float dyr = (j & 1) ? bf_hi(dyv[q][j >> 1]) : bf_lo(dyv[q][j >> 1]);
                     const float dy_ = gs * dyr;
-                    if constexpr (ADD) {
-                        dh[j] = dy_;
-                        dq[j] = dy_ * gt * (1.0f - gt);
-                    } else if constexpr (YF) {      // (the row ring's second tile is y)
-                        const float yv = (j & 1) ? bf_hi(x2v[q][j >> 1]) : bf_lo(x2v[q][j >> 1]);
-                        dh[j] = dy_ * gt;
-                        dq[j] = dyr * yv * (1.0f - gt);
-                    } else {
-                        const float hv = s2 * ((j & 1) ? bf_hi(x2v[q][j >> 1]) : bf_lo(x2v[q][j >> 1])) + sd * aA[e];
-                        dh[j] = dy_ * gt;
-                        dq[j] = dh[j] * hv * (1.0f - gt);
-                    }
+                    const float x2r = (j & 1) ? bf_hi(x2v[q][j >> 1]) : bf_lo(x2v[q][j >> 1]);       // x2, or (YF: the row ring's second tile) y
+                    gate_bwd_ew<ADD, YF>(dy_, dyr, gt, ADD ? 0.f : YF ? x2r : s2 * x2r + sd * aA[e], dh[j], dq[j]);
                 }
                 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
                 const bf16x4 th = {(__bf16)dh[0], (__bf16)dh[1], (__bf16)dh[2], (__bf16)dh[3]};

@@ -119,7 +119,7 @@ __global__ __launch_bounds__((RT + (RT == 6 ? 2 : 1)) * 64, 2) void k1_down_kern
             for (int qq = 0; qq < QN; ++qq) {
                 const int q = ld * QN + qq;
                 const int row = 8 * q + (lane >> 3);
-                const uint32_t o = roff[qq] - (uint32_t)(row > last ? row - last : 0) * (uint32_t)(F2_D * 2);
+                const uint32_t o = roff[qq] - cols_rows_back(row, last) * (uint32_t)(F2_D * 2);
 #pragma unroll
                 for (int st = 0; st < SSN; ++st) glds16_row(src + o + st * 128, dst + st * 4096 + q * 1024);
             }
@@ -364,18 +364,13 @@ __global__ __launch_bounds__(512, WPE) void k1_up_kernel(PetFwdArgs a, int row_c
         poff[j] = (uint32_t)(prow[j] * PB + ((sig % (PB / 16)) ^ gsw(prow[j])) * 16);
         pdst[j] = (uint32_t)(t * PT_B + piece * 1024);
     }
-    auto sbase = [](const uint8_t* p) {
-        const uint64_t u = reinterpret_cast<uint64_t>(p);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-        return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
-    };
     auto issue_x = [&](int s) {
         const int64_t rb = r_begin + 32 * (int64_t)s;
         uint8_t* st = smem + (size_t)(s % NX) * X_B;
         const int last = (int)(r_end - rb) - 1;                               // rows past the end re-read the last row
 #pragma unroll
         for (int k = 0; k < 2; ++k)
-            glds16_row(sbase(x2p + rb * (F2_D * 2)) + xoff[k] - (uint32_t)(xrow[k] > last ? xrow[k] - last : 0) * (uint32_t)(F2_D * 2), st + xdst[k]);
+            glds16_row(sbase(x2p + rb * (F2_D * 2)) + xoff[k] - cols_rows_back(xrow[k], last) * (uint32_t)(F2_D * 2), st + xdst[k]);
     };
     auto issue_z = [&](int s) {
         const int64_t rb = r_begin + 32 * (int64_t)s;
@@ -384,7 +379,7 @@ __global__ __launch_bounds__(512, WPE) void k1_up_kernel(PetFwdArgs a, int row_c
 #pragma unroll
         for (int j = 0; j < NB; ++j)
             if (wave + NW * j < NPZ)
-                glds16(sbase(zbase[pten[j] ? 1 : 0] + rb * PB) + poff[j] - (uint32_t)(prow[j] > last ? prow[j] - last : 0) * PB, st + pdst[j]);
+                glds16(sbase(zbase[pten[j] ? 1 : 0] + rb * PB) + poff[j] - cols_rows_back(prow[j], last) * PB, st + pdst[j]);
     };
     // per-lane LDS addresses (relative to the slot bases)
     uint32_t a_xcl[2], a_pbf[2];

@@ -110,11 +110,6 @@ __global__ __launch_bounds__(512, 2) void visproj_gemm_kernel(VisGemmArgs a) {
             prm[512 + tid] = a.beta ? a.beta[f] : 0.f;
         }
     }
-    auto sbase = [](const uint8_t* p) {     // a wave-uniform pointer as a fresh scalar (keeps the per-lane part a 32-bit loop invariant)
-        const uint64_t u = reinterpret_cast<uint64_t>(p);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-        return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
-    };
     const uint8_t* Xp = reinterpret_cast<const uint8_t*>(a.feats);
     const uint8_t* Wp = reinterpret_cast<const uint8_t*>(a.w);
     const uint8_t* Rp = reinterpret_cast<const uint8_t*>(a.R);

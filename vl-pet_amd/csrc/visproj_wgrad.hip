@@ -58,20 +58,15 @@ __global__ __launch_bounds__(512, 2) void k4_wgrad_kernel(K4WgArgs a) {
     const uint32_t xoff = (uint32_t)xrow * (uint32_t)ldx2 + (uint32_t)((((lane & 31) ^ ((xrow & 3) << 2))) * 16);
     const uint8_t* Pb = reinterpret_cast<const uint8_t*>(a.P) + (int64_t)ch * 768;
     const uint8_t* Xb = reinterpret_cast<const uint8_t*>(a.X) + (int64_t)ns * 512;
-    auto sbase = [](const uint8_t* p) {     // a wave-uniform pointer as a fresh scalar (keeps the per-lane part a 32-bit loop invariant)
-        const uint64_t u = reinterpret_cast<uint64_t>(p);
-        const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)u), hi = __builtin_amdgcn_readfirstlane((uint32_t)(u >> 32));
-        return reinterpret_cast<const uint8_t*>(((uint64_t)hi << 32) | lo);
-    };
     auto issue = [&](int s) {
         const int64_t rb = r_begin + 32 * (int64_t)s;
         uint8_t* st = smem + (size_t)(s % NSTG) * STG_B;
         const int last = (int)(r_end - rb) - 1;                          // rows past the end re-read the last row (wave-uniform test first)
         uint32_t po = poff, xo0 = xoff, xo1 = xoff + 16u * (uint32_t)ldx2;
         if (last < 31) {
-            po -= (uint32_t)(prow > last ? prow - last : 0) * (uint32_t)ldp2;
-            xo0 -= (uint32_t)(xrow > last ? xrow - last : 0) * (uint32_t)ldx2;
-            xo1 -= (uint32_t)(xrow + 16 > last ? xrow + 16 - last : 0) * (uint32_t)ldx2;
+            po -= cols_rows_back(prow, last) * (uint32_t)ldp2;
+            xo0 -= cols_rows_back(xrow, last) * (uint32_t)ldx2;
+            xo1 -= cols_rows_back(xrow + 16, last) * (uint32_t)ldx2;
         }
         const uint8_t* pb = sbase(Pb + rb * ldp2);
         const uint8_t* xb = sbase(Xb + rb * ldx2);
