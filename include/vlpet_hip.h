@@ -488,6 +488,20 @@ int vlpet_concat_dropout_fwd(const void* a, const void* v, void* x, int64_t B, i
                              int io_dtype, vlpet_stream_t stream);
 int vlpet_concat_dropout_bwd(const void* dx, void* da, void* dv, int64_t B, int La, int Lv, int d, float p, uint64_t seed,
                              int io_dtype, vlpet_stream_t stream);
+/* Prompt tuning (src/prompt/prompt_modeling.py InputPrompts; src/modeling_bart.py:776-833, src/modeling_t5.py:236-327): the same assembly
+ * with the encoder prompt in front, x [B, P + La + Lv, d] = dropout(cat([pre, a, v], dim = 1), p), where pre [P, d] holds the SAME rows for
+ * every batch item (the reference expands them to [B, P, d] before its MLP).  Mask: the Philox site over the row-major x, as above.
+ * Backward: da, dv as above; dpre [P, d] = sum over b of the masked, scaled dx[b, :P], accumulated in fp32 and rounded once, no atomics:
+ * B is split into vlpet_prefix_concat_chunks(B) chunks (a function of B alone), each chunk's sum goes to ws in b order and a second small
+ * launch adds the chunks in order -- bitwise repeatable.  ws: vlpet_prefix_concat_ws_bytes(B, P, d) bytes, 16-byte aligned, required
+ * exactly when dpre is wanted (VLPET_E_NULL without it, VLPET_E_SHAPE if passed without dpre).  Any of dpre / da / dv may be NULL (not
+ * wanted), all three NULL is VLPET_E_NULL.  Every extent positive, d % 8 == 0, 0 <= p < 1 (VLPET_E_SHAPE); VLPET_E_DTYPE; VLPET_E_ALIGN. */
+int vlpet_prefix_concat_chunks(int64_t B);
+size_t vlpet_prefix_concat_ws_bytes(int64_t B, int P, int d);
+int vlpet_prefix_concat_dropout_fwd(const void* pre, const void* a, const void* v, void* x, int64_t B, int P, int La, int Lv, int d,
+                                    float p, uint64_t seed, int io_dtype, vlpet_stream_t stream);
+int vlpet_prefix_concat_dropout_bwd(const void* dx, void* dpre, void* da, void* dv, float* ws, int64_t B, int P, int La, int Lv, int d,
+                                    float p, uint64_t seed, int io_dtype, vlpet_stream_t stream);
 
 /* ---- LM-head cross entropy (the loss of the training step; src/modeling_bart.py:1574-1586, src/modeling_t5.py:680-694) --
  * CrossEntropyLoss(ignore_index=-100, reduction='none') on logits [N, V] stored with a row stride of ld elements

@@ -134,6 +134,10 @@ SIGNATURES = {
     "vlpet_attn_bwd_bias": (c_int, [c_void_p] * 12 + [c_int] * 7 + [c_float, c_float, c_uint64, c_void_p]),
     "vlpet_concat_dropout_fwd": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_int, c_int, c_float, c_uint64, c_int, c_void_p]),
     "vlpet_concat_dropout_bwd": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_int, c_int, c_float, c_uint64, c_int, c_void_p]),
+    "vlpet_prefix_concat_chunks": (c_int, [c_int64]),
+    "vlpet_prefix_concat_ws_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "vlpet_prefix_concat_dropout_fwd": (c_int, [c_void_p] * 4 + [c_int64, c_int, c_int, c_int, c_int, c_float, c_uint64, c_int, c_void_p]),
+    "vlpet_prefix_concat_dropout_bwd": (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_int, c_int, c_float, c_uint64, c_int, c_void_p]),
     "vlpet_attn_fwd_kv": (c_int, [c_void_p] * 8 + [c_int] * 8 + [c_float, c_float, c_uint64, c_void_p]),
     "vlpet_attn_bwd_kv": (c_int, [c_void_p] * 12 + [c_int] * 8 + [c_float, c_float, c_uint64, c_void_p]),
     "vlpet_attn_long_fwd": (c_int, [c_void_p] * 7 + [c_int] * 8 + [c_float, c_void_p]),

@@ -116,3 +116,63 @@ def concat_dropout(a: torch.Tensor, v: torch.Tensor, p: float = 0.0, training: b
     if seed is None:
         seed = _draw_seed() if pe > 0.0 else 0
     return _ConcatDropFn.apply(a, v, pe, int(seed))
+
+
+# ------------------------------------------------------------------------------------------------ ... with a prompt in front
+FUSE_PREFIX_CONCAT = True       # A/B switch (tools/ab_switches.py: VLPET_NO_PREFIX_CONCAT=1): expand + torch.cat + F.dropout instead
+
+
+class _PrefixConcatDropFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pre, a, v, p, seed):
+        lib = _lib.load()
+        _need_cuda(pre, a, v)
+        pc, ac, vc = pre.contiguous(), a.contiguous(), v.contiguous()
+        B, La, d = ac.shape
+        P, Lv = pc.shape[0], vc.shape[1]
+        io = _io_dtype(ac)
+        x = torch.empty(B, P + La + Lv, d, dtype=ac.dtype, device=ac.device)
+        rc = _timed("prefix_concat_drop_fwd", B * (P + La + Lv), lambda: lib.vlpet_prefix_concat_dropout_fwd(
+            pc.data_ptr(), ac.data_ptr(), vc.data_ptr(), x.data_ptr(), B, P, La, Lv, d, float(p), seed, io, _stream()))
+        _lib.check(rc, "vlpet_prefix_concat_dropout_fwd")
+        ctx.cfg = (B, P, La, Lv, d, float(p), seed, io, ac.dtype)
+        return x
+
+    @staticmethod
+    def backward(ctx, dx):
+        lib = _lib.load()
+        B, P, La, Lv, d, p, seed, io, dtype = ctx.cfg
+        dxc = dx.contiguous()
+        if dxc.dtype != dtype:
+            dxc = dxc.to(dtype)
+        dev = dx.device
+        dpre = torch.empty(P, d, dtype=dtype, device=dev) if ctx.needs_input_grad[0] else None
+        da = torch.empty(B, La, d, dtype=dtype, device=dev) if ctx.needs_input_grad[1] else None
+        dv = torch.empty(B, Lv, d, dtype=dtype, device=dev) if ctx.needs_input_grad[2] else None
+        if dpre is None and da is None and dv is None:
+            return None, None, None, None, None
+        # fp32 partials of dpre, one [P, d] slab per batch chunk (the chunk count is a function of B alone)
+        ws = torch.empty(lib.vlpet_prefix_concat_ws_bytes(B, P, d) // 4, dtype=torch.float32, device=dev) if dpre is not None else None
+        rc = _timed("prefix_concat_drop_bwd", B * (P + La + Lv), lambda: lib.vlpet_prefix_concat_dropout_bwd(
+            dxc.data_ptr(), _ptr(dpre), _ptr(da), _ptr(dv), _ptr(ws), B, P, La, Lv, d, p, seed, io, _stream()))
+        _lib.check(rc, "vlpet_prefix_concat_dropout_bwd")
+        return dpre, da, dv, None, None
+
+
+def prefix_concat_dropout(pre: torch.Tensor, a: torch.Tensor, v: torch.Tensor, p: float = 0.0, training: bool = False,
+                          seed=None) -> torch.Tensor:
+    """``F.dropout(torch.cat([pre.expand(B, -1, -1), a, v], dim=1), p, training)`` for ``pre [P, d]`` (the encoder prompt: the same
+    rows for every batch item), ``a [B, La, d]``, ``v [B, Lv, d]`` in one HIP pass forward; backward one pass for ``da`` / ``dv`` and
+    the batch sum ``dpre`` (fp32 partials per batch chunk, added in chunk order: no atomics, bitwise repeatable) -- the joint encoder's
+    input assembly under prompt tuning (src/modeling_bart.py:776-820, src/modeling_t5.py:236-300).  Plain torch ops where the kernel
+    does not apply (CPU tensors, other dtypes, widths not a multiple of 8)."""
+    pe = float(p) if training else 0.0
+    ok = (FUSE_PREFIX_CONCAT and pre.is_cuda and a.is_cuda and v.is_cuda and pre.dim() == 2 and a.dim() == 3 and v.dim() == 3
+          and pre.dtype == a.dtype == v.dtype and a.dtype in (torch.bfloat16, torch.float32) and a.shape[0] == v.shape[0]
+          and pre.shape[1] == a.shape[2] == v.shape[2] and a.shape[2] % 8 == 0 and a.shape[0] > 0 and pre.shape[0] > 0
+          and a.shape[1] > 0 and v.shape[1] > 0)
+    if not ok:
+        return torch.nn.functional.dropout(torch.cat([pre.expand(a.shape[0], -1, -1), a, v], dim=1), p=p, training=training)
+    if seed is None:
+        seed = _draw_seed() if pe > 0.0 else 0
+    return _PrefixConcatDropFn.apply(pre, a, v, pe, int(seed))

@@ -8,7 +8,7 @@
 #include <stdio.h>
 #include <vector>
 
-#define VLPET_VERSION 670      // 670: vlpet_phm_expand_pair_fwd, vlpet_phm_expand_pair_bwd, vlpet_phm_workspace_bytes (phm.hip: Compacter's PHM weight expansion of one adapter and its backward); 660: vlpet_adapter_tail_fwd, vlpet_adapter_tail_applies, vlpet_adapter_tail_rows (adapter_tail.hip: sequential adapter + residual + norm in one launch, inference form); 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
+#define VLPET_VERSION 680      // 680: vlpet_prefix_concat_dropout_fwd, vlpet_prefix_concat_dropout_bwd, vlpet_prefix_concat_chunks, vlpet_prefix_concat_ws_bytes (prefix_cat.hip: the joint encoder's input assembly with a broadcast prompt in front, prompt tuning); 670: vlpet_phm_expand_pair_fwd, vlpet_phm_expand_pair_bwd, vlpet_phm_workspace_bytes (phm.hip: Compacter's PHM weight expansion of one adapter and its backward); 660: vlpet_adapter_tail_fwd, vlpet_adapter_tail_applies, vlpet_adapter_tail_rows (adapter_tail.hip: sequential adapter + residual + norm in one launch, inference form); 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
 #define VLPET_VERSION_R3 300      // 300: column-parallel K1 backward pass (pet_cols.hip), phases bits 3 / 4, vlpet_adapter_gate_bwd_form;
 #define VLPET_VERSION_R2 221      // 221: vlpet_sublayer_tail_reduce, vlpet_layernorm_bwd_xhat, vlpet_rmsnorm_{fwd,bwd}, vlpet_colsum;  round 2: LoRA dropout generator ABI, sliced AdamW, K3 training form; 210: strided attention entry points, streaming weight gradients; 220: low-rank visual projector
 
@@ -1524,6 +1524,52 @@ extern "C" int vlpet_concat_dropout_bwd(const void* dx, void* da, void* dv, int6
     const uint32_t thr = tail_thr(p);
     return herr(launch_cat_dropout(da, dv, const_cast<void*>(dx), B, La, Lv, d, thr, thr ? 1.0f / (1.0f - p) : 1.0f, seed, g_seed_ctr.load(), true,
                                    io_dtype == VLPET_F32, (hipStream_t)stream));
+}
+
+// ---- prompt tuning: x [B, P + La + Lv, d] = dropout(cat([pre [P, d] (every batch item), a [B, La, d], v [B, Lv, d]], dim = 1), p) -------
+extern "C" int vlpet_prefix_concat_chunks(int64_t B) {
+    if (B <= 0) return 0;
+    int cs, nc;
+    prefix_cat_split(B, &cs, &nc);
+    return nc;
+}
+extern "C" size_t vlpet_prefix_concat_ws_bytes(int64_t B, int P, int d) {
+    if (B <= 0 || P <= 0 || d <= 0) return 0;
+    return (size_t)vlpet_prefix_concat_chunks(B) * (size_t)P * (size_t)d * sizeof(float);
+}
+static int prefix_cat_common(int64_t B, int P, int La, int Lv, int d, float p, int io_dtype) {
+    if (B <= 0 || P <= 0 || La <= 0 || Lv <= 0 || d <= 0 || d % 8 != 0 || !(p >= 0.f && p < 1.f)) return VLPET_E_SHAPE;
+    if (!dtype_ok(io_dtype)) return VLPET_E_DTYPE;
+    return 0;
+}
+static PrefixCatArgs prefix_cat_args(const void* pre, const void* a, const void* v, void* x, int64_t B, int P, int La, int Lv, int d, float p,
+                                     uint64_t seed) {
+    PrefixCatArgs c{};
+    c.pre = pre; c.a = a; c.v = v; c.x = x; c.B = B; c.P = P; c.La = La; c.Lv = Lv; c.d = d;
+    prefix_cat_split(B, &c.CS, &c.NC);
+    c.thr = tail_thr(p); c.keep_scale = c.thr ? 1.0f / (1.0f - p) : 1.0f; c.seed = seed; c.seed_ctr = g_seed_ctr.load();
+    return c;
+}
+extern "C" int vlpet_prefix_concat_dropout_fwd(const void* pre, const void* a, const void* v, void* x, int64_t B, int P, int La, int Lv, int d,
+                                               float p, uint64_t seed, int io_dtype, vlpet_stream_t stream) {
+    if (!pre || !a || !v || !x) return VLPET_E_NULL;
+    if (int rc = prefix_cat_common(B, P, La, Lv, d, p, io_dtype)) return rc;
+    if (!aligned16(pre) || !aligned16(a) || !aligned16(v) || !aligned16(x)) return VLPET_E_ALIGN;
+    const PrefixCatArgs c = prefix_cat_args(pre, a, v, x, B, P, La, Lv, d, p, seed);
+    return herr(launch_prefix_cat(c, false, io_dtype == VLPET_F32, (hipStream_t)stream));
+}
+// ... backward: dx -> dpre [P, d] (summed over the batch), da, dv; any of them NULL: not wanted.  ws: vlpet_prefix_concat_ws_bytes(B, P, d)
+// bytes of fp32 partials, required exactly when dpre is wanted
+extern "C" int vlpet_prefix_concat_dropout_bwd(const void* dx, void* dpre, void* da, void* dv, float* ws, int64_t B, int P, int La, int Lv,
+                                               int d, float p, uint64_t seed, int io_dtype, vlpet_stream_t stream) {
+    if (!dx || (!dpre && !da && !dv) || (dpre && !ws)) return VLPET_E_NULL;
+    if (int rc = prefix_cat_common(B, P, La, Lv, d, p, io_dtype)) return rc;
+    if (!dpre && ws) return VLPET_E_SHAPE;            // a workspace without the output it serves: a caller's mistake
+    if (!aligned16(dx) || (dpre && !aligned16(dpre)) || (da && !aligned16(da)) || (dv && !aligned16(dv)) || (ws && !aligned16(ws)))
+        return VLPET_E_ALIGN;
+    PrefixCatArgs c = prefix_cat_args(nullptr, da, dv, const_cast<void*>(dx), B, P, La, Lv, d, p, seed);
+    c.dpre = dpre; c.ws = ws;
+    return herr(launch_prefix_cat(c, true, io_dtype == VLPET_F32, (hipStream_t)stream));
 }
 
 extern "C" int vlpet_act_dropout_bwd(const void* dy, const void* x, void* dx, int64_t n, int act, float p, uint64_t seed,

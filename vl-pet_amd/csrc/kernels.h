@@ -412,6 +412,18 @@ hipError_t launch_act_dropout(const ActDropArgs& a, bool bwd, int io_fp32, hipSt
 // x = dropout(cat([a, v], dim = 1), p) over [B, La | Lv, d] (actdrop.hip); bwd: x = dx in, a / v = da / dv out (nullptr: not wanted)
 hipError_t launch_cat_dropout(const void* a, const void* v, void* x, int64_t B, int La, int Lv, int d, uint32_t thr, float keep_scale,
                               uint64_t seed, const uint64_t* seed_ctr, bool bwd, int io_fp32, hipStream_t stream);
+// the same assembly with a broadcast prompt in front (prefix_cat.hip): x [B, P + La + Lv, d] = dropout(cat([pre [P, d], a, v], dim = 1)).
+// bwd: x = dx in, a / v = da / dv out, dpre [P, d] = the masked gradient summed over the batch through the fp32 partials in ws
+// ([NC, P, d]; B split into NC chunks of CS items: prefix_cat_split, a function of B alone).  nullptr outputs: not wanted.
+#define PREFIX_CAT_MAX_CHUNKS 32
+struct PrefixCatArgs {
+    const void* pre; const void* a; const void* v; void* x;
+    void* dpre; float* ws;
+    int64_t B; int P, La, Lv, d, CS, NC;
+    uint32_t thr; float keep_scale; uint64_t seed; const uint64_t* seed_ctr;
+};
+void prefix_cat_split(int64_t B, int* cs, int* nc);
+hipError_t launch_prefix_cat(const PrefixCatArgs& c, bool bwd, int io_fp32, hipStream_t stream);
 
 // token-level cross entropy over the LM-head logits (celoss.hip)
 struct CeArgs {

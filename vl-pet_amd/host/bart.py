@@ -35,8 +35,9 @@ from ..adapters import AdapterController
 from ..encoder_pet import apply_pet, build_pet, has_pet
 from ..lora import LoRALinearController, LoraConfig
 from ..visual import Downsample, LowRankVisualEmbedding, VisualEmbedding
-from .common import (COMPACTER_DEFAULTS, check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail,
-                     install_shared_phm_rule, is_key_mask, make_adapter_config, sequential_adapters, shift_right, unpack_vis_inputs,
+from ..prompt import PromptController
+from .common import (COMPACTER_DEFAULTS, PROMPT_DEFAULTS, check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail,
+                     install_shared_phm_rule, is_key_mask, make_adapter_config, make_prompt_config, sequential_adapters, shift_right, unpack_vis_inputs,
                      value_parallel_adapter)
 
 TASKS = ["vqa", "gqa", "nlvr", "caption"]
@@ -74,7 +75,7 @@ def vlpet_config(**over) -> SimpleNamespace:
         use_lora=False, lora_dim=4, lora_alpha=32, lora_dropout=0.1, use_single_lora=False, reduction_factor=8,
         use_encoder_multihead_up_zero_init=False, use_encoder_gating_large_x_lowrank_up_zero_init=False,
         use_decoder_enc_vpa_up_zero_init=False, freeze_vis_emb=False,
-        **COMPACTER_DEFAULTS,
+        **COMPACTER_DEFAULTS, **PROMPT_DEFAULTS,
     )
     for k, v in over.items():
         if not hasattr(c, k):
@@ -83,6 +84,7 @@ def vlpet_config(**over) -> SimpleNamespace:
     check_sequential_adapter_flags(c)
     task_list = [t for t in c.tasks.replace(" ", ",").split(",") if t]
     c.task_list = task_list
+    c.encoder_prompt_config = make_prompt_config(c, task_list)
     if c.use_adapter or c.use_compacter or c.use_decoder_enc_attn_value_parallel_adapter_down_dim:
         c.adapter_config = make_adapter_config(c, task_list)
     else:
@@ -524,8 +526,13 @@ class JointEncoder(nn.Module):
         if config.downsample:
             s = int(config.n_boxes ** 0.5)
             self.downsample = Downsample((s, s))
+        # src/modeling_bart.py:725-728 (prompt tuning); without the flag no attribute and no state-dict key, as before
+        if getattr(config, "encoder_prompt_config", None) is not None:
+            self.prompt_modules = PromptController(config.encoder_prompt_config)
 
     def forward(self, input_ids, vis_inputs, attention_mask=None, task=None, no_padding=False):
+        if getattr(self, "prompt_modules", None) is not None:
+            return self._forward_prompted(input_ids, vis_inputs, attention_mask, task, no_padding)
         B, L = input_ids.shape
         if attention_mask is None and not no_padding:
             # src/modeling_bart.py:817-818: the text mask defaults to input_ids != pad; it also becomes the decoder's
@@ -545,6 +552,31 @@ class JointEncoder(nn.Module):
             full = torch.cat([attention_mask.bool(), torch.ones(B, vis.shape[1], dtype=torch.bool,
                                                                 device=x.device)], dim=1)
             mask = full[:, None, None, :]
+        for layer in self.layers:
+            x = layer(x, mask, task)
+        return x, mask
+
+    def _forward_prompted(self, input_ids, vis_inputs, attention_mask, task, no_padding):
+        """src/modeling_bart.py:776-833 with an encoder prompt: [prompt | text | visual].  The prompt gets no positions; it goes through
+        ``layernorm_embedding`` with the text (a per-row norm: applied to its P rows once, not to B * P), and the key mask -- the
+        decoder's cross-attention mask and ``generate``'s too -- is [ones(P) | text mask | ones(V)] (none under ``no_padding``)."""
+        B, L = input_ids.shape
+        if attention_mask is None and not no_padding:
+            attention_mask = input_ids.ne(self.config.pad_token_id)
+        x = self.embed_tokens(input_ids) * self.embed_scale + self.embed_positions(L, input_ids.device)
+        vis = self.visual_embedding(*unpack_vis_inputs(vis_inputs, self.downsample, x.dtype)).to(x.dtype)   # K4
+        pre = self.prompt_modules.prompt_rows(task).to(x.dtype)                  # [P, d]: the MLP on P rows
+        P = pre.shape[0]
+        if self.config.share_vis_lang_layer_norm:
+            x = self.layernorm_embedding(torch.cat([pre.expand(B, -1, -1), x, vis], dim=1))
+            x = F.dropout(x, p=self.dropout, training=self.training)
+        else:
+            from ..act import prefix_concat_dropout
+            x = prefix_concat_dropout(self.layernorm_embedding(pre), self.layernorm_embedding(x), vis, self.dropout, self.training)
+        mask = None
+        if attention_mask is not None:
+            ones = lambda n: torch.ones(B, n, dtype=torch.bool, device=x.device)
+            mask = torch.cat([ones(P), attention_mask.bool(), ones(vis.shape[1])], dim=1)[:, None, None, :]
         for layer in self.layers:
             x = layer(x, mask, task)
         return x, mask

@@ -9,6 +9,7 @@ import torch
 
 from .. import functional as VF
 from ..adapters import AdapterConfig, AdapterController
+from ..prompt import EncoderPromptConfig
 
 
 def derived_weights(owner, slot, mods, dtype):
@@ -54,6 +55,24 @@ def sequential_adapters(config, side: str) -> bool:
 # no factorization)
 COMPACTER_DEFAULTS = dict(use_compacter=False, hypercomplex_division=4, phm_rank=1, shared_phm_rule=True, factorized_phm=True,
                           phm_init_range=0.01, shared_phm_rule_over_tasks=False)
+
+
+# the prompt-tuning flags of both hosts (param.py:141-143 and --mid_dim; scripts/*/single_prompt.sh: 40, 800, single)
+PROMPT_DEFAULTS = dict(encoder_prompt_len=0, decoder_prompt_len=0, mid_dim=768, use_single_prompt=False)
+
+
+def make_prompt_config(c, task_list):
+    """the ``encoder_prompt_config`` of a host config namespace (trainer_base.py:184-191), or None without ``encoder_prompt_len``;
+    ``input_dim`` = the model's width (the reference leaves it at 768, the width of its backbones)"""
+    if int(c.decoder_prompt_len) > 0:
+        raise NotImplementedError("vl-pet_amd: decoder_prompt_len > 0 (the reference's decoder-prefix path, src/modeling_t5.py:642-645) "
+                                  "is not provided: scripts/*/single_prompt.sh set encoder_prompt_len only")
+    if int(c.encoder_prompt_len) < 0:
+        raise ValueError("vl-pet_amd: encoder_prompt_len must not be negative")
+    if int(c.encoder_prompt_len) == 0:
+        return None
+    return EncoderPromptConfig(prompt_len=int(c.encoder_prompt_len), seq_len=int(c.encoder_prompt_len), input_dim=c.d_model,
+                               mid_dim=int(c.mid_dim), use_single_prompt=bool(c.use_single_prompt), tasks=list(task_list))
 
 
 def make_adapter_config(c, task_list) -> AdapterConfig:

@@ -27,9 +27,10 @@ from .. import adapter_tail as AT
 from ..adapters import AdapterController
 from ..encoder_pet import apply_pet, build_pet, has_pet
 from ..visual import Downsample, T5LayerNorm, VisualEmbedding
+from ..prompt import PromptController
 from .bart import TASKS, _linear
-from .common import (COMPACTER_DEFAULTS, check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail,
-                     install_shared_phm_rule, make_adapter_config, sequential_adapters, shift_right, unpack_vis_inputs,
+from .common import (COMPACTER_DEFAULTS, PROMPT_DEFAULTS, check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail,
+                     install_shared_phm_rule, make_adapter_config, make_prompt_config, sequential_adapters, shift_right, unpack_vis_inputs,
                      value_parallel_adapter)
 
 
@@ -173,7 +174,7 @@ def vlt5_config(**over) -> SimpleNamespace:
         use_lora=False, reduction_factor=8,
         use_encoder_multihead_up_zero_init=True, use_encoder_gating_large_x_lowrank_up_zero_init=True,
         use_decoder_enc_vpa_up_zero_init=True, freeze_vis_emb=False,
-        **COMPACTER_DEFAULTS,
+        **COMPACTER_DEFAULTS, **PROMPT_DEFAULTS,
     )
     for k, v in over.items():
         if not hasattr(c, k):
@@ -183,6 +184,7 @@ def vlt5_config(**over) -> SimpleNamespace:
     c.task_list = [t for t in c.tasks.replace(" ", ",").split(",") if t]
     c.adapter_config = make_adapter_config(c, c.task_list)
     c.lora_config = None
+    c.encoder_prompt_config = make_prompt_config(c, c.task_list)
     return c
 
 
@@ -508,17 +510,30 @@ class JointEncoder(nn.Module):
         if config.downsample:
             s = int(config.n_boxes ** 0.5)
             self.downsample = Downsample((s, s))
+        # src/modeling_t5.py:198-201 (prompt tuning); without the flag no attribute and no state-dict key, as before
+        if getattr(config, "encoder_prompt_config", None) is not None:
+            self.prompt_modules = PromptController(config.encoder_prompt_config)
 
     def forward(self, input_ids, vis_inputs, attention_mask=None, task=None):
         B, L = input_ids.shape
         x = self.embed_tokens(input_ids)
         vis = self.visual_embedding(*unpack_vis_inputs(vis_inputs, self.downsample, x.dtype)).to(x.dtype)             # K4
         V = vis.shape[1]
-        from ..act import concat_dropout
-        x = concat_dropout(x, vis, self.p, self.training)      # cat + dropout (src/modeling_t5.py:263, 300): one pass each way
         if attention_mask is None:
             attention_mask = input_ids.ne(self.config.pad_token_id)
-        full = torch.cat([attention_mask.to(torch.float32), torch.ones(B, V, device=x.device)], dim=1)
+        keep = attention_mask.to(torch.float32)
+        if getattr(self, "prompt_modules", None) is not None:
+            # src/modeling_t5.py:236-238, 271-276: [prompt | text | visual]; the prompt rows count as text for the relative-position
+            # bias (L = P + text length) and are always attended.  The MLP runs on the P rows once, not on B * P.
+            from ..act import prefix_concat_dropout
+            pre = self.prompt_modules.prompt_rows(task).to(x.dtype)
+            x = prefix_concat_dropout(pre, x, vis, self.p, self.training)
+            keep = torch.cat([torch.ones(B, pre.shape[0], device=x.device), keep], dim=1)
+            L += pre.shape[0]
+        else:
+            from ..act import concat_dropout
+            x = concat_dropout(x, vis, self.p, self.training)      # cat + dropout (src/modeling_t5.py:263, 300): one pass each way
+        full = torch.cat([keep, torch.ones(B, V, device=x.device)], dim=1)
         # relative position bias only between text positions (src/modeling_t5.py:311-327)
         sa0 = self.block[0].layer[0].SelfAttention
         text_bias = sa0.compute_bias(L, L)

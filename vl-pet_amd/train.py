@@ -66,8 +66,13 @@ def trainable_names(model: nn.Module, config) -> List[str]:
     if getattr(config, "unfreeze_layer_norms", False):      # trainer_base.py:375-380: every LayerNorm / T5LayerNorm module, wherever it sits
         from .visual import T5LayerNorm
         norm_params = {id(p) for m in model.modules() if isinstance(m, (nn.LayerNorm, T5LayerNorm)) for p in m.parameters()}
+    # prompt tuning: every parameter of a PromptController (trainer_base.py:347-351)
+    prompt_params = set()
+    if getattr(config, "encoder_prompt_len", 0) > 0 or getattr(config, "decoder_prompt_len", 0) > 0:
+        from .prompt import PromptController
+        prompt_params = {id(p) for m in model.modules() if isinstance(m, PromptController) for p in m.parameters()}
     for n, p in model.named_parameters():
-        on = id(p) in norm_params
+        on = id(p) in norm_params or id(p) in prompt_params
         if not config.freeze_vis_emb and "visual_embedding" in n:
             on = True
         if config.use_lora and ("lora" in n or "bias" in n):
@@ -229,11 +234,11 @@ def _flat_order(named):
 
 
 def _has_per_task_params(names, params) -> bool:
-    """True when some trainable parameter belongs to ONE task (``...adapters.<task>.*`` / ``lora_As.<task>`` entries that
-    are distinct tensors per task).  Shared modules registered under every task key (use_single_adapter /
+    """True when some trainable parameter belongs to ONE task (``...adapters.<task>.*`` / ``lora_As.<task>`` /
+    ``prompt_modules.prompts.<task>.*`` entries that are distinct tensors per task).  Shared modules registered under every task key (use_single_adapter /
     use_single_lora, adapters/adapter_controller.py:49-58, lora/controller.py:72-80) are one tensor with one name."""
     import re
-    pat = re.compile(r"(.*\.(?:adapters|lora_As|lora_Bs))\.([^.]+)(\..*)?$")
+    pat = re.compile(r"(.*\.(?:adapters|lora_As|lora_Bs|prompts))\.([^.]+)(\..*)?$")
     seen = {}
     for n in names:
         m = pat.match(n)
