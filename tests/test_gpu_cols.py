@@ -78,8 +78,9 @@ def _abi_case(M, dtype=torch.bfloat16, seed=11, gate_mode=1, r=96):
     assert lib.vlpet_adapter_gate_fwd_save(x1.data_ptr(), x2.data_ptr(), pa.buf.data_ptr(), pg.buf.data_ptr(), out.data_ptr(),
                                            sv.data_ptr(), M, d, tiles, gate_mode, 1.0, 1.0, 0.7, io, st) == 0
 
-    def run(phases_list, acc, from_y=None, sync_device=True):   # from_y: None = the round-4 entry points, False / True = ..._bwd_saved_y without / with y
-        dx1 = torch.zeros_like(x1); dx2 = torch.zeros_like(x2)
+    def run(phases_list, acc, from_y=None, sync_device=True, dx1=None):   # from_y: None = the round-4 entry points, False / True = ..._bwd_saved_y without / with y
+        dx1 = torch.zeros_like(x1) if dx1 is None else dx1      # (dx1: the caller's own output tensor)
+        dx2 = torch.zeros_like(x2)
         ws = torch.empty(nws, dtype=torch.uint8, device=dev)
         G = [torch.zeros_like(w) for w in W]
         common = [t.data_ptr() for t in G] + [r, r, ws.data_ptr(), nws, M, d, tiles, gate_mode, 1.0, 1.0, 0.7, io, st]
@@ -111,6 +112,34 @@ def test_incoming_dx1_travels_with_the_stage(M, r):
     plain, acc = run([3], False), run([3], True)
     ref = plain[0] + dxin.float()
     assert (acc[0] - ref).abs().max().item() <= TOL * ref.abs().max().item()
+    for a, b in zip(plain[1:], acc[1:]):
+        assert torch.equal(a, b)
+
+
+ADD_INPLACE_CAP = 2048 * 256 * 8        # optim.hip:137 (blocks capped at 2048) x OPT_THREADS = 256 x 8 elements per thread and iteration
+
+
+def test_incoming_dx1_through_the_add_pass_past_its_grid_cap():
+    """add_inplace_kernel (csrc/optim.hip) is the fallback that adds dx1_in for the K1 backward forms that do not add it in an
+    epilogue.  fp32 with r = 192 is such a form at every M: run_bwd (csrc/api.hip) takes the two-pass form (pet_gate_bwd3_applies:
+    RT == 6) but not the column-parallel kernels (bf16 only), so pass 2 is launch_pet_gate_cols followed by
+    launch_add_inplace(dxg, dx1_in, M * d) -- vlpet_adapter_gate_bwd_form says 1 for it.  M = 16,400, d = 768: 12.6 M elements,
+    three grid passes and a ragged fourth."""
+    import vlpet_amd.functional as F
+    from sentinel import pad_intact, padded_rows
+    from vlpet_amd import _lib
+    M, r, d = 16400, 192, 768
+    assert M * d >= 3 * ADD_INPLACE_CAP and (M * d) % ADD_INPLACE_CAP != 0
+    assert _lib.load().vlpet_adapter_gate_bwd_form(M, d, F.rank_tiles(r), _lib.VLPET_F32) == 1
+    run, dxin = _abi_case(M, dtype=torch.float32, r=r)
+    pbuf, pbody = padded_rows(M, d, torch.float32)
+    abuf, abody = padded_rows(M, d, torch.float32)
+    plain, acc = run([3], False, dx1=pbody), run([3], True, dx1=abody)
+    assert pad_intact(pbuf, pbody) and pad_intact(abuf, abody)
+    ref = plain[0].double() + dxin.double()
+    err = (acc[0].double() - ref).abs()
+    assert float(err.max()) <= 1e-5 * float(ref.abs().max())
+    assert bool((err <= 1e-5 * (plain[0].double().abs() + dxin.double().abs())).all())       # every element, at the size of its own terms
     for a, b in zip(plain[1:], acc[1:]):
         assert torch.equal(a, b)
 

@@ -10,6 +10,11 @@ from oracle import vlpet_oracle as O
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
 
+# ---- launch geometry (csrc/downsample.hip) ------------------------------------------------------------------------------------
+GATHER_CAP_ITEMS = 4096 * 256       # downsample.hip:113 (blocks capped at 256 * 16) x 256 threads: work items (8 channels of one output
+                                    # token) per grid pass of downsample_kernel, the gather form
+SLAB_LDS_BYTES = 64 * 1024          # downsample.hip:105: the slab form takes fp32 input whose s_in * s_in * 256 * 4 bytes fit in this
+
 
 def test_downsample_fixture_bit_exact():
     from vlpet_amd.visual import Downsample
@@ -50,3 +55,54 @@ def test_downsample_bench_shape_nlvr():
     yr, br, ir, orr = O.downsample_nlvr(x, boxes, img, obj)
     assert torch.equal(y.cpu(), yr.to(torch.bfloat16)) and torch.equal(i.cpu(), ir) and torch.equal(o.cpu(), orr)
     assert y.shape == (B, 72, 2048) and b.shape == (B, 72, 4)
+
+
+def _abi_downsample(x, s_out, out_dtype):
+    """vlpet_downsample_fwd on x [B, L, dim] into a NaN-filled output with sentinel rows behind it."""
+    from sentinel import pad_intact, padded_rows
+    from vlpet_amd import _lib
+    lib = _lib.load()
+    B, L, dim = x.shape
+    s_in = int(L ** 0.5)
+    io = lambda dt: _lib.VLPET_F32 if dt == torch.float32 else _lib.VLPET_BF16
+    xg = x.cuda()
+    buf, out = padded_rows(B * s_out * s_out, dim, out_dtype)
+    assert lib.vlpet_downsample_fwd(xg.data_ptr(), out.data_ptr(), B, s_in, s_out, dim, io(x.dtype), io(out_dtype),
+                                    torch.cuda.current_stream().cuda_stream) == 0
+    torch.cuda.synchronize()
+    assert pad_intact(buf, out)
+    return out.cpu().view(B, s_out * s_out, dim)
+
+
+@pytest.mark.parametrize("dtype,B,L,dim,out", [(torch.bfloat16, 360, 49, 2048, 6), (torch.float32, 64, 81, 2048, 4)])
+def test_downsample_gather_form_past_the_grid_cap(dtype, B, L, dim, out):
+    """The gather form (bf16 input; fp32 input whose 9 x 9 grid exceeds the slab form's LDS) against the oracle, bit for bit.  The
+    bf16 case is 3.3 M work items: every thread walks three and some a fourth."""
+    items = B * out * out * dim // 8
+    if dtype == torch.bfloat16:
+        assert items >= 3 * GATHER_CAP_ITEMS and items % GATHER_CAP_ITEMS != 0
+    else:
+        assert L * 256 * 4 > SLAB_LDS_BYTES
+    x = torch.randn(B, L, dim, generator=torch.Generator().manual_seed(B + L)).to(dtype)
+    ref = O.downsample(x.float(), (out, out)).to(dtype)
+    assert torch.equal(_abi_downsample(x, out, dtype), ref)
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["slab", "gather"])
+def test_downsample_nan_and_infinities_propagate_like_torch(dtype):
+    """NaN in some windows, -inf filling one whole window, +inf in one: the output equals O.downsample of the same input, NaN
+    positions included.  fp32 [3, 49, 2048] takes the slab form, the same in bf16 the gather form."""
+    B, L, dim, out = 3, 49, 2048, 6
+    assert L * 256 * 4 <= SLAB_LDS_BYTES and dim % 256 == 0
+    gen = torch.Generator().manual_seed(12)
+    x = torch.randn(B, L, dim, generator=gen)
+    x[torch.rand(B, L, dim, generator=gen) < 0.01] = float("nan")
+    g = x.view(B, 7, 7, dim)
+    g[0, 0:2, 0:2] = float("-inf")          # 7 -> 6: window (0, 0) is rows 0..1 x columns 0..1
+    g[1, 3, 3, ::2] = float("inf")
+    x = x.to(dtype)
+    ref = O.downsample(x.float(), (out, out)).to(dtype)
+    assert bool(ref.isnan().any()) and bool((ref[0, 0] == float("-inf")).all()) and bool((ref == float("inf")).any())
+    got = _abi_downsample(x, out, dtype)
+    assert torch.equal(got.isnan(), ref.isnan())
+    assert torch.equal(got.nan_to_num(nan=0.0), ref.nan_to_num(nan=0.0))

@@ -139,3 +139,83 @@ def test_gate_matches_oracle_d768(mode, add, gs, dtype):
         else:
             err = _rel(p.grad, ref_g)
         assert err <= (tol if dtype == torch.float32 else 1e-2), (n, err)
+
+
+# ---- the module path past the launch cap of the row kernels -------------------------------------------------------------------
+ROWGATE_ROW_CAP = 2048 * 4      # rowgate.hip:168 (cap = 256 * 8 workgroups) x rowgate.hip:22 (RG_WAVES = 4): rows in one round of waves
+PAST_CAP = [(147, 56, 128), (147, 56, 768)]             # M = 8,232: the last 40 rows are second rows of their waves
+SMALL_M = [(3, 5, 1024), (2, 7, 2048)]                  # four pieces per lane: fp32 d = 1024, bf16 d = 2048
+GATE_SHAPES = ([(s, dt) for s in PAST_CAP + SMALL_M[:1] for dt in (torch.float32, torch.bfloat16)]
+               + [(SMALL_M[1], torch.bfloat16)])
+
+
+def _gate_ref64(mode, x1, h, par, add, gs, dy):
+    """The gate on a given h, in fp64 (reference inline code: my_transformers/modeling_bart.py:1210-1231, 1256-1257)."""
+    x1r, hr = x1.double().requires_grad_(True), h.double().requires_grad_(True)
+    par = {k: v.detach().double().cpu().requires_grad_(True) for k, v in par.items()}
+    if mode == O.GATE_MIDDLE_Y:
+        y = hr + 1.0 + par["z"] if add else hr + hr * par["z"]
+    else:
+        gi = torch.cat([x1r, hr], 2) if mode == O.GATE_SMALL else x1r + hr
+        g = torch.sigmoid(gi @ par["w"].t() + par["b"])
+        if mode == O.GATE_SMALL:
+            g = g.mean(1, keepdim=True)
+        y = hr + g if add else hr * g
+    y = y * gs
+    y.backward(dy.double())
+    return y.detach(), x1r.grad, hr.grad, {k: v.grad for k, v in par.items()}
+
+
+@pytest.mark.parametrize("shape,dtype", GATE_SHAPES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v)[6:])
+@pytest.mark.parametrize("add,gs,x1_fp32", [(False, 1.0, False), (False, 0.3, True), (True, 0.3, True)])
+@pytest.mark.parametrize("mode", [O.GATE_SMALL, O.GATE_MIDDLE_X, O.GATE_MIDDLE_Y])
+def test_gate_functions_past_the_row_cap(mode, add, gs, x1_fp32, shape, dtype):
+    """gates.small_gate / middle_x_gate / middle_y_gate called directly on a given h (no K1 in front), against fp64 torch on the same
+    rounded inputs.  dy arrives as a non-contiguous view; with a bf16 h the row gates get x1 in bf16 (unscaled multiplicative case)
+    and in fp32 (the two cases with gate scale 0.3, multiplicative and additive; it holds the same rounded values: the host casts
+    it).  Every tensor is judged element-wise (gpu_cases.el_rel_err <= 0.1 at its default 2 % floor)
+    and with the per-tensor tolerances of test_gate_matches_oracle_d768; the scalar bias gradient at the scale of the weight
+    gradient, as argued there."""
+    from gpu_cases import el_rel_err
+    from vlpet_amd import gates
+    B, S, d = shape
+    assert (B * S > ROWGATE_ROW_CAP) == (shape in PAST_CAP)
+    gen = torch.Generator().manual_seed(B * S + d + mode)
+    q = lambda t: t.to(dtype)
+    x1, h = q(torch.randn(B, S, d, generator=gen)), q(torch.randn(B, S, d, generator=gen))
+    dy2 = q(torch.randn(B, S, 2 * d, generator=gen))
+    dy = dy2[..., :d]
+    assert not dy.is_contiguous()
+    if mode == O.GATE_MIDDLE_Y:
+        par = dict(z=nn.Parameter(torch.randn(d, generator=gen) * 0.05))
+    else:
+        lin = nn.Linear(2 * d if mode == O.GATE_SMALL else d, 1)
+        with torch.no_grad():
+            lin.weight.copy_(torch.randn(lin.weight.shape, generator=gen) * 0.05); lin.bias.copy_(torch.randn(1, generator=gen) * 0.05)
+        par = dict(w=lin.weight, b=lin.bias)
+    y_ref, dx1_ref, dh_ref, g_ref = _gate_ref64(mode, x1, h, par, add, gs, dy)
+    H = h.cuda().requires_grad_(True)
+    if mode == O.GATE_MIDDLE_Y:
+        par["z"].data = par["z"].data.cuda()
+        y = gates.middle_y_gate(H, par["z"], add, gs)
+        X1 = None
+    else:
+        lin.cuda()
+        X1 = (x1.float() if (dtype == torch.bfloat16 and x1_fp32) else x1).cuda().requires_grad_(True)
+        y = (gates.small_gate if mode == O.GATE_SMALL else gates.middle_x_gate)(X1, H, lin, add, gs)
+    y.backward(dy2.cuda()[..., :d])
+    torch.cuda.synchronize()
+    tol = 1e-3 if dtype == torch.float32 else 1e-2
+    pairs = [("y", y, y_ref), ("dh", H.grad, dh_ref)]
+    if X1 is not None:
+        pairs += [("dx1", X1.grad, dx1_ref), ("dw", par["w"].grad, g_ref["w"])]
+    else:
+        pairs += [("dz", par["z"].grad, g_ref["z"])]
+    for name, got, ref in pairs:
+        el, pt = el_rel_err(got, ref.float()), _rel(got, ref.float())
+        print(f"GATES {name} el {el:.2e} rel {pt:.2e}")
+        assert el <= 0.1 and pt <= tol, (name, el, pt)
+    if X1 is not None:
+        err = float((par["b"].grad.double().cpu() - g_ref["b"]).abs().max() / g_ref["w"].abs().max())
+        print(f"GATES db at the scale of dw {err:.2e}")
+        assert err <= tol, ("db", err)

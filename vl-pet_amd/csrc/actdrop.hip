@@ -43,8 +43,13 @@ template <int ACT> __device__ __forceinline__ float act_df(float x) {
     else if constexpr (ACT == VLPET_ACT_GELU_NEW) {
         const float x2 = x * x;
         const float u = 0.7978845608028654f * (x + 0.044715f * x * x2);
-        const float sg = sigmoid_fast(2.0f * u);              // = 0.5 (1 + tanh u);  1 - tanh^2 u = 4 sg (1 - sg)
-        return sg + x * 2.0f * sg * (1.0f - sg) * 0.7978845608028654f * (1.0f + 0.134145f * x2);
+        // sg = 0.5 (1 + tanh u) = 1 / (1 + e), e = exp(-2 u);  1 - tanh^2 u = 4 sg (1 - sg), with 1 - sg formed as e sg: the
+        // difference 1.0f - sg cancels for x > 0 down to the last bits of sg (x = 4: 1 - sg = 1.8e-5 known to 6e-8, 0.4 % of the
+        // term, 7e-7 of the derivative -- tests/test_gpu_act.py value sweep).  e sg <= 1; e = inf gives inf * 0, which the min drops.
+        const float e = __builtin_amdgcn_exp2f(-1.4426950408889634f * (2.0f * u));
+        const float sg = __builtin_amdgcn_rcpf(1.0f + e);     // = sigmoid_fast(2 u)
+        const float om = __builtin_fminf(e * sg, 1.0f);
+        return sg + x * 2.0f * sg * om * 0.7978845608028654f * (1.0f + 0.134145f * x2);
     } else {
         const GeluParts g = gelu_erf_parts(x);
         return g.cdf + x * 0.3989422804014327f * g.e;
