@@ -25,7 +25,11 @@ def test_pack_matches_spec(r, d, nh, fp32):
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
-@pytest.mark.parametrize("M,d,r,rg,nh", [(224, 768, 96, 96, 4), (40, 64, 8, 8, 4), (1000, 768, 96, 48, 4), (129, 128, 16, 40, 2)])
+# (40, 64, 96, 96) and (40, 64, 192, 192): d % 128 != 0 keeps bf16 off the column-parallel kernels of pet_cols.hip / pet_cols6y.hip, so
+# the two-pass backward of pet_gate_bwd3.hip runs at three and six tiles in bf16 as well (pet_gate_cols2_kernel<__bf16, 3, 2, 2>,
+# pet_gate_cols_kernel<__bf16, 6, 1, 2>); one ragged 32-row group + 8 rows
+@pytest.mark.parametrize("M,d,r,rg,nh", [(224, 768, 96, 96, 4), (40, 64, 8, 8, 4), (1000, 768, 96, 48, 4), (129, 128, 16, 40, 2),
+                                         (40, 64, 96, 96, 4), (40, 64, 192, 192, 4)])
 def test_k1_large_gate(dtype, M, d, r, rg, nh):
     check(C.run_k1(dtype, M=M, d=d, r=r, rg=rg, nh=nh), dtype)
 
@@ -35,6 +39,7 @@ def test_k1_variants(dtype):
     check(C.run_k1(dtype, M=130, gate_mode=0), dtype)                       # adapter only
     check(C.run_k1(dtype, M=130, gate_mode=2, gate_scale=0.3), dtype)       # additive gate + gate scale
     check(C.run_k1(dtype, M=100, r=192, rg=192, delta_scale=4.0, x2_scale=0.5, gate_scale=0.3), dtype)  # T5 script
+    check(C.run_k1(dtype, M=40, d=64, r=192, rg=192, gate_mode=2, gate_scale=0.3), dtype)   # six tiles with the additive gate (forward without loader waves, two-pass backward)
 
 
 _WG_CHILD = """
@@ -46,6 +51,10 @@ assert _lib.load().vlpet_debug_build() == 1
 dtype = getattr(torch, {dtype!r})
 tol = 1e-3 if dtype == torch.float32 else 1e-2
 for errs in (C.run_k1(dtype, M=1000, d=768, r=96, rg=96, nh=4), C.run_k1(dtype, M=333, d=128, r=16, rg=40, nh=2, gate_mode=2, gate_scale=0.3),
+             # one tile (r = 8) at every forced geometry: the forward and, in fp32, pass 1 of the two-pass backward (129 rows); past the
+             # 4,096-row rule at d % 128 != 0 the split backward's row kernel pet_gate_bwd2_kernel, one and three tiles, either dtype
+             C.run_k1(dtype, M=129, d=64, r=8, rg=8, nh=4), C.run_k1(dtype, M=4129, d=64, r=8, rg=8, nh=4, gate_mode=2, gate_scale=0.3),
+             C.run_k1(dtype, M=4129, d=64, r=96, rg=96, nh=4),
              C.run_k2(dtype, M=777)):
     assert max(errs.values()) <= tol, errs
 print("ok")

@@ -17,7 +17,7 @@ ALLOWED = [
     (r"^void wgrad_kernel<.*, 6>", "register-tile weight gradients at six tiles: superseded by the streaming / column-parallel kernels"),
     (r"^void wgrad_stream_kernel<6, ", "six-tile streaming weight gradients: only the recompute / explicit-mask forms at r > 96 reach it (the training form runs pet_cols_ng)"),
     (r"^void pet_gate_bwd2_kernel<float, ", "fp32 IO = parity mode"),
-    (r"^void pet_gate_cols2?_kernel<", "round-2 two-pass backward (ABI phases bit 2 / debug switches): the default is pet_dz2 / pet_dz6 + pet_cols / pet_cols6y"),
+    (r"^void pet_gate_cols2?_kernel<", "round-2 pass 2: fp32 IO (parity mode), widths with d % 128 != 0 or d > 4,096, and bf16 at six tiles with a multiplicative gate and no y (DESIGN.md section 4, dispatch table); other bf16 calls run pet_cols / pet_cols6y"),
     (r"^void visproj_fwd2_kernel<float, ", "fp32 IO = parity mode"),
     (r"^void visproj_fwd2_kernel<__bf16, 24>", "round-2 fused K4 forward: superseded by visproj_gemm_kernel (round 5) wherever d_model is a multiple of 256 (both backbones); left for other widths and for visproj.K4_FORM = \"fused\" A/Bs"),
 ]

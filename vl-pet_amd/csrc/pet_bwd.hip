@@ -23,11 +23,10 @@
 // rounds does.
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include "common.h"
 #include "kernels.h"
 #include "pet32.h"
-
-template <bool B> struct BoolK { static constexpr bool value = B; };
 
 template <typename IO, int RT, bool GATE, int WAVES>
 struct BwdLds {
@@ -421,7 +420,7 @@ __global__ __launch_bounds__(WAVES * 64) void pet_bwd_kernel(PetBwdArgs a) {
                     dfG[e] = frag_from_f32<NS>(dq8);
                 }
             };
-            if (gate_add) elementwise(BoolK<true>{}); else elementwise(BoolK<false>{});
+            if (gate_add) elementwise(std::bool_constant<true>{}); else elementwise(std::bool_constant<false>{});
             store_rows4(DH, rl, su * 128, t0, wave, lane);
             store_rows4(DQ, rl, su * 128, t1, wave, lane);
             wait_vm(rows_count(s + 2, s) + 2 * rl.n_inst);

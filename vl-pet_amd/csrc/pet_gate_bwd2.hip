@@ -29,22 +29,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
-#include "pet32.h"
-
-template <typename IO, int RT, int RG>
-struct Bwd2Lds {
-    static constexpr int NS = Geo4<IO>::NS;
-    static constexpr int SEG_KB = 4 * RT;
-    static constexpr int SEG_FR = SEG_KB / NS;
-    static constexpr int W_B = SEG_KB * 1024 * 2;
-    static constexpr int TILE_B = RG * 32 * 128;
-    static constexpr int ROW_B = 2 * TILE_B;
-    static constexpr int ROW_OFF = 2 * W_B;
-    static constexpr int BIAS_OFF = ROW_OFF + 3 * ROW_B;
-    static size_t bytes(int d) { return (size_t)BIAS_OFF + (size_t)2 * (32 * RT + d) * 4; }
-};
-
-template <bool B> struct Bool2 { static constexpr bool value = B; };
+#include "gate_chain.h"
 
 // LR = low-rank visual projector form (LowRankVisualEmbedding, autograd of src/modeling_bart.py:278-295): d is the OUTPUT
 // width; no residual term (res is never read), gate value sigmoid(.) + go, and no input gradients -- the features are data --
@@ -52,7 +37,7 @@ template <bool B> struct Bool2 { static constexpr bool value = B; };
 template <typename IO, int RT, int RG, bool LR = false>
 __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
     using G = Geo4<IO>;
-    using L = Bwd2Lds<IO, RT, RG>;
+    using L = ChainLds<IO, RT, RG>;
     constexpr int NS = G::NS;
     constexpr int KT = 2 * RT;
     constexpr int PW = L::SEG_KB / RG;              // weight pieces of the own segment per wave and stage
@@ -78,9 +63,6 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
     uint8_t* DQ = reinterpret_cast<uint8_t*>(a.dq);
     const uint8_t* DXIN = reinterpret_cast<const uint8_t*>(a.dxg_in);     // optional: dx1 += the sublayer tail's residual gradient
 
-    auto slot_w = [&](int j) { return smem + (size_t)j * L::W_B + (isA ? 0 : L::SEG_KB * 1024); };   // own segment
-    auto slot_t0 = [&](int j) { return smem + L::ROW_OFF + (size_t)j * L::ROW_B; };
-    auto slot_t1 = [&](int j) { return smem + L::ROW_OFF + (size_t)j * L::ROW_B + L::TILE_B; };
     // exchange buffer (row slot 2 during the middle phase): [written by A | written by G], per row group 16 fp32 per lane
     constexpr int XH = G::LW / 2;                   // features per lane and half
     uint8_t* xbuf = smem + L::ROW_OFF + (size_t)2 * L::ROW_B;
@@ -122,16 +104,16 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
     auto issue_mid_rows = [&](int su, bool both) {
         if (su >= S) return 0;
         int n = 0;
-        if constexpr (!LR) { if (both || isA) { glds_rows4(res, rl, su * 128, slot_t0(su & 1), rg); n += 4; } }
-        if (both || !isA) { glds_rows4(dy, rl, su * 128, slot_t1(su & 1), rg); n += 4; }
+        if constexpr (!LR) { if (both || isA) { glds_rows4(res, rl, su * 128, chain_slot_t0<L>(smem, su & 1), rg); n += 4; } }
+        if (both || !isA) { glds_rows4(dy, rl, su * 128, chain_slot_t1<L>(smem, su & 1), rg); n += 4; }
         return n;
     };
     // last-phase rows of block su: dh -> tile t0 of slot su % 3; the incoming dx1 (optional) -> tile t1
     auto issue_last_rows = [&](int su, bool both) {
         if (su >= S) return 0;
         int n = 0;
-        if (both || isA) { glds_rows4(DH, rl, su * 128, slot_t0(su % 3), rg); n += 4; }
-        if ((both || !isA) && DXIN != nullptr) { glds_rows4(DXIN, rl, su * 128, slot_t1(su % 3), rg); n += 4; }
+        if (both || isA) { glds_rows4(DH, rl, su * 128, chain_slot_t0<L>(smem, su % 3), rg); n += 4; }
+        if ((both || !isA) && DXIN != nullptr) { glds_rows4(DXIN, rl, su * 128, chain_slot_t1<L>(smem, su % 3), rg); n += 4; }
         return n;
     };
 
@@ -180,15 +162,8 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
         {
             int nrows = rl.n_inst;                  // chain G: only its dq stores of the previous block may still be in flight
             if (isA) { issue_w(st + 1, true); nrows = issue_mid_rows(su + 1, true); }
-            const uint8_t* w = slot_w(st & 1);
-#pragma unroll
-            for (int v = 0; v < G::NV; ++v) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 tb = *reinterpret_cast<const f32x4*>(bu + su * G::FE + 16 * v + 4 * q);
-                    au[v][4 * q] = tb[0]; au[v][4 * q + 1] = tb[1]; au[v][4 * q + 2] = tb[2]; au[v][4 * q + 3] = tb[3];
-                }
-            }
+            const uint8_t* w = chain_slot_w<L>(smem, isA, st & 1);
+            bias_seed<G::NV>(bu + su * G::FE, au);
             Frag<NS> wf[G::NV * KT];
 #pragma unroll
             for (int ks = 0; ks < KT; ++ks) {
@@ -220,9 +195,9 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
         // ================= stage b: elementwise backward of the own half, then the contraction over features
         {
             if (isA) issue_w(st + 1, true);
-            const uint8_t* w = slot_w(st & 1);
-            uint8_t* t0 = slot_t0(su & 1);
-            uint8_t* t1 = slot_t1(su & 1);
+            const uint8_t* w = chain_slot_w<L>(smem, isA, st & 1);
+            uint8_t* t0 = chain_slot_t0<L>(smem, su & 1);
+            uint8_t* t1 = chain_slot_t1<L>(smem, su & 1);
             const uint8_t* xb = xslot(1 - chain);
             auto elementwise = [&](auto add_c) {
                 constexpr bool ADD = decltype(add_c)::value;
@@ -267,7 +242,7 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
                     stage_lane_vals8<IO>(t1, trow, h, e, dq8);
                 }
             };
-            if (gate_add) elementwise(Bool2<true>{}); else elementwise(Bool2<false>{});
+            if (gate_add) elementwise(std::bool_constant<true>{}); else elementwise(std::bool_constant<false>{});
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();           // both halves of the dh / dq tiles of this row group are complete
             uint8_t* mine = isA ? t0 : t1;
@@ -325,8 +300,8 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
     for (int su = 0; su < S; ++su, ++st) {
         int nrows = 0;
         if (!isA) { issue_w(st + 1, true); nrows = issue_last_rows(su + 2, true); }
-        const uint8_t* w = slot_w(st & 1);
-        uint8_t* tile = isA ? slot_t0(su % 3) : slot_t1(su % 3);
+        const uint8_t* w = chain_slot_w<L>(smem, isA, st & 1);
+        uint8_t* tile = isA ? chain_slot_t0<L>(smem, su % 3) : chain_slot_t1<L>(smem, su % 3);
         f32x16 ax[G::NV];
 #pragma unroll
         for (int v = 0; v < G::NV; ++v) ax[v] = zero16();
@@ -365,27 +340,13 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_bwd2_kernel(PetBwdArgs a) {
     }
 }
 
-template <typename IO, int RT, int RG, bool LR = false>
-static hipError_t launch_one(const PetBwdArgs& a, hipStream_t stream) {
-    using L = Bwd2Lds<IO, RT, RG>;
-    const size_t lds = L::bytes(a.d);
-    auto kern = pet_gate_bwd2_kernel<IO, RT, RG, LR>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    const int rows = RG * 32;
-    const int blocks = (int)((a.M + rows - 1) / rows);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3(RG * 128), lds, stream, a);
-    return hipGetLastError();
-}
-
-template <typename IO, int RT>
+// row groups by pick_row_groups; workgroups of RG * 32 rows, 2 * RG waves, ChainLds::bytes(d) of LDS
+template <typename IO, int RT, bool LR>
 static hipError_t launch_rt(const PetBwdArgs& a, hipStream_t stream) {
-    switch (pick_row_groups(a.M, 4, 2)) {
-        case 4: return launch_one<IO, RT, 4>(a, stream);
-        case 3: if constexpr ((4 * RT) % 3 == 0) return launch_one<IO, RT, 3>(a, stream);   // (else: falls through)
-        default: return launch_one<IO, RT, 2>(a, stream);
-    }
+    return with_row_groups<RT>(a.M, [&](auto rg) {
+        constexpr int RG = decltype(rg)::value;
+        return launch_chain_rows<ChainLds<IO, RT, RG>, RG, RG * 128>(pet_gate_bwd2_kernel<IO, RT, RG, LR>, a, stream);
+    });
 }
 
 // true when this form applies: gated K1, saved activations, r <= 96, every dimension it was written for
@@ -394,23 +355,11 @@ bool pet_gate_bwd2_applies(const PetBwdArgs& a) {
 }
 
 hipError_t launch_pet_gate_bwd2(const PetBwdArgs& a, int io_fp32, hipStream_t stream) {
-    if (a.RT == 1) return io_fp32 ? launch_rt<float, 1>(a, stream) : launch_rt<__bf16, 1>(a, stream);
-    if (a.RT == 3) return io_fp32 ? launch_rt<float, 3>(a, stream) : launch_rt<__bf16, 3>(a, stream);
-    return hipErrorInvalidValue;
+    return with_io_rt<false>(io_fp32, a.RT, [&](auto io, auto rt) { return launch_rt<decltype(io), decltype(rt)::value, false>(a, stream); });
 }
 
 // low-rank visual projector form: saved activations, multiplicative gate, r, r_g <= 96
-template <typename IO, int RT>
-static hipError_t launch_lr(const PetBwdArgs& a, hipStream_t stream) {
-    switch (pick_row_groups(a.M, 4, 2)) {
-        case 4: return launch_one<IO, RT, 4, true>(a, stream);
-        case 3: if constexpr ((4 * RT) % 3 == 0) return launch_one<IO, RT, 3, true>(a, stream);   // (else: falls through)
-        default: return launch_one<IO, RT, 2, true>(a, stream);
-    }
-}
 hipError_t launch_pet_lowrank_bwd(const PetBwdArgs& a, int io_fp32, hipStream_t stream) {
     if (!a.saved || !(a.flags & PET_GATE) || (a.flags & PET_GATE_ADD) || drop_active(a.drop)) return hipErrorInvalidValue;
-    if (a.RT == 1) return io_fp32 ? launch_lr<float, 1>(a, stream) : launch_lr<__bf16, 1>(a, stream);
-    if (a.RT == 3) return io_fp32 ? launch_lr<float, 3>(a, stream) : launch_lr<__bf16, 3>(a, stream);
-    return hipErrorInvalidValue;
+    return with_io_rt<false>(io_fp32, a.RT, [&](auto io, auto rt) { return launch_rt<decltype(io), decltype(rt)::value, true>(a, stream); });
 }

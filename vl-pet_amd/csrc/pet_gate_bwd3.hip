@@ -1,12 +1,20 @@
 // K1 backward in two passes that move each [M, d] tensor as few times as the op allows (gated K1 with the forward's
-// saved activations, r <= 96).  Autograd of my_transformers/modeling_bart.py:1147-1155,1195-1209.
+// saved activations, r <= 192).  Autograd of my_transformers/modeling_bart.py:1147-1155,1195-1209.
 //
-// The previous form (pet_gate_bwd2.hip + wgrad.hip) moved ~11 units of d*M*b for 5 algorithmic: the row kernel wrote the
-// side products dh, dq, re-read dh for its last phase, and the column-parallel weight-gradient kernel then read x1, x2, dh
-// and dq again.  The structure of the op forces two passes (dz = Wu^T dh needs EVERY feature of a row before any input
-// gradient of that row exists, and the four [r x d] weight gradients are sums over EVERY row), so here the passes are
+// Who runs this today (run_bwd in api.hip; the table is in DESIGN.md section 4): bf16 at d % 128 == 0 has its own
+// column-parallel pass 2 (pet_cols.hip, pet_cols6y.hip) and, up to r = 96, its own pass 1 (pet_dz2.hip).  What comes here is
+// every fp32 call and every width with d % 128 != 0 -- at r = 192 whatever M, at r <= 96 up to 4,096 rows (pet_gate_bwd3_applies)
+// -- both passes; and pass 1 alone (pet_gate_dz_kernel<__bf16, 6, 2>) in front of pet_cols6y.hip at r = 192 where pet_dz6.hip
+// does not take the shape, the T5 benchmark step included.
 //
-//   pass 1  pet_gate_dz_kernel (row-parallel; the middle phase of pet_gate_bwd2_kernel and nothing else):
+// The split form (pet_gate_bwd2.hip + wgrad.hip; above 4,096 rows at r <= 96, and wherever the caller asks for the input
+// gradients first, `phases` bit 2) moves ~11 units of d*M*b for 5 algorithmic: the row kernel writes the side products dh, dq,
+// re-reads dh for its last phase, and the weight-gradient kernel then reads x1, x2, dh and dq again.  The structure of the op
+// forces two passes (dz = Wu^T dh needs EVERY feature of a row before any input gradient of that row exists, and the four
+// [r x d] weight gradients are sums over EVERY row), so here the passes are
+//
+//   pass 1  pet_gate_dz_kernel (row-parallel; the middle phase of pet_gate_bwd2_kernel and nothing else -- two kernels on the
+//           shared pieces of gate_chain.h: their stage bodies did not survive a move into one definition, see that header):
 //           reads dy, x2 (+ the saved z, gelu');  recomputes both up projections, dh, dq tile by tile, contracts
 //           dz_a += Wu^T dh, dz_g += Wgu^T dq in registers;  writes only dpre_a, dpre_g  [M, 32*RT].
 //   pass 2  pet_gate_cols_kernel (column-parallel: a workgroup owns one feature block of 128 bytes per row = one stage
@@ -31,27 +39,13 @@
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
-#include "pet32.h"
+#include "gate_chain.h"
 
 // ================================================================================================== pass 1
 template <typename IO, int RT, int RG>
-struct DzLds {
-    static constexpr int NS = Geo4<IO>::NS;
-    static constexpr int SEG_KB = 4 * RT;
-    static constexpr int W_B = SEG_KB * 1024 * 2;
-    static constexpr int TILE_B = RG * 32 * 128;
-    static constexpr int ROW_B = 2 * TILE_B;
-    static constexpr int ROW_OFF = 2 * W_B;
-    static constexpr int BIAS_OFF = ROW_OFF + 3 * ROW_B;          // two row slots + the fp32 exchange buffer
-    static size_t bytes(int d) { return (size_t)BIAS_OFF + (size_t)2 * (32 * RT + d) * 4; }
-};
-
-template <bool B> struct Bool3 { static constexpr bool value = B; };
-
-template <typename IO, int RT, int RG>
 __global__ __launch_bounds__(RG * 128) void pet_gate_dz_kernel(PetBwdArgs a) {
     using G = Geo4<IO>;
-    using L = DzLds<IO, RT, RG>;
+    using L = ChainLds<IO, RT, RG>;
     constexpr int NS = G::NS;
     constexpr int KT = 2 * RT;
     constexpr int PW = L::SEG_KB / RG;
@@ -74,9 +68,6 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_dz_kernel(PetBwdArgs a) {
     const uint8_t* res = reinterpret_cast<const uint8_t*>(a.res);
     const uint8_t* dy = reinterpret_cast<const uint8_t*>(a.dy);
 
-    auto slot_w = [&](int j) { return smem + (size_t)j * L::W_B + (isA ? 0 : L::SEG_KB * 1024); };
-    auto slot_t0 = [&](int j) { return smem + L::ROW_OFF + (size_t)j * L::ROW_B; };
-    auto slot_t1 = [&](int j) { return smem + L::ROW_OFF + (size_t)j * L::ROW_B + L::TILE_B; };
     constexpr int XH = G::LW / 2;
     uint8_t* xbuf = smem + L::ROW_OFF + (size_t)2 * L::ROW_B;
     auto xslot = [&](int writer_chain) { return xbuf + (size_t)writer_chain * L::TILE_B + (size_t)rg * (XH * 256); };
@@ -93,14 +84,14 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_dz_kernel(PetBwdArgs a) {
         if (st >= NST) return;
         const int ss = st >> 1, pack = (st & 1) ? 2 : 1;
         const uint8_t* src = pk + (int64_t)pack * pg.pack_bytes + (int64_t)ss * L::SEG_KB * 1024;
-        uint8_t* dst = slot_w(st & 1) + rg * 1024;
+        uint8_t* dst = chain_slot_w<L>(smem, isA, st & 1) + rg * 1024;
 #pragma unroll
         for (int j = 0; j < PW; ++j) glds16(src + (wv_off + j * RG * 1024), dst + j * RG * 1024);
     };
     auto issue_rows = [&](int su) {
         if (su >= S) return 0;
-        if (isA) glds_rows4(res, rl, su * 128, slot_t0(su & 1), rg);
-        else glds_rows4(dy, rl, su * 128, slot_t1(su & 1), rg);
+        if (isA) glds_rows4(res, rl, su * 128, chain_slot_t0<L>(smem, su & 1), rg);
+        else glds_rows4(dy, rl, su * 128, chain_slot_t1<L>(smem, su & 1), rg);
         return 4;
     };
 
@@ -138,15 +129,8 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_dz_kernel(PetBwdArgs a) {
         {
             issue_w(st + 1);
             const int nrows = issue_rows(su + 1);
-            const uint8_t* w = slot_w(st & 1);
-#pragma unroll
-            for (int v = 0; v < G::NV; ++v) {
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    const f32x4 tb = *reinterpret_cast<const f32x4*>(bu + su * G::FE + 16 * v + 4 * q);
-                    au[v][4 * q] = tb[0]; au[v][4 * q + 1] = tb[1]; au[v][4 * q + 2] = tb[2]; au[v][4 * q + 3] = tb[3];
-                }
-            }
+            const uint8_t* w = chain_slot_w<L>(smem, isA, st & 1);
+            bias_seed<G::NV>(bu + su * G::FE, au);
             if constexpr (!PIPE) {
                 Frag<NS> wf[G::NV * KT];
 #pragma unroll
@@ -198,9 +182,9 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_dz_kernel(PetBwdArgs a) {
         // ---- stage b: elementwise backward of the own half, then the contraction over this block's features
         {
             issue_w(st + 1);
-            const uint8_t* w = slot_w(st & 1);
-            uint8_t* t0 = slot_t0(su & 1);
-            uint8_t* t1 = slot_t1(su & 1);
+            const uint8_t* w = chain_slot_w<L>(smem, isA, st & 1);
+            uint8_t* t0 = chain_slot_t0<L>(smem, su & 1);
+            uint8_t* t1 = chain_slot_t1<L>(smem, su & 1);
             const uint8_t* xb = xslot(1 - chain);
             auto elementwise = [&](auto add_c) {
                 constexpr bool ADD = decltype(add_c)::value;
@@ -235,7 +219,7 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_dz_kernel(PetBwdArgs a) {
                     stage_lane_vals8<IO>(t1, trow, h, e, dq8);
                 }
             };
-            if (gate_add) elementwise(Bool3<true>{}); else elementwise(Bool3<false>{});
+            if (gate_add) elementwise(std::bool_constant<true>{}); else elementwise(std::bool_constant<false>{});
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();           // both halves of the dh / dq tiles of this row group are complete
             const uint8_t* mine = isA ? t0 : t1;
@@ -296,55 +280,6 @@ __global__ __launch_bounds__(RG * 128) void pet_gate_dz_kernel(PetBwdArgs a) {
 }
 
 // ================================================================================================== pass 2
-struct ColsArgs {
-    const void* dy; const void* x1; const void* x2;
-    const void* z_a; const void* z_g;       // the forward's saved z  [M, 32*RT]
-    const void* dp_a; const void* dp_g;     // pass 1's dpre         [M, 32*RT]
-    void* dx1; void* dx2;
-    const uint8_t* pk_a; const uint8_t* pk_g;
-    int64_t M;
-    int d, RT;
-    float s2, sd, gs;
-    int flags;
-    int GS, NG;                             // feature blocks per XCD group, groups per row chunk (S = GS * NG)
-    WgradArgs wg;                           // partial layout (job 0 dWd, 1 dWu, 2 dWgd, 3 dWgu), row_chunks, rows_per_chunk
-};
-
-template <typename IO, int NRG, int NBUF_>
-struct ColsLds {
-    using G = Geo4<IO>;
-    static constexpr int NBUF = NBUF_;                              // input tile buffers (NBUF - 1 iterations ahead)
-    static constexpr int TILE_B = 32 * 128;
-    static constexpr int XH_B = 32 * G::FE * 4;                     // fp32 exchange of h: LW values per lane
-    static constexpr int RG_B = (3 * NBUF + 2) * TILE_B + XH_B;     // x2, dy, x1 buffers; dh, dq tiles; exchange
-    static int w_bytes(int RT) { return 4 * 4 * RT * 1024; }        // [up A | up G | down_t A | down_t G] of one stage
-    static size_t bytes(int RT) {
-        const size_t main = (size_t)w_bytes(RT) + NRG * RG_B + 2 * G::FE * 4;
-        const size_t red = NRG > 1 ? (size_t)4 * (RT * G::NV * 16 + RT + G::NV) * 64 * 4 : 0;     // end-of-kernel reduction over the row groups
-        return main > red ? main : red;
-    }
-};
-
-template <int NS>
-__device__ __forceinline__ f32x16 transpose32(const Frag<NS>& lo16, const Frag<NS>& hi16, bf16x8 I0, bf16x8 I1) {
-    f32x16 t = zero16();
-#pragma unroll
-    for (int p = 0; p < NS; ++p) {
-        t = mfma32(lo16.p[p], I0, t);
-        t = mfma32(hi16.p[p], I1, t);
-    }
-    return t;
-}
-
-template <int NS>
-__device__ __forceinline__ Frag<NS> zero_frag() {
-    Frag<NS> f;
-#pragma unroll
-    for (int p = 0; p < NS; ++p)
-#pragma unroll
-        for (int j = 0; j < 8; ++j) f.p[p][j] = (__bf16)0.0f;
-    return f;
-}
 
 // NRG = row groups (32 rows) per workgroup: 2 for r <= 96 (8 waves, two per SIMD, 256 registers each); 1 for r = 192
 // (4 waves, one per SIMD: the 192 accumulator registers of a role need the whole register file of a SIMD lane)
@@ -404,11 +339,7 @@ __global__ __launch_bounds__(NRG * 256) void pet_gate_cols_kernel(ColsArgs a) {
     }
 
     bf16x8 I0, I1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        I0[j] = (m == 8 * h + j) ? (__bf16)1.0f : (__bf16)0.0f;
-        I1[j] = (m == 16 + 8 * h + j) ? (__bf16)1.0f : (__bf16)0.0f;
-    }
+    cols_identity(m, h, I0, I1);
     const uint8_t* Xsrc = reinterpret_cast<const uint8_t*>(role == 0 ? a.x2 : (role == 2 ? a.x1 : a.dy));   // role 1 loads no tile
     const IO* Psrc = reinterpret_cast<const IO*>(role == 0 ? a.dp_a : (role == 1 ? a.z_a : (role == 2 ? a.dp_g : a.z_g)));
     uint8_t* dxo = reinterpret_cast<uint8_t*>(role == 0 ? a.dx2 : a.dx1);
@@ -438,32 +369,10 @@ __global__ __launch_bounds__(NRG * 256) void pet_gate_cols_kernel(ColsArgs a) {
     auto issue_tile = [&](int it) {                                  // this wave's input tile of iteration it
         if (role == 1 || it >= n_it) return 0;
         const int64_t row0t = r_begin + (int64_t)it * IR + 32 * rg;
-        uint8_t* dst = tile_of(it % NBUF);
-        if (row0t + 32 <= a.M) {
-            const uint8_t* base = Xsrc + row0t * d * (int64_t)sizeof(IO) + su * 128;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) glds16_row(base + voff[i], dst + i * 1024);
-        } else {
-            const RowLanes rl = row_lanes<IO>(row0t, a.M, d, 0, lane);
-            glds_rows4(Xsrc, rl, su * 128, dst, 0);
-        }
+        cols_load_tile<IO>(Xsrc, row0t, a, d, su, lane, voff, tile_of(it % NBUF));
         return 4;
     };
-    // whole-line stores of a staged tile (the wave's 32 rows of feature block su)
-    auto store_tile = [&](uint8_t* base_out, int64_t row0t, const uint8_t* tile) {
-        if (row0t + 32 <= a.M) {
-            uint8_t* base = base_out + row0t * d * (int64_t)sizeof(IO) + su * 128;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(tile + ((size_t)(8 * i + (lane >> 3)) * 8 + (lane & 7)) * 16);
-                *reinterpret_cast<u32x4*>(base + voff[i]) = v;
-            }
-            return 4;
-        }
-        const RowLanes rl = row_lanes<IO>(row0t, a.M, d, 0, lane);
-        store_rows4(base_out, rl, su * 128, tile, 0, lane);
-        return rl.n_inst;
-    };
+    auto store_tile = [&](uint8_t* base_out, int64_t row0t, const uint8_t* tile) { return cols_store_tile<IO>(base_out, row0t, a, d, su, lane, voff, tile); };
     Frag<NS> pn[KT];                                                 // this role's P rows, natural fragments
     constexpr int NPL = KT * (int)(sizeof(IO) / 2);                  // global loads of one load_p
     auto load_p = [&](int it) {                                      // (rows past the end: clamped address, zeroed at use)
@@ -512,28 +421,7 @@ __global__ __launch_bounds__(NRG * 256) void pet_gate_cols_kernel(ColsArgs a) {
         }
     };
     // projection of this stage: out[v] = init + W(v, ks) . pn[ks]
-    // (fragment reads one k-step ahead of the MFMAs: 2 * NV fragments live instead of NV * KT -- this kernel holds 96
-    // accumulator registers per wave and two waves share a SIMD's register file)
-    auto project = [&](const uint8_t* w, f32x16* out) {
-        Frag<NS> cur[NV], nxt[NV];
-#pragma unroll
-        for (int v = 0; v < NV; ++v) cur[v] = wfrag<NS>(w, v * KT, lane);
-#pragma unroll
-        for (int ks = 0; ks < KT; ++ks) {
-            if (ks + 1 < KT) {
-#pragma unroll
-                for (int v = 0; v < NV; ++v) nxt[v] = wfrag<NS>(w, v * KT + ks + 1, lane);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int v = 0; v < NV; ++v) out[v] = mfma_ns<NS>(cur[v], pn[ks], out[v]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks + 1 < KT) {
-#pragma unroll
-                for (int v = 0; v < NV; ++v) cur[v] = nxt[v];
-            }
-        }
-    };
+    auto project = [&](const uint8_t* w, f32x16* out) { project_ahead<NS, NV, KT>(w, lane, pn, out); };
 
 #pragma unroll
     for (int k = 0; k < NBUF - 1; ++k) issue_tile(k);
@@ -797,11 +685,7 @@ __global__ __launch_bounds__(NRG * 128) void pet_gate_cols2_kernel(ColsArgs a) {
     }
 
     bf16x8 I0, I1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        I0[j] = (m == 8 * h + j) ? (__bf16)1.0f : (__bf16)0.0f;
-        I1[j] = (m == 16 + 8 * h + j) ? (__bf16)1.0f : (__bf16)0.0f;
-    }
+    cols_identity(m, h, I0, I1);
     // chain A: x tile = x2, P rows = dpre_a (job 0) and z_a (job 1); chain G: x tile = x1 (+ the dy tile), dpre_g (job 2), z_g (job 3)
     const uint8_t* Xsrc = reinterpret_cast<const uint8_t*>(isA ? a.x2 : a.x1);
     const uint8_t* Ysrc = reinterpret_cast<const uint8_t*>(a.dy);
@@ -828,16 +712,7 @@ __global__ __launch_bounds__(NRG * 128) void pet_gate_cols2_kernel(ColsArgs a) {
         const int tr = 8 * i + (lane >> 3);
         voff[i] = (uint32_t)tr * (uint32_t)(d * (int)sizeof(IO)) + (uint32_t)(((lane & 7) ^ swz(tr)) * 16);
     }
-    auto load_tile = [&](const uint8_t* src, int64_t row0t, uint8_t* dst) {
-        if (row0t + 32 <= a.M) {
-            const uint8_t* base = src + row0t * d * (int64_t)sizeof(IO) + su * 128;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) glds16_row(base + voff[i], dst + i * 1024);
-        } else {
-            const RowLanes rl = row_lanes<IO>(row0t, a.M, d, 0, lane);
-            glds_rows4(src, rl, su * 128, dst, 0);
-        }
-    };
+    auto load_tile = [&](const uint8_t* src, int64_t row0t, uint8_t* dst) { cols_load_tile<IO>(src, row0t, a, d, su, lane, voff, dst); };
     auto issue_tiles = [&](int it) {                                 // A: x2;  G: x1 and dy
         if (it >= n_it) return 0;
         const int64_t row0t = r_begin + (int64_t)it * IR + 32 * rg;
@@ -846,20 +721,7 @@ __global__ __launch_bounds__(NRG * 128) void pet_gate_cols2_kernel(ColsArgs a) {
         load_tile(Ysrc, row0t, Tdy(it % NBUF));
         return 8;
     };
-    auto store_tile = [&](uint8_t* base_out, int64_t row0t, const uint8_t* tile) {
-        if (row0t + 32 <= a.M) {
-            uint8_t* base = base_out + row0t * d * (int64_t)sizeof(IO) + su * 128;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const u32x4 v = *reinterpret_cast<const u32x4*>(tile + ((size_t)(8 * i + (lane >> 3)) * 8 + (lane & 7)) * 16);
-                *reinterpret_cast<u32x4*>(base + voff[i]) = v;
-            }
-            return 4;
-        }
-        const RowLanes rl = row_lanes<IO>(row0t, a.M, d, 0, lane);
-        store_rows4(base_out, rl, su * 128, tile, 0, lane);
-        return rl.n_inst;
-    };
+    auto store_tile = [&](uint8_t* base_out, int64_t row0t, const uint8_t* tile) { return cols_store_tile<IO>(base_out, row0t, a, d, su, lane, voff, tile); };
     // P rows of the tile in registers, re-loaded IN PLACE for the next tile right after their last use (a second register set
     // for the next iteration does not fit beside the 192 accumulator registers)
     Frag<NS> pdp[KT], pz[KT];
@@ -902,26 +764,7 @@ __global__ __launch_bounds__(NRG * 128) void pet_gate_cols2_kernel(ColsArgs a) {
             __builtin_amdgcn_sched_barrier(0);
         }
     };
-    auto project = [&](const uint8_t* w, const Frag<NS>* pp, f32x16* out) {
-        Frag<NS> cur[NV], nxt[NV];
-#pragma unroll
-        for (int v = 0; v < NV; ++v) cur[v] = wfrag<NS>(w, v * KT, lane);
-#pragma unroll
-        for (int ks = 0; ks < KT; ++ks) {
-            if (ks + 1 < KT) {
-#pragma unroll
-                for (int v = 0; v < NV; ++v) nxt[v] = wfrag<NS>(w, v * KT + ks + 1, lane);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int v = 0; v < NV; ++v) out[v] = mfma_ns<NS>(cur[v], pp[ks], out[v]);
-            __builtin_amdgcn_sched_barrier(0);
-            if (ks + 1 < KT) {
-#pragma unroll
-                for (int v = 0; v < NV; ++v) cur[v] = nxt[v];
-            }
-        }
-    };
+    auto project = [&](const uint8_t* w, const Frag<NS>* pp, f32x16* out) { project_ahead<NS, NV, KT>(w, lane, pp, out); };
 
 #pragma unroll
     for (int k = 0; k < NBUF - 1; ++k) issue_tiles(k);
@@ -985,7 +828,7 @@ __global__ __launch_bounds__(NRG * 128) void pet_gate_cols2_kernel(ColsArgs a) {
         __builtin_amdgcn_s_barrier();                                // B1: h is in the exchange buffer
 
         // ================= phase 2: G: dh, dq of the tile;  A: dWd = dpre_a^T x2 (independent of dh)
-        if constexpr (CA) accumulate(Tx2(bf), valid, pdp, accD, cspD, csxD, std::true_type{}); else {
+        if constexpr (CA) accumulate(Tx2(bf), valid, pdp, accD, cspD, csxD, std::bool_constant<true>{}); else {
             const uint8_t* ty = Tdy(bf);
 #pragma unroll
             for (int e = 0; e < G::E4; ++e) {
@@ -1018,7 +861,7 @@ __global__ __launch_bounds__(NRG * 128) void pet_gate_cols2_kernel(ColsArgs a) {
 
         // ================= phase 3: A: dx2, dWu;  G: dWgd, dx1, dWgu
         if constexpr (CA) {
-            accumulate(Tdh, valid, pz, accU, cspU, csxU, std::false_type{});
+            accumulate(Tdh, valid, pz, accU, cspU, csxU, std::bool_constant<false>{});
             load_p(it + 1, Pz, pz);
             f32x16 ax[NV];
 #pragma unroll
@@ -1036,9 +879,9 @@ __global__ __launch_bounds__(NRG * 128) void pet_gate_cols2_kernel(ColsArgs a) {
             }
             n_store = store_tile(dxo, row0, tile);
         } else {
-            accumulate(Tdq, valid, pz, accU, cspU, csxU, std::false_type{});
+            accumulate(Tdq, valid, pz, accU, cspU, csxU, std::bool_constant<false>{});
             load_p(it + 1, Pz, pz);
-            accumulate(Tx1(bf), valid, pdp, accD, cspD, csxD, std::true_type{});
+            accumulate(Tx1(bf), valid, pdp, accD, cspD, csxD, std::bool_constant<true>{});
             f32x16 ax[NV];
 #pragma unroll
             for (int v = 0; v < NV; ++v) ax[v] = zero16();
@@ -1063,7 +906,7 @@ __global__ __launch_bounds__(NRG * 128) void pet_gate_cols2_kernel(ColsArgs a) {
     }
 
     };
-    if (isA) run(std::true_type{}); else run(std::false_type{});
+    if (isA) run(std::bool_constant<true>{}); else run(std::bool_constant<false>{});
 
     // ---- reduce the row groups (fixed order) and emit this chunk's partials: jobs 2*chain (down) and 2*chain + 1 (up)
     constexpr int NVAL = RT * NV * 16 + RT + NV;
@@ -1164,62 +1007,35 @@ bool pet_gate_bwd3_applies(const PetBwdArgs& a) {
     return a.RT == 6 || a.M <= 4096;
 }
 
-template <typename IO, int RT, int RG>
-static hipError_t launch_dz_one(const PetBwdArgs& a, hipStream_t stream) {
-    using L = DzLds<IO, RT, RG>;
-    const size_t lds = L::bytes(a.d);
-    auto kern = pet_gate_dz_kernel<IO, RT, RG>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    const int rows = RG * 32;
-    hipLaunchKernelGGL(kern, dim3((unsigned)((a.M + rows - 1) / rows)), dim3(RG * 128), lds, stream, a);
-    return hipGetLastError();
-}
-template <typename IO, int RT>
-static hipError_t launch_dz_rt(const PetBwdArgs& a, hipStream_t stream) {
-    if constexpr (RT == 6) {
-        return launch_dz_one<IO, RT, 2>(a, stream);      // r = 192: the 2 x 48 KiB weight ring leaves room for 64 rows
-    } else {
-        switch (pick_row_groups(a.M, 4, 2)) {
-            case 4: return launch_dz_one<IO, RT, 4>(a, stream);
-            case 3: if constexpr ((4 * RT) % 3 == 0) return launch_dz_one<IO, RT, 3>(a, stream);   // (else: falls through)
-            default: return launch_dz_one<IO, RT, 2>(a, stream);
-        }
-    }
-}
+// pass 1: workgroups of RG * 32 rows, 2 * RG waves, ChainLds::bytes(d) of LDS (launch_chain_rows, as pet_gate_bwd2.hip)
 hipError_t launch_pet_gate_dz(const PetBwdArgs& a, int io_fp32, hipStream_t stream) {
-    if (a.RT == 1) return io_fp32 ? launch_dz_rt<float, 1>(a, stream) : launch_dz_rt<__bf16, 1>(a, stream);
-    if (a.RT == 3) return io_fp32 ? launch_dz_rt<float, 3>(a, stream) : launch_dz_rt<__bf16, 3>(a, stream);
-    if (a.RT == 6) return io_fp32 ? launch_dz_rt<float, 6>(a, stream) : launch_dz_rt<__bf16, 6>(a, stream);
-    return hipErrorInvalidValue;
+    return with_io_rt<true>(io_fp32, a.RT, [&](auto io, auto rt) {
+        using IO = decltype(io);
+        constexpr int RT = decltype(rt)::value;
+        auto launch = [&](auto rg) {
+            constexpr int RG = decltype(rg)::value;
+            return launch_chain_rows<ChainLds<IO, RT, RG>, RG, RG * 128>(pet_gate_dz_kernel<IO, RT, RG>, a, stream);
+        };
+        if constexpr (RT == 6) return launch(std::integral_constant<int, 2>{});   // r = 192: the 2 x 48 KiB weight ring leaves room for 64 rows
+        else return with_row_groups<RT>(a.M, launch);
+    });
 }
 
-template <typename IO, int RT, int NRG, int NBUF>
-static hipError_t launch_cols_cfg(const ColsArgs& c, hipStream_t stream) {
-    const size_t lds = ColsLds<IO, NRG, NBUF>::bytes(RT);
-    auto kern = pet_gate_cols_kernel<IO, RT, NRG, NBUF>;
+// pass 2: one workgroup per (feature block, row chunk) in the XCD-aware numbering, NRG row groups of WPG waves each.  kern =
+// pet_gate_cols_kernel (WPG = 4: one wave per role) or pet_gate_cols2_kernel (WPG = 2: one wave per chain).
+// Workgroup shape, measured at M = 28,000, bf16, r = 96 (profiles/r02_kbench_two_pass_ab.txt): 8 waves (2 row groups x 4 roles, 256
+// registers each) spill 70-140 registers and take 290-410 us -- every scratch reload waits, in order, behind the tile prefetches;
+// 4 waves (one per SIMD, no spill, P rows prefetched) take 189 us whether the tiles run one or two iterations ahead, i.e. the pass
+// is bound by the three-phase dependency chain of an iteration (~7k cycles per 32 rows), not by memory.  Kept: the 4-wave shape
+// (r > 32) and the 8-wave shape where it does not spill (r <= 32).
+template <typename IO, int NRG, int NBUF, int WPG>
+static hipError_t launch_cols_cfg(void (*kern)(ColsArgs), const ColsArgs& c, hipStream_t stream) {
+    const size_t lds = ColsLds<IO, NRG, NBUF>::bytes(c.RT);
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     const int units = c.NG * c.wg.row_chunks;
     const unsigned grid = 8u * (unsigned)c.GS * (unsigned)((units + 7) / 8);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NRG * 256), lds, stream, c);
-    return hipGetLastError();
-}
-
-// workgroup shape of pass 2.  Measured at M = 28,000, bf16, r = 96 (profiles/r02_kbench_two_pass_ab.txt): 8 waves (2 row
-// groups x 4 roles, 256 registers each) spill 70-140 registers and take 290-410 us -- every scratch reload waits, in order,
-// behind the tile prefetches; 4 waves (one per SIMD, no spill, P rows prefetched) take 189 us whether the tiles run one or
-// two iterations ahead, i.e. the pass is bound by the three-phase dependency chain of an iteration (~7k cycles per 32 rows),
-// not by memory.  Kept: the 4-wave shape (r > 32) and the 8-wave shape where it does not spill (r <= 32).
-template <typename IO, int RT, int NRG, int NBUF>
-static hipError_t launch_cols2_cfg(const ColsArgs& c, hipStream_t stream) {
-    const size_t lds = ColsLds<IO, NRG, NBUF>::bytes(RT);
-    auto kern = pet_gate_cols2_kernel<IO, RT, NRG, NBUF>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    const int units = c.NG * c.wg.row_chunks;
-    const unsigned grid = 8u * (unsigned)c.GS * (unsigned)((units + 7) / 8);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NRG * 128), lds, stream, c);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(NRG * WPG * 64), lds, stream, c);
     return hipGetLastError();
 }
 
@@ -1228,11 +1044,11 @@ static hipError_t launch_cols_one(const ColsArgs& c, hipStream_t stream) {
     // three tiles: two waves per row group, two row groups per workgroup, instead of four roles per row group (4 waves, one tile
     // at a time): 198.8 -> 137.2 us at M = 28 k, 58.9 -> 55.0 at 3.5 k; profiles/r02_kbench_pass2_forms.txt
     if constexpr (RT == 3) {
-        return launch_cols2_cfg<IO, RT, 2, 2>(c, stream);
+        return launch_cols_cfg<IO, 2, 2, 2>(pet_gate_cols2_kernel<IO, RT, 2, 2>, c, stream);
     } else if constexpr (RT == 6) {
-        return launch_cols_cfg<IO, RT, 1, 2>(c, stream);     // 96 KiB of weight fragments: room for two tile buffers
+        return launch_cols_cfg<IO, 1, 2, 4>(pet_gate_cols_kernel<IO, RT, 1, 2>, c, stream);     // 96 KiB of weight fragments: room for two tile buffers
     } else {
-        return launch_cols_cfg<IO, RT, 2, 2>(c, stream);
+        return launch_cols_cfg<IO, 2, 2, 4>(pet_gate_cols_kernel<IO, RT, 2, 2>, c, stream);
     }
 }
 
@@ -1246,11 +1062,7 @@ hipError_t launch_pet_gate_cols(const PetBwdArgs& a, const WgradArgs& g, int GS,
     c.pk_a = a.pk_a; c.pk_g = a.pk_g;
     c.M = a.M; c.d = a.d; c.RT = a.RT; c.s2 = a.s2; c.sd = a.sd; c.gs = a.gs; c.flags = a.flags;
     c.GS = GS; c.NG = NG; c.wg = g;
-    hipError_t e;
-    if (a.RT == 1) e = io_fp32 ? launch_cols_one<float, 1>(c, stream) : launch_cols_one<__bf16, 1>(c, stream);
-    else if (a.RT == 3) e = io_fp32 ? launch_cols_one<float, 3>(c, stream) : launch_cols_one<__bf16, 3>(c, stream);
-    else if (a.RT == 6) e = io_fp32 ? launch_cols_one<float, 6>(c, stream) : launch_cols_one<__bf16, 6>(c, stream);
-    else return hipErrorInvalidValue;
+    const hipError_t e = with_io_rt<true>(io_fp32, a.RT, [&](auto io, auto rt) { return launch_cols_one<decltype(io), decltype(rt)::value>(c, stream); });
     if (e != hipSuccess) return e;
     return launch_wgrad_finalize(g, stream);
 }

@@ -27,19 +27,7 @@
 #include <cstdlib>
 #include "common.h"
 #include "kernels.h"
-#include "pet32.h"
-
-template <typename IO, int RT, int RG>
-struct GateLds {
-    static constexpr int NS = Geo4<IO>::NS;
-    static constexpr int SEG_KB = 4 * RT;
-    static constexpr int SEG_FR = SEG_KB / NS;
-    static constexpr int W_B = SEG_KB * 1024 * 2;
-    static constexpr int TILE_B = RG * 32 * 128;
-    static constexpr int ROW_OFF = 2 * W_B;
-    static constexpr int BIAS_OFF = ROW_OFF + 6 * TILE_B;      // row area: 3 down-phase slots of [x2 tile | x1 tile]
-    static size_t bytes(int d) { return (size_t)BIAS_OFF + (size_t)2 * (32 * RT + d) * 4; }
-};
+#include "gate_chain.h"
 
 // LR = low-rank visual projector form (LowRankVisualEmbedding, src/modeling_bart.py:278-295): both chains read the same
 // [M, d_in] feature rows (one LDS tile per stage instead of two), the down phase runs d_in / FE stages on the separate
@@ -48,7 +36,7 @@ template <typename IO, int RT, bool GATE_ADD, int RG, bool LD, bool LR = false>
 __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(PetFwdArgs a) {
     static_assert(!LR || LD, "the low-rank projector form exists with loader waves only");
     using G = Geo4<IO>;
-    using L = GateLds<IO, RT, RG>;
+    using L = ChainLds<IO, RT, RG>;
     constexpr int NS = G::NS;
     constexpr int KT = 2 * RT;
     constexpr int NW = 2 * RG;                   // waves
@@ -194,7 +182,7 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
     for (; t < S; ++t) {
         issue_w(t + 1);
         const int nrows = issue_rows(t);
-        const uint8_t* w = slot_w(t & 1) + (isA ? 0 : L::SEG_KB * 1024);
+        const uint8_t* w = chain_slot_w<L>(smem, isA, t & 1);
         const uint8_t* tile = slot_d(t % 3);
         // all LDS fragment reads of the stage first, then the MFMAs behind counted lgkmcnt waits: with two waves per
         // SIMD a read -> wait -> MFMA chain per fragment leaves the matrix pipe idle for the LDS latency every time
@@ -273,7 +261,7 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
         const int su = isA ? t - S - 1 : t - S;
         int n_after = 0;                                // vector-memory operations allowed to stay in flight
         if (su >= 0 && su < SU) {
-            const uint8_t* w = slot_w(t & 1) + (isA ? 0 : L::SEG_KB * 1024);
+            const uint8_t* w = chain_slot_w<L>(smem, isA, t & 1);
             f32x16 au[G::NV];
 #pragma unroll
             for (int v = 0; v < G::NV; ++v) {
@@ -362,23 +350,14 @@ __global__ __launch_bounds__((LD ? 3 : 2) * RG * 64) void pet_gate_fwd_kernel(Pe
 
 template <typename IO, int RT, bool GATE_ADD, int RG, bool LD, bool LR = false>
 static hipError_t launch_one(const PetFwdArgs& a, hipStream_t stream) {
-    using L = GateLds<IO, RT, RG>;
-    const size_t lds = L::bytes(a.d);
-    auto kern = pet_gate_fwd_kernel<IO, RT, GATE_ADD, RG, LD, LR>;
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern),
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    const int rows = RG * 32;
-    const int blocks = (int)((a.M + rows - 1) / rows);
-    hipLaunchKernelGGL(kern, dim3(blocks), dim3((LD ? 3 : 2) * RG * 64), lds, stream, a);
-    return hipGetLastError();
+    return launch_chain_rows<ChainLds<IO, RT, RG>, RG, (LD ? 3 : 2) * RG * 64>(pet_gate_fwd_kernel<IO, RT, GATE_ADD, RG, LD, LR>, a, stream);
 }
 
 template <typename IO, int RT>
 static hipError_t launch_rt(const PetFwdArgs& a, hipStream_t stream) {
     const bool add = a.flags & PET_GATE_ADD;
     // up to 4 row groups (128 rows) with loader waves unless the rings would not fit the 160 KiB LDS
-    if constexpr (GateLds<IO, RT, 4>::BIAS_OFF + 8 * 1024 <= 160 * 1024) {
+    if constexpr (ChainLds<IO, RT, 4>::BIAS_OFF + 8 * 1024 <= 160 * 1024) {
         // forward: 128-row workgroups unless 64-row ones still fit one round of 256 (measured at M = 15 k / 32 k / 47 k:
         // 96-row workgroups -- 9 waves, uneven over the 4 SIMDs -- are the slowest form at every size, and two rounds of
         // 128 rows beat three of 64); the backward rows kernel follows pick_row_groups' cost model
@@ -412,13 +391,11 @@ hipError_t launch_pet_gate_fwd(const PetFwdArgs& a, int io_fp32, hipStream_t str
 // low-rank visual projector form (PetFwdArgs::d_in, pk_a_dn, pk_g_dn, go): r, r_g <= 96, multiplicative gate
 template <typename IO, int RT>
 static hipError_t launch_lr(const PetFwdArgs& a, hipStream_t stream) {
-    static_assert(GateLds<IO, RT, 4>::BIAS_OFF + 8 * 1024 <= 160 * 1024, "loader-wave form must fit");
+    static_assert(ChainLds<IO, RT, 4>::BIAS_OFF + 8 * 1024 <= 160 * 1024, "loader-wave form must fit");
     return a.M <= 256 * 64 ? launch_one<IO, RT, false, 2, true, true>(a, stream)
                            : launch_one<IO, RT, false, 4, true, true>(a, stream);
 }
 hipError_t launch_pet_lowrank_fwd(const PetFwdArgs& a, int io_fp32, hipStream_t stream) {
     if (a.d_in <= 0 || !a.pk_a_dn || !a.pk_g_dn || (a.flags & PET_GATE_ADD)) return hipErrorInvalidValue;
-    if (a.RT == 1) return io_fp32 ? launch_lr<float, 1>(a, stream) : launch_lr<__bf16, 1>(a, stream);
-    if (a.RT == 3) return io_fp32 ? launch_lr<float, 3>(a, stream) : launch_lr<__bf16, 3>(a, stream);
-    return hipErrorInvalidValue;
+    return with_io_rt<false>(io_fp32, a.RT, [&](auto io, auto rt) { return launch_lr<decltype(io), decltype(rt)::value>(a, stream); });
 }
