@@ -58,9 +58,10 @@ def make_k1(seed, M, d, r, rg, nh, wscale=None):
 
 
 def run_k1(dtype, M=224, d=768, r=96, rg=96, nh=4, gate_mode=1, delta_scale=1.0, x2_scale=1.0, gate_scale=1.0,
-           seed=0, tensors=None, col_errs=None, el_errs=None):
+           seed=0, tensors=None, col_errs=None, el_errs=None, dx1_in=False):
     """returns dict name -> relative error (max-abs / max-abs-ref) for y, dx1, dx2 and the 8 grads; ``col_errs`` (a dict)
-    additionally receives the per-column relative errors of the four bias gradients"""
+    additionally receives the per-column relative errors of the four bias gradients.  ``dx1_in``: a seeded gradient is parked in a
+    ResidualLink for the backward (the sublayer tail's hand-over) and added to the reference's dx1"""
     import vlpet_amd.functional as F
     t = tensors if tensors is not None else make_k1(seed, M, d, r, rg, nh)
     dev = "cuda"
@@ -82,8 +83,15 @@ def run_k1(dtype, M=224, d=768, r=96, rg=96, nh=4, gate_mode=1, delta_scale=1.0,
     pk_a = F.pack_pair(dws, dbs, P["wu"], P["bu"], io, tiles)
     pk_g = F.pack_pair([P["wgd"]], [P["bgd"]], P["wgu"], P["bgu"], io, tiles) if has_gate else None
     gp = (P["wgd"], P["bgd"], P["wgu"], P["bgu"]) if has_gate else None
-    y = F.adapter_gate(x1, x2, dws, dbs, P["wu"], P["bu"], gp, pk_a, pk_g, gate_mode, delta_scale, x2_scale, gate_scale)
+    link = F.ResidualLink() if dx1_in else None
+    y = F.adapter_gate(x1, x2, dws, dbs, P["wu"], P["bu"], gp, pk_a, pk_g, gate_mode, delta_scale, x2_scale, gate_scale, link=link)
+    if dx1_in:
+        assert link.armed, "this call does not take dx1_in"
+        parked = _rand(torch.Generator().manual_seed(seed + 1000), M, d).to(dtype)
+        link.park(parked.to(dev))
+        g_ref["x1"] = g_ref["x1"] + parked.float()
     y.backward(act["dy"].to(dev))
+    assert link is None or not link.holds
     torch.cuda.synchronize()
     errs = dict(y=rel_err(y, y_ref), dx2=rel_err(x2.grad, g_ref["x2"]))
     if has_gate:

@@ -1,4 +1,5 @@
 // C ABI of libvlpet_hip.so (declared in include/vlpet_hip.h): argument checking + launch plumbing.
+#include <algorithm>
 #include <atomic>
 #include "../../include/vlpet_hip.h"
 #include "common.h"
@@ -344,17 +345,20 @@ struct BwdWs {
     int row_chunks;
     int64_t rows_per_chunk;
 };
+// The feature-split pass 1 (pet_dz2.hip, pet_dz6.hip: small M) parks its fp32 partial dz, [nfb][M][2][32 * tiles], in the dh / dq area,
+// which the two-pass form does not use.  The split is on (the return value: PetBwdArgs::fsplit) where there is more than one block and
+// the partials fit the `room` the kernel's own rule allows them; silently off otherwise.
+static size_t dz_part_bytes(int nfb, int64_t M, int tiles) { return (size_t)nfb * (size_t)M * 2 * 32 * tiles * 4; }
+static int dz_fsplit(int nfb, int64_t M, int tiles, size_t room) { return nfb > 1 && dz_part_bytes(nfb, M, tiles) <= room ? nfb : 0; }
+
 static BwdWs bwd_ws(int64_t M, int d, int tiles, bool gate, int io_dtype) {
     BwdWs w{};
     const size_t esz = io_dtype == VLPET_F32 ? 4 : 2;
     const size_t side = align256((size_t)M * 32 * tiles * esz);
     size_t wide = align256((size_t)M * d * esz);
-    // the feature-split pass 1 parks its fp32 partial dz in the dh / dq area (unused by the two-pass form): four blocks at six tiles
-    // need twice the room of the two wide tensors
-    if (gate && tiles == 6 && io_dtype != VLPET_F32 && k1_dz6_feature_blocks(M, d) > 1) {
-        const size_t need = align256((size_t)k1_dz6_feature_blocks(M, d) * (size_t)M * 32 * tiles * 4);
-        if (need > wide) wide = need;
-    }
+    // six tiles: the feature blocks of pet_dz6.hip may need more than the two wide tensors have -- half of the partials in each
+    if (gate && tiles == 6 && io_dtype != VLPET_F32 && k1_dz6_feature_blocks(M, d) > 1)
+        wide = std::max(wide, align256(dz_part_bytes(k1_dz6_feature_blocks(M, d), M, tiles) / 2));
     size_t o = 0;
     w.z_a = o; o += side;
     w.dp_a = o; o += side;
@@ -395,6 +399,112 @@ extern "C" size_t vlpet_bwd_workspace_bytes(int64_t M, int d, int tiles, int has
     return bwd_ws(M, d, tiles, has_gate != 0, io_dtype).total;
 }
 
+// ------------------------------------------------------------------ backward: what a call launches
+// One row of the table in DESIGN.md section 4 (bwd_plan is its source).  `phases` still decides which of the launches a call runs.
+// pass 1 / the row kernel:
+//   ROWS_PET_BWD    pet_bwd.hip: the one-kernel row pass (every call the forms below do not take)
+//   ROWS_GATE_BWD2  pet_gate_bwd2.hip: chain-split row kernel (gated, saved activations, r <= 96); adds dx1_in in its epilogue
+//   ROWS_GATE_DZ    pet_gate_bwd3.hip pass 1: dpre only, chain-split
+//   ROWS_K1_DZ2     pet_dz2.hip: the same pass, feature-split (bf16, r <= 96); zeroes pass 2's reduce state itself
+//   ROWS_K1_DZ6     pet_dz6.hip: the same pass at six tiles
+//   ROWS_NG         pet_cols_ng.hip pass 1 (no gate, bf16, saved activations, whole call)
+enum BwdRows { ROWS_PET_BWD, ROWS_GATE_BWD2, ROWS_GATE_DZ, ROWS_K1_DZ2, ROWS_K1_DZ6, ROWS_NG };
+// pass 2 / the weight gradients:
+//   WG_WGRAD        wgrad.hip from the row kernel's side products (vlpet_adapter_gate_bwd_form: 0)
+//   WG_GATE_COLS    pet_gate_bwd3.hip pass 2 (form 1)
+//   WG_K1_COLS      pet_cols.hip + finalize launch (form 2)
+//   WG_K1_COLS_RED  pet_cols.hip, row chunks summed inside the launch (cols_reduce.h; form 2, no finalize launch)
+//   WG_K1_COLS6Y    pet_cols6y.hip + finalize launch (form 2)
+//   WG_NG           pet_cols_ng.hip pass 2 + finalize launch
+enum BwdWgrad { WG_WGRAD, WG_GATE_COLS, WG_K1_COLS, WG_K1_COLS_RED, WG_K1_COLS6Y, WG_NG };
+struct BwdPlan {
+    BwdRows rows;
+    BwdWgrad wgrad;
+    int fsplit;             // feature blocks of pass 1 (PetBwdArgs::fsplit; 0: unsplit)
+    bool finalize;          // launch_wgrad_finalize follows pass 2 (`phases` bits 3 / 4 split it off)
+    int add_dx1;            // 0, or the `phases` bit of the pass after which dx1_in takes a launch_add_inplace of its own (the other forms add it in a kernel)
+    bool memset_red;        // the reduce state of WG_K1_COLS_RED needs a memset node: this pass 1 does not zero it
+    int row_chunks; int64_t rows_per_chunk; int gs3, ng3;      // the row chunks of pass 2 (gs3, ng3: gate_bwd3_plan's groups)
+};
+
+// The only place that asks the *_applies predicates, the tuning switches and the row-chunk plans of the forms.
+// Two-pass forms (pass 1: dpre only; pass 2: input gradients + weight gradients from recomputed dh / dq) unless the caller needs the
+// input gradients right after phase 1 (`phases` bit 2: weight gradients on a side stream).
+static BwdPlan bwd_plan(const PetBwdArgs& b, int phases, int io_dtype, const BwdWs& w) {
+    const int f32 = io_dtype == VLPET_F32;
+    const bool whole = !(phases & 4);
+    BwdPlan p{};
+    p.row_chunks = w.row_chunks; p.rows_per_chunk = w.rows_per_chunk;
+    // without a gate (K2, adapter-only K1, K3 without dropout), bf16, saved activations, whole call: pass 1 (dpre) + the
+    // column-parallel pass of pet_cols_ng.hip (dx and both weight gradients from one read of dy and x)
+    // (the in-launch reduce-scatter of cols_reduce.h was built for this pass 2 as well and measured no gain: K2 backward 67.9 / 66.7 us
+    //  with it against 66.4 / 67.1 us with the finalize launch in the configs[1] step, profiles/r06_in_launch_reduce_ab.txt -- not kept)
+    if (!(b.flags & PET_GATE) && phases == 3 && ng_two_pass_applies(b, f32)) {
+        p.rows = ROWS_NG; p.wgrad = WG_NG; p.finalize = true;
+        ng_cols_plan(b.M, b.d, &p.row_chunks, &p.rows_per_chunk);
+        return p;
+    }
+    // bf16: pass 1 + the column-parallel pass of pet_cols.hip / pet_cols6y.hip (input gradients + the four weight gradients from one
+    // read of dy, x1, x2).  Round 6: at r <= 96 pass 2 sums its row-chunk partials inside the launch -- no finalize launch; `phases`
+    // bit 5 keeps the round-3 two-launch form where other kernels may run beside the call (k1_in_launch_reduce; bit-identical results)
+    if (whole && k1_cols6_applies(b, f32)) {
+        p.wgrad = WG_K1_COLS6Y;
+        k1_cols6_plan(b.M, b.d, &p.row_chunks, &p.rows_per_chunk);
+    } else if (whole && k1_cols_applies(b, f32)) {
+        p.wgrad = !(phases & 32) && k1_in_launch_reduce(b.M) ? WG_K1_COLS_RED : WG_K1_COLS;
+        k1_cols_plan(b.M, b.d, &p.row_chunks, &p.rows_per_chunk);
+    } else if (whole && pet_gate_bwd3_applies(b)) {
+        p.wgrad = WG_GATE_COLS;
+        gate_bwd3_plan(b.M, b.d, f32, &p.row_chunks, &p.rows_per_chunk, &p.gs3, &p.ng3);
+    } else {
+        p.wgrad = WG_WGRAD;
+        p.rows = pet_gate_bwd2_applies(b) ? ROWS_GATE_BWD2 : ROWS_PET_BWD;
+        p.add_dx1 = p.rows == ROWS_PET_BWD ? 1 : 0;     // (the chain-split row kernel adds dx1_in in its epilogue)
+        return p;
+    }
+    p.finalize = p.wgrad == WG_K1_COLS || p.wgrad == WG_K1_COLS6Y;
+    p.add_dx1 = p.wgrad == WG_GATE_COLS ? 2 : 0;        // (dx1 is an output of pass 2 there; pet_cols*.hip take dx1_in themselves)
+    if (k1_dz2_applies(b, f32)) {
+        p.rows = ROWS_K1_DZ2;
+        p.fsplit = dz_fsplit(k1_dz2_feature_blocks(b.M, b.d), b.M, b.RT, 2 * align256((size_t)b.M * b.d * (f32 ? 4 : 2)));
+    } else if (vlpet_tuning().dz6 != 0 && k1_dz6_applies(b, f32)) {
+        p.rows = ROWS_K1_DZ6;
+        p.fsplit = dz_fsplit(k1_dz6_feature_blocks(b.M, b.d), b.M, b.RT, w.dq > w.dh ? 2 * (w.dq - w.dh) : 0);
+    } else {
+        p.rows = ROWS_GATE_DZ;
+    }
+    p.memset_red = p.wgrad == WG_K1_COLS_RED && p.rows != ROWS_K1_DZ2;
+    return p;
+}
+
+// pass 2 of pet_cols.hip / pet_cols6y.hip; b.red_ctrl set: the row chunks are summed inside the launch
+static ColzArgs colz_args(const PetBwdArgs& b, const WgradArgs& g, const void* dx1_in) {
+    ColzArgs c{};
+    c.dy = b.dy; c.x1 = b.xg; c.x2 = b.res; c.dxin = dx1_in; c.y = b.y;
+    c.z_a = b.z_a; c.z_g = b.z_g; c.dp_a = b.dp_a; c.dp_g = b.dp_g;
+    c.dx1 = b.dxg; c.dx2 = b.dxa;
+    c.pk_a = b.pk_a; c.pk_g = b.pk_g;
+    c.M = b.M; c.d = b.d; c.s2 = b.s2; c.sd = b.sd; c.gs = b.gs; c.flags = b.flags;
+    c.row_chunks = g.row_chunks; c.rows_per_chunk = g.rows_per_chunk;
+    const WgradLayout L = wgrad_layout(g);
+    for (int j = 0; j < 4; ++j) c.part[j] = g.partial + L.off[j];
+    if (b.red_ctrl) {
+        // the same workspace bytes, cut differently: [RC][NCB] slabs (= the four [RC][PR][d] blocks), then the column-sum partials
+        const int64_t PRl = 32 * b.RT;
+        c.red.slab = g.partial;
+        c.red.bias_x = g.partial + (int64_t)4 * g.row_chunks * PRl * b.d;
+        c.red.bias_p = c.red.bias_x + (int64_t)2 * g.row_chunks * b.d;
+        c.red.ctrl = b.red_ctrl;
+        c.red.spin_limit = COLS_RED_SPIN_DEFAULT;
+        for (int j = 0; j < 4; ++j) {
+            const WgradJob& J = g.job[j];
+            c.red.job[j] = ColsRedJob{J.out, J.ldo, J.transposed, J.out_rows, J.scale, J.colsum_x, J.colsum_p};
+        }
+    }
+    return c;
+}
+
+// Four steps: argument checks, PetBwdArgs, bwd_plan, the launches of the plan that `phases` asks for.
 static int run_bwd(const void* dy, const void* xa, const void* res, const void* xg,
                    const void* pk_a, const void* pk_g, const DropSpec& drop,
                    void* dxa, void* dxg,
@@ -418,12 +528,16 @@ static int run_bwd(const void* dy, const void* xa, const void* res, const void* 
         return VLPET_E_ALIGN;
     const BwdWs w = bwd_ws(M, d, tiles, gate, io_dtype);
     if (workspace_bytes < w.total) return VLPET_E_WORKSPACE;
+    if (dx1_in && (!gate || !aligned16(dx1_in) || dx1_in == dxg)) return VLPET_E_ALIGN;
+    if (yout && (!gate || !saved || !aligned16(yout))) return VLPET_E_ALIGN;
+    if (saved && !aligned16(saved)) return VLPET_E_ALIGN;
     uint8_t* ws = reinterpret_cast<uint8_t*>(workspace);
+    const int f32 = io_dtype == VLPET_F32;
+    const hipStream_t st = (hipStream_t)stream;
 
     PetBwdArgs b;
     b.dy = dy; b.xa = xa; b.res = res; b.xg = xg;
     b.dxa = dxa; b.dxg = dxg; b.dxg_in = nullptr;
-    if (dx1_in && (!gate || !aligned16(dx1_in) || dx1_in == dxg)) return VLPET_E_ALIGN;
     b.z_a = ws + w.z_a; b.dp_a = ws + w.dp_a;
     b.z_g = gate ? ws + w.z_g : nullptr; b.dp_g = gate ? ws + w.dp_g : nullptr;
     b.dh = gate ? ws + w.dh : nullptr; b.dq = gate ? ws + w.dq : nullptr;
@@ -437,92 +551,20 @@ static int run_bwd(const void* dy, const void* xa, const void* res, const void* 
     b.M = M; b.d = d; b.RT = tiles;
     b.s2 = s2; b.sd = sd; b.gs = gs; b.flags = flags;
     b.gm = 1.f; b.go = 0.f; b.fsplit = 0; b.dz_part = nullptr;
-    if (yout && (!gate || !saved || !aligned16(yout))) return VLPET_E_ALIGN;
     b.y = (flags & PET_GATE_ADD) ? nullptr : yout;
     b.red_ctrl = nullptr; b.red_words = 0;
-    if (saved && !aligned16(saved)) return VLPET_E_ALIGN;
     b.saved = saved; b.saved_stride = (int64_t)saved_stride(M, tiles, io_dtype);
     if (saved) {        // z comes from the forward; the rows kernel does not write it
         b.z_a = const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(saved));
         if (gate) b.z_g = const_cast<uint8_t*>(reinterpret_cast<const uint8_t*>(saved)) + 2 * b.saved_stride;
     }
-    // two-pass form (pass 1: dpre only; pass 2: input gradients + weight gradients from recomputed dh / dq) unless the
-    // caller needs the input gradients right after phase 1 (phases bit 2: weight gradients on a side stream)
-    // bf16, r <= 96: pass 1 (dpre) + the column-parallel pass of pet_cols.hip (input gradients + the four weight gradients from
-    // one read of dy, x1, x2) -- unless the caller needs the input gradients right after phase 1
-    const bool cols6 = !(phases & 4) && k1_cols6_applies(b, io_dtype == VLPET_F32);
-    const bool cols4 = cols6 || (!(phases & 4) && k1_cols_applies(b, io_dtype == VLPET_F32));
-    const bool two_pass = cols4 || (!(phases & 4) && pet_gate_bwd3_applies(b));
-    const bool rows2 = !two_pass && pet_gate_bwd2_applies(b);
-    // without a gate (K2, adapter-only K1, K3 without dropout), bf16, saved activations, whole call: pass 1 (dpre) + the
-    // column-parallel pass of pet_cols_ng.hip (dx and both weight gradients from one read of dy and x)
-    const bool ng2 = !gate && phases == 3 && ng_two_pass_applies(b, io_dtype == VLPET_F32);
-    // round 6: pass 2 sums its row-chunk partials inside the launch (cols_reduce.h) -- no finalize launch; `phases` bit 5 keeps the
-    // round-3 two-launch form where other kernels may run beside the call (k1_in_launch_reduce; the results are bit-identical)
-    const bool red4 = cols4 && !cols6 && !(phases & 32) && k1_in_launch_reduce(M);
-    if (red4) { b.red_ctrl = reinterpret_cast<unsigned*>(ws + w.red_ctrl); b.red_words = (d / 128) * COLS_RED_STRIDE; }
-    int gs3 = 0, ng3 = 0;
-    if (ng2) {
-        WgradArgs g{};
-        g.M = M; g.RT = tiles; g.njobs = 2;
-        ng_cols_plan(M, d, &g.row_chunks, &g.rows_per_chunk);
-        g.partial = reinterpret_cast<float*>(ws + w.partial);
-        const int ldp = 32 * tiles;
-        WgradJob& J0 = g.job[0];                        // dWd[c,k] = sum_m dpre[m,c] x[m,k];  dbd = column sums of dpre
-        J0.P = b.dp_a; J0.ldp = ldp; J0.pcols = ldp; J0.X = xa; J0.ldx = d; J0.xcols = d; J0.drop = NO_DROP; J0.has_drop = 0;
-        J0.scale = drop_active(b.drop) ? b.drop.keep_scale : 1.f;      // (dropout: the kernel clears the dropped x, 1 / (1 - p) here)
-        J0.out = dwd; J0.ldo = d; J0.transposed = 0; J0.out_rows = r; J0.colsum_x = nullptr; J0.colsum_p = dbd;
-        WgradJob& J1 = g.job[1];                        // dWu[f,c] = sd * sum_m dy[m,f] z[m,c];  dbu = sd * column sums of dy
-        J1.P = b.z_a; J1.ldp = ldp; J1.pcols = ldp; J1.X = dy; J1.ldx = d; J1.xcols = d; J1.drop = NO_DROP; J1.has_drop = 0;
-        J1.scale = sd; J1.out = dwu; J1.ldo = r; J1.transposed = 1; J1.out_rows = r; J1.colsum_x = dbu; J1.colsum_p = nullptr;
-        // (the in-launch reduce-scatter of cols_reduce.h was built for this pass 2 as well and measured no gain: K2 backward 67.9 / 66.7 us
-        //  with it against 66.4 / 67.1 us with the finalize launch in the configs[1] step, profiles/r06_in_launch_reduce_ab.txt -- not kept)
-        hipError_t e = launch_ng_two_pass(b, g, 3, (hipStream_t)stream);
-        if (e != hipSuccess) return (int)e;
-        return herr(launch_wgrad_finalize(g, (hipStream_t)stream));
-    }
-    if (phases & 1) {
-        if (rows2) b.dxg_in = dx1_in;                   // the chain-split row kernel adds it in its epilogue
-        const bool dz2 = two_pass && k1_dz2_applies(b, io_dtype == VLPET_F32);
-        if (dz2 && gate) {      // small M: feature blocks (their fp32 partial dz in the dh / dq area, which the two-pass form does not use)
-            const int nfb = k1_dz2_feature_blocks(M, d);
-            const size_t need = (size_t)nfb * (size_t)M * 2 * 32 * tiles * 4;
-            if (nfb > 1 && need <= 2 * align256((size_t)M * d * (io_dtype == VLPET_F32 ? 4 : 2))) {
-                b.fsplit = nfb;
-                b.dz_part = reinterpret_cast<float*>(ws + w.dh);
-            }
-        }
-        const bool dz6 = two_pass && !dz2 && vlpet_tuning().dz6 != 0 && k1_dz6_applies(b, io_dtype == VLPET_F32);
-        if (dz6 && gate) {
-            const int nfb = k1_dz6_feature_blocks(M, d);
-            const size_t need = (size_t)nfb * (size_t)M * 2 * 32 * tiles * 4;
-            if (nfb > 1 && w.dq > w.dh && need <= 2 * (w.dq - w.dh)) {
-                b.fsplit = nfb;
-                b.dz_part = reinterpret_cast<float*>(ws + w.dh);
-            }
-        }
-        if (b.red_ctrl && !dz2) {       // a pass 1 that does not zero the reduce-scatter state itself (non-default forms): a memset node
-            hipError_t em = hipMemsetAsync(b.red_ctrl, 0, (size_t)b.red_words * 4, (hipStream_t)stream);
-            if (em != hipSuccess) return (int)em;
-        }
-        hipError_t e = dz2 ? launch_k1_dz2(b, (hipStream_t)stream)
-                     : dz6 ? launch_k1_dz6(b, (hipStream_t)stream)
-                     : two_pass ? launch_pet_gate_dz(b, io_dtype == VLPET_F32, (hipStream_t)stream)
-                     : rows2 ? launch_pet_gate_bwd2(b, io_dtype == VLPET_F32, (hipStream_t)stream)
-                             : launch_pet_bwd(b, io_dtype == VLPET_F32, (hipStream_t)stream);
-        if (e != hipSuccess) return (int)e;
-        if (dx1_in && !two_pass && !rows2) {            // other row kernels: one more pass over dx1
-            e = launch_add_inplace(dxg, dx1_in, M * (int64_t)d, io_dtype == VLPET_F32, (hipStream_t)stream);
-            if (e != hipSuccess) return (int)e;
-        }
-    }
-    if (!(phases & (2 | 16))) return 0;
 
+    const BwdPlan p = bwd_plan(b, phases, io_dtype, w);
+    if (p.rows == ROWS_GATE_BWD2) b.dxg_in = dx1_in;
+    if (p.fsplit) { b.fsplit = p.fsplit; b.dz_part = reinterpret_cast<float*>(ws + w.dh); }
+    if (p.wgrad == WG_K1_COLS_RED) { b.red_ctrl = reinterpret_cast<unsigned*>(ws + w.red_ctrl); b.red_words = (d / 128) * COLS_RED_STRIDE; }
     WgradArgs g{};
-    g.M = M; g.RT = tiles; g.row_chunks = w.row_chunks; g.rows_per_chunk = w.rows_per_chunk;
-    if (cols6) k1_cols6_plan(M, d, &g.row_chunks, &g.rows_per_chunk);
-    else if (cols4) k1_cols_plan(M, d, &g.row_chunks, &g.rows_per_chunk);
-    else if (two_pass) gate_bwd3_plan(M, d, io_dtype == VLPET_F32, &g.row_chunks, &g.rows_per_chunk, &gs3, &ng3);
+    g.M = M; g.RT = tiles; g.row_chunks = p.row_chunks; g.rows_per_chunk = p.rows_per_chunk;
     g.partial = reinterpret_cast<float*>(ws + w.partial);
     const int ldp = 32 * tiles;
     auto job = [&](int i, const void* P, const void* X, bool dropped, float scale, float* out, int ldo,
@@ -535,7 +577,9 @@ static int run_bwd(const void* dy, const void* xa, const void* res, const void* 
         J.colsum_x = csx; J.colsum_p = csp;
     };
     // down weight:  dWd[c,k] = sum_m dpre[m,c] * xa[m,k];  bias = column sums of dpre
-    job(0, b.dp_a, xa, true, 1.f, dwd, d, 0, r, nullptr, dbd);
+    // (dropout: wgrad.hip applies the mask to xa; pet_cols_ng.hip clears the dropped x itself and leaves 1 / (1 - p) to the scale)
+    const bool ng = p.wgrad == WG_NG;
+    job(0, b.dp_a, xa, !ng, ng && drop_active(b.drop) ? b.drop.keep_scale : 1.f, dwd, d, 0, r, nullptr, dbd);
     // up weight:    dWu[f,c] = sd * sum_m dh[m,f] * z[m,c]  (X = dh, or dy itself without a gate)
     job(1, b.z_a, gate ? b.dh : dy, false, sd, dwu, r, 1, r, dbu, nullptr);
     g.njobs = 2;
@@ -544,66 +588,62 @@ static int run_bwd(const void* dy, const void* xa, const void* res, const void* 
         job(3, b.z_g, b.dq, false, 1.f, dwgu, rg, 1, rg, dbgu, nullptr);
         g.njobs = 4;
     }
-    if (cols4) {
-        ColzArgs c{};
-        c.dy = dy; c.x1 = xg; c.x2 = res; c.dxin = dx1_in; c.y = b.y;
-        c.z_a = b.z_a; c.z_g = b.z_g; c.dp_a = b.dp_a; c.dp_g = b.dp_g;
-        c.dx1 = dxg; c.dx2 = dxa;
-        c.pk_a = b.pk_a; c.pk_g = b.pk_g;
-        c.M = M; c.d = d; c.s2 = s2; c.sd = sd; c.gs = gs; c.flags = flags;
-        c.row_chunks = g.row_chunks; c.rows_per_chunk = g.rows_per_chunk;
-        const WgradLayout L = wgrad_layout(g);
-        for (int j = 0; j < 4; ++j) c.part[j] = g.partial + L.off[j];
-        if (red4) {
-            // the same workspace bytes, cut differently: [RC][NCB] slabs (= the four [RC][PR][d] blocks), then the column-sum partials
-            const int64_t PRl = 32 * tiles;
-            c.red.slab = g.partial;
-            c.red.bias_x = g.partial + (int64_t)4 * g.row_chunks * PRl * d;
-            c.red.bias_p = c.red.bias_x + (int64_t)2 * g.row_chunks * d;
-            c.red.ctrl = reinterpret_cast<unsigned*>(ws + w.red_ctrl);
-            c.red.spin_limit = COLS_RED_SPIN_DEFAULT;
-            for (int j = 0; j < 4; ++j) {
-                const WgradJob& J = g.job[j];
-                c.red.job[j] = ColsRedJob{J.out, J.ldo, J.transposed, J.out_rows, J.scale, J.colsum_x, J.colsum_p};
-            }
-            if (!(phases & 2)) return 0;                    // ("finalize only": there is none)
-            return herr(launch_k1_cols(c, tiles, (hipStream_t)stream));
+    auto add_dx1 = [&](int after) {     // the forms whose kernels do not take dx1_in: one more pass over dx1
+        if (!dx1_in || p.add_dx1 != after) return hipSuccess;
+        return launch_add_inplace(dxg, dx1_in, M * (int64_t)d, f32, st);
+    };
+
+    hipError_t e = hipSuccess;
+    if (phases & 1) {
+        if (p.memset_red) e = hipMemsetAsync(b.red_ctrl, 0, (size_t)b.red_words * 4, st);
+        if (e != hipSuccess) return (int)e;
+        switch (p.rows) {
+            case ROWS_PET_BWD:   e = launch_pet_bwd(b, f32, st); break;
+            case ROWS_GATE_BWD2: e = launch_pet_gate_bwd2(b, f32, st); break;
+            case ROWS_GATE_DZ:   e = launch_pet_gate_dz(b, f32, st); break;
+            case ROWS_K1_DZ2:    e = launch_k1_dz2(b, st); break;
+            case ROWS_K1_DZ6:    e = launch_k1_dz6(b, st); break;
+            case ROWS_NG:        e = launch_ng_two_pass(b, g, 1, st); break;
         }
-        if (phases & 2) {
-            hipError_t e = cols6 ? launch_k1_cols6y(c, (hipStream_t)stream)
-                                 : launch_k1_cols(c, tiles, (hipStream_t)stream);
-            if (e != hipSuccess) return (int)e;
+        if (e == hipSuccess) e = add_dx1(1);
+        if (e != hipSuccess) return (int)e;
+    }
+    if (phases & 2) {
+        switch (p.wgrad) {
+            case WG_WGRAD:       e = launch_wgrad(g, f32, st); break;
+            case WG_GATE_COLS:   e = launch_pet_gate_cols(b, g, p.gs3, p.ng3, f32, st); break;
+            case WG_K1_COLS:
+            case WG_K1_COLS_RED: e = launch_k1_cols(colz_args(b, g, dx1_in), tiles, st); break;
+            case WG_K1_COLS6Y:   e = launch_k1_cols6y(colz_args(b, g, dx1_in), st); break;
+            case WG_NG:          e = launch_ng_two_pass(b, g, 2, st); break;
         }
-        if ((phases & 8) && !(phases & 16)) return 0;       // (the partial sums stay in the workspace)
-        return herr(launch_wgrad_finalize(g, (hipStream_t)stream));
+        if (e == hipSuccess) e = add_dx1(2);
+        if (e != hipSuccess) return (int)e;
     }
-    if (!(phases & 2)) return 0;                            // (bits 3 / 4 split the column-parallel form only)
-    if (two_pass) {                                     // (dx1 is an output of pass 2 there)
-        hipError_t e = launch_pet_gate_cols(b, g, gs3, ng3, io_dtype == VLPET_F32, (hipStream_t)stream);
-        if (e == hipSuccess && dx1_in) e = launch_add_inplace(dxg, dx1_in, M * (int64_t)d, io_dtype == VLPET_F32, (hipStream_t)stream);
-        return herr(e);
-    }
-    return herr(launch_wgrad(g, io_dtype == VLPET_F32, (hipStream_t)stream));
+    // bit 3 without bit 4 leaves the partial sums in the workspace; bit 4 alone ("finalize only") sums them
+    if (p.finalize && (phases & (2 | 16)) && (!(phases & 8) || (phases & 16))) e = launch_wgrad_finalize(g, st);
+    return herr(e);
 }
 
+// The plan of the default gated call at a shape: the forward's block and its output handed over, the whole call, no `phases` bit 5
+static BwdPlan gate_bwd_plan_at(int64_t M, int d, int tiles, int io_dtype) {
+    PetBwdArgs b{};
+    b.M = M; b.d = d; b.RT = tiles; b.flags = PET_GATE; b.saved = &b; b.drop = NO_DROP; b.y = &b;
+    return bwd_plan(b, 3, io_dtype, bwd_ws(M, d, tiles, true, io_dtype));
+}
+
+// 2: pass 1 + the column-parallel pass of pet_cols.hip / pet_cols6y.hip; 1: the two passes of pet_gate_bwd3.hip; 0: row kernel + wgrad.hip
 extern "C" int vlpet_adapter_gate_bwd_form(int64_t M, int d, int tiles, int io_dtype) {
     if (check_common(M, d, tiles, io_dtype)) return -1;
-    PetBwdArgs b{};
-    b.M = M; b.d = d; b.RT = tiles; b.flags = PET_GATE; b.saved = &b; b.drop = NO_DROP; b.y = &b;      // (the default path hands the forward's output over)
-    if (k1_cols_applies(b, io_dtype == VLPET_F32) || k1_cols6_applies(b, io_dtype == VLPET_F32)) return 2;
-    if (pet_gate_bwd3_applies(b)) return 1;
-    return 0;
+    const BwdWgrad wg = gate_bwd_plan_at(M, d, tiles, io_dtype).wgrad;
+    return wg == WG_WGRAD ? 0 : wg == WG_GATE_COLS ? 1 : 2;
 }
 
 // For a call without `phases` bit 5 -- 1: the two-pass form at this shape ends in a separate finalize launch (`phases` bit 4 runs
 // it); 0: pass 2 sums its row chunks itself (round 6, cols_reduce.h) or the form is not the two-pass one
 extern "C" int vlpet_adapter_gate_bwd_finalize_launch(int64_t M, int d, int tiles, int io_dtype) {
     if (check_common(M, d, tiles, io_dtype)) return -1;
-    PetBwdArgs b{};
-    b.M = M; b.d = d; b.RT = tiles; b.flags = PET_GATE; b.saved = &b; b.drop = NO_DROP; b.y = &b;
-    if (k1_cols6_applies(b, io_dtype == VLPET_F32)) return 1;
-    if (k1_cols_applies(b, io_dtype == VLPET_F32)) return k1_in_launch_reduce(M) ? 0 : 1;
-    return 0;
+    return gate_bwd_plan_at(M, d, tiles, io_dtype).finalize ? 1 : 0;
 }
 
 // K1 / K2 / K3 backward: one argument check per operator in front of run_bwd.

@@ -164,3 +164,54 @@ __device__ __forceinline__ void gate_bwd_ew(float dys, float dyl, float gt, floa
         dq = dh * hy * (1.0f - gt);
     }
 }
+
+// ================================================================================================== pass 1, feature-split forms
+// What pet_dz2.hip and pet_dz6.hip share.
+// Cache policy of pass 1's row loads (dy, x2).  Pass 2 reads both tensors again right after this launch: with the non-temporal policy
+// of the other row streams (aux 2) pass 1 discourages exactly the lines pass 2 is about to ask for.
+constexpr int P1_AUX = 2;
+__device__ __forceinline__ void glds16_p1(const void* gsrc, void* lds_wave_base) {
+    __builtin_amdgcn_global_load_lds((gmem_cv*)gsrc, (lmem_v*)lds_wave_base, 16, 0, P1_AUX);
+}
+// The elementwise backward of a lane's 16 values (4 features at a time) once their dy and x2 (YF: y) words are on their way from the
+// row tiles: dh, dq come out as bf16 pairs in register order -- the B fragments kappa = 0 (words 0-3) and 1 (words 4-7) of the
+// contraction.  aG / aA: the gate's and the adapter chain's up projections (aA is read by the plain form only).  PIN: k1_dz2_kernel
+// pins the operands of a group of four in registers at the group's start.
+template <bool ADD, bool YF, bool PIN>
+__device__ __forceinline__ void dz_ew(u32x2* dyv, u32x2* x2v, f32x16& aG, const f32x16* aA, const float& gs, const float& s2,
+                                      const float& sd, uint32_t* bh, uint32_t* bq) {
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dyv[0]), "+v"(x2v[0]), "+v"(dyv[1]), "+v"(x2v[1]), "+v"(dyv[2]), "+v"(x2v[2]), "+v"(dyv[3]), "+v"(x2v[3]) :: "memory");
+    sfor<4>([&](auto Q) {
+        constexpr int q = Q.value;
+        if constexpr (PIN)
+            asm volatile("" : "+v"(dyv[q]), "+v"(x2v[q]), "+v"(aG[4 * q]), "+v"(aG[4 * q + 1]), "+v"(aG[4 * q + 2]), "+v"(aG[4 * q + 3]) :: "memory");
+        float dh[4], dq[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int e = 4 * q + j;
+            const float gt = sigm(aG[e]);
+            const float dyr = (j & 1) ? bf_hi(dyv[q][j >> 1]) : bf_lo(dyv[q][j >> 1]);
+            const float dy_ = gs * dyr;
+            const float x2r = (j & 1) ? bf_hi(x2v[q][j >> 1]) : bf_lo(x2v[q][j >> 1]);       // x2, or (YF: the row ring's second tile) y
+            gate_bwd_ew<ADD, YF>(dy_, dyr, gt, ADD ? 0.f : YF ? x2r : s2 * x2r + sd * (*aA)[e], dh[j], dq[j]);
+        }
+        typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
+        const bf16x4 th = {(__bf16)dh[0], (__bf16)dh[1], (__bf16)dh[2], (__bf16)dh[3]};
+        const bf16x4 tq = {(__bf16)dq[0], (__bf16)dq[1], (__bf16)dq[2], (__bf16)dq[3]};
+        const u32x2 uh = __builtin_bit_cast(u32x2, th), uq = __builtin_bit_cast(u32x2, tq);
+        bh[2 * q] = uh[0]; bh[2 * q + 1] = uh[1];
+        bq[2 * q] = uq[0]; bq[2 * q + 1] = uq[1];
+    });
+}
+// host: (M / 128 row blocks) x (feature blocks) workgroups of THREADS, GEO::bytes(d) of LDS; the feature blocks are summed by a second launch
+template <typename GEO, int THREADS, int PR>
+static hipError_t launch_dz_form(void (*kern)(PetBwdArgs), const PetBwdArgs& a, hipStream_t stream) {
+    const size_t lds = GEO::bytes(a.d);
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) return e;
+    const unsigned blocks = (unsigned)((a.M + 127) / 128);
+    const unsigned nfb = a.fsplit > 1 ? (unsigned)a.fsplit : 1u;
+    hipLaunchKernelGGL(kern, dim3(blocks, nfb), dim3(THREADS), lds, stream, a);
+    if (nfb > 1) return launch_k1_dz_reduce(a, PR, stream);
+    return hipGetLastError();
+}

@@ -84,7 +84,8 @@ struct PetBwdArgs {
     float s2, sd, gs;
     int flags;
     float gm, go;           // low-rank visual projector: gate value = gm * sigmoid(.) + go (unused otherwise)
-    int fsplit;             // pass 1 of the two-pass form (pet_dz2.hip), small M: feature blocks (> 1: partial dz in dz_part, summed by a second launch)
+    int fsplit;             // pass 1 of the two-pass form (pet_dz2.hip, pet_dz6.hip), small M: feature blocks, set from api.hip BwdPlan::fsplit
+                            //   (> 1: partial dz in dz_part, summed by a second launch)
     float* dz_part;         //   [fsplit][M][2][32*RT] fp32
     const void* y;          // optional (gated K1, multiplicative gate, saved form): the forward's OUTPUT [M,d] -- pass 1 then forms
                             //   dq = dy * y * (1 - g) and skips the adapter chain's up projection (pet_dz2.hip / pet_dz6.hip)

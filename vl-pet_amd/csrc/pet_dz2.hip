@@ -19,13 +19,6 @@
 // like pet_cols' bottleneck tiles) + the dy and x2 tiles [128 rows x 128 B] (pet16.h swz); three weight slots + two row slots + the biases = 142 KiB (see the loop for why three).
 #include "cols_common.h"
 
-// Cache policy of pass 1's row loads (dy, x2).  Pass 2 reads both tensors again right after this launch: with the non-temporal policy
-// of the other row streams (aux 2) pass 1 discourages exactly the lines pass 2 is about to ask for.
-constexpr int P1_AUX = 2;
-__device__ __forceinline__ void glds16_p1(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gmem_cv*)gsrc, (lmem_v*)lds_wave_base, 16, 0, P1_AUX);
-}
-
 template <int RT> struct Dz2Geo {
     static constexpr int AW = RT == 1 ? 2 : 1, AX = RT == 1 ? 2 : 1;   // stages the weight / row requests run ahead: two at RT = 1 (LDS allows it)
     static constexpr int NWS = AW + 2, NXS = AX + 1;   // slots (a stage's weight image is used for two steps)
@@ -168,27 +161,7 @@ __global__ __launch_bounds__(512, 2) void k1_dz2_kernel(PetBwdArgs a) {
             lds_read8<0>(dyv[Q.value], xb + a_row[Q.value]);
             lds_read8<XT_B>(x2v[Q.value], xb + a_row[Q.value]);
         });
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dyv[0]), "+v"(x2v[0]), "+v"(dyv[1]), "+v"(x2v[1]), "+v"(dyv[2]), "+v"(x2v[2]), "+v"(dyv[3]), "+v"(x2v[3]) :: "memory");
-        sfor<4>([&](auto Q) {
-            constexpr int q = Q.value;
-            asm volatile("" : "+v"(dyv[q]), "+v"(x2v[q]), "+v"(aG[4 * q]), "+v"(aG[4 * q + 1]), "+v"(aG[4 * q + 2]), "+v"(aG[4 * q + 3]) :: "memory");
-            float dh[4], dq[4];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const int e = 4 * q + j;
-                const float gt = sigm(aG[e]);
-                const float dyr = (j & 1) ? bf_hi(dyv[q][j >> 1]) : bf_lo(dyv[q][j >> 1]);
-                const float dy_ = gs * dyr;
-                const float x2r = (j & 1) ? bf_hi(x2v[q][j >> 1]) : bf_lo(x2v[q][j >> 1]);       // x2, or (YF: the row ring's second tile) y
-                gate_bwd_ew<ADD, YF>(dy_, dyr, gt, ADD ? 0.f : YF ? x2r : s2 * x2r + sd * aA[e], dh[j], dq[j]);
-            }
-            typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-            const bf16x4 th = {(__bf16)dh[0], (__bf16)dh[1], (__bf16)dh[2], (__bf16)dh[3]};
-            const bf16x4 tq = {(__bf16)dq[0], (__bf16)dq[1], (__bf16)dq[2], (__bf16)dq[3]};
-            const u32x2 uh = __builtin_bit_cast(u32x2, th), uq = __builtin_bit_cast(u32x2, tq);
-            bh[2 * q] = uh[0]; bh[2 * q + 1] = uh[1];
-            bq[2 * q] = uq[0]; bq[2 * q + 1] = uq[1];
-        });
+        dz_ew<ADD, YF, true>(dyv, x2v, aG, &aA, gs, s2, sd, bh, bq);
     };
     // contraction over this wave's 32 features of stage s: dz[ct] += W^T (transpose reads of the same image) . dh / dq
     auto contract1 = [&](uint32_t sb, auto TC, const uint32_t* bw, f32x16* dz) {
@@ -392,24 +365,12 @@ bool k1_dz2_applies(const PetBwdArgs& a, int io_fp32) {
     return false;
 }
 
-template <int RT, bool ADD, bool YF>
-static hipError_t launch_dz2_form(const PetBwdArgs& a, hipStream_t stream) {
-    using GEO = Dz2Geo<RT>;
-    const size_t lds = GEO::bytes(a.d);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k1_dz2_kernel<RT, ADD, YF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    const unsigned blocks = (unsigned)((a.M + 127) / 128);
-    const unsigned nfb = a.fsplit > 1 ? (unsigned)a.fsplit : 1u;
-    hipLaunchKernelGGL((k1_dz2_kernel<RT, ADD, YF>), dim3(blocks, nfb), dim3(512), lds, stream, a);
-    if (nfb > 1) return launch_k1_dz_reduce(a, 32 * RT, stream);
-    return hipGetLastError();
-}
-
 template <int RT>
 static hipError_t launch_dz2_rt(const PetBwdArgs& a, hipStream_t stream) {
-    if (a.flags & PET_GATE_ADD) return launch_dz2_form<RT, true, false>(a, stream);
-    if (a.y != nullptr) return launch_dz2_form<RT, false, true>(a, stream);      // from the forward's output (see the kernel)
-    return launch_dz2_form<RT, false, false>(a, stream);
+    auto launch = [&](void (*kern)(PetBwdArgs)) { return launch_dz_form<Dz2Geo<RT>, 512, 32 * RT>(kern, a, stream); };
+    if (a.flags & PET_GATE_ADD) return launch(k1_dz2_kernel<RT, true, false>);
+    if (a.y != nullptr) return launch(k1_dz2_kernel<RT, false, true>);      // from the forward's output (see the kernel)
+    return launch(k1_dz2_kernel<RT, false, false>);
 }
 
 hipError_t launch_k1_dz2(const PetBwdArgs& a, hipStream_t stream) {

@@ -16,13 +16,6 @@
 // refilled every second half-stage) + the up biases (6 KiB) = 118 KiB.
 #include "cols_common.h"
 
-// Cache policy of pass 1's row loads (dy, x2).  Pass 2 reads both tensors again right after this launch: with the non-temporal policy
-// of the other row streams (aux 2) pass 1 discourages exactly the lines pass 2 is about to ask for.
-constexpr int P1_AUX = 2;
-__device__ __forceinline__ void glds16_p1(const void* gsrc, void* lds_wave_base) {
-    __builtin_amdgcn_global_load_lds((gmem_cv*)gsrc, (lmem_v*)lds_wave_base, 16, 0, P1_AUX);
-}
-
 // Round 5 (profiles/r05_k1bench_dz6_variants.txt): the first requests go out before the z / bias wait, the z registers are pinned at the
 // wait, and the epilogue's act' rows come through LDS (all 48 act' loads first measured SLOWER: 69.9 vs 62.1 us at 18,250 rows -- 96 more
 // live registers cost the loop more than the batched loads save).
@@ -227,26 +220,7 @@ __global__ __launch_bounds__(256) void k1_dz6_kernel(PetBwdArgs a) {
                 lds_read8<0>(dyv[Q.value], xb + (a_row[Q.value] ^ fbit));
                 lds_read8<XT_B>(x2v[Q.value], xb + (a_row[Q.value] ^ fbit));
             });
-            asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(dyv[0]), "+v"(x2v[0]), "+v"(dyv[1]), "+v"(x2v[1]), "+v"(dyv[2]), "+v"(x2v[2]), "+v"(dyv[3]), "+v"(x2v[3]) :: "memory");
-            sfor<4>([&](auto Q) {
-                constexpr int q = Q.value;
-                float dh[4], dq[4];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const int e = 4 * q + j;
-                    const float gt = sigm(aG[e]);
-                    const float dyr = (j & 1) ? bf_hi(dyv[q][j >> 1]) : bf_lo(dyv[q][j >> 1]);
-                    const float dy_ = gs * dyr;
-                    const float x2r = (j & 1) ? bf_hi(x2v[q][j >> 1]) : bf_lo(x2v[q][j >> 1]);       // x2, or (YF: the row ring's second tile) y
-                    gate_bwd_ew<ADD, YF>(dy_, dyr, gt, ADD ? 0.f : YF ? x2r : s2 * x2r + sd * aA[e], dh[j], dq[j]);
-                }
-                typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
-                const bf16x4 th = {(__bf16)dh[0], (__bf16)dh[1], (__bf16)dh[2], (__bf16)dh[3]};
-                const bf16x4 tq = {(__bf16)dq[0], (__bf16)dq[1], (__bf16)dq[2], (__bf16)dq[3]};
-                const u32x2 uh = __builtin_bit_cast(u32x2, th), uq = __builtin_bit_cast(u32x2, tq);
-                bh[2 * q] = uh[0]; bh[2 * q + 1] = uh[1];
-                bq[2 * q] = uq[0]; bq[2 * q + 1] = uq[1];
-            });
+            dz_ew<ADD, YF, false>(dyv, x2v, aG, &aA, gs, s2, sd, bh, bq);
         }
         contract1(sb, std::integral_constant<int, 0>{}, bh, dzA);
         contract1(sb, std::integral_constant<int, 1>{}, bq, dzG);
@@ -352,21 +326,9 @@ bool k1_dz6_applies(const PetBwdArgs& a, int io_fp32) {
     return a.RT == 6 && Dz6Geo<6>::bytes(a.d) <= (size_t)160 * 1024;
 }
 
-template <bool ADD, bool YF>
-static hipError_t launch_dz6_form(const PetBwdArgs& a, hipStream_t stream) {
-    using GEO = Dz6Geo<6>;
-    const size_t lds = GEO::bytes(a.d);
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k1_dz6_kernel<6, ADD, YF>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) return e;
-    const unsigned blocks = (unsigned)((a.M + 127) / 128);
-    const unsigned nfb = a.fsplit > 1 ? (unsigned)a.fsplit : 1u;
-    hipLaunchKernelGGL((k1_dz6_kernel<6, ADD, YF>), dim3(blocks, nfb), dim3(256), lds, stream, a);
-    if (nfb > 1) return launch_k1_dz_reduce(a, 32 * 6, stream);
-    return hipGetLastError();
-}
-
 hipError_t launch_k1_dz6(const PetBwdArgs& a, hipStream_t stream) {
-    if (a.flags & PET_GATE_ADD) return launch_dz6_form<true, false>(a, stream);
-    if (a.y != nullptr) return launch_dz6_form<false, true>(a, stream);
-    return launch_dz6_form<false, false>(a, stream);
+    auto launch = [&](void (*kern)(PetBwdArgs)) { return launch_dz_form<Dz6Geo<6>, 256, 32 * 6>(kern, a, stream); };
+    if (a.flags & PET_GATE_ADD) return launch(k1_dz6_kernel<6, true, false>);
+    if (a.y != nullptr) return launch(k1_dz6_kernel<6, false, true>);
+    return launch(k1_dz6_kernel<6, false, false>);
 }

@@ -712,7 +712,7 @@ def k1_bwd_schedule(gate: bool, saved: bool, side: bool, previous_split: bool, b
     if not bracketed:
         return [(None, 3, False)]
     if not gate:
-        # adapter-only K1 (small / middle gate scripts): its two-pass form is taken for the WHOLE op only (csrc/api.hip ng2), so the
+        # adapter-only K1 (small / middle gate scripts): its two-pass form is taken for the WHOLE op only (csrc/api.hip bwd_plan: ROWS_NG), so the
         # bracketed path issues it as one call too -- split phases would time the round-2 row kernel instead of what ships
         return [(rows, 3, False)]
     if not (saved and form == 2):
