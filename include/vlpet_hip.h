@@ -802,6 +802,31 @@ int vlpet_phm_expand_pair_bwd(const float* dwt_d, const float* dwt_u, const void
                               const void* W_u, float* drule_d, float* dW_d, float* drule_u, float* dW_u, void* workspace,
                               size_t workspace_bytes, int d, int r, int n, int param_dtype, vlpet_stream_t stream);
 
+/* Hyperformer: the adapter weights of every layer of one stack, generated from the layers' embeddings (csrc/hyper.hip).  A stack's
+ * hyper-network is S linear maps applied to the same E embedding rows: map s has weight G[s] [n[s], P] and bias g[s] [n[s]] (the `.0`
+ * Linear of a weight_generator / bias_generator, nn.Linear layout, in param_dtype); e [E, P] is fp32.
+ *   out[s][l, i] = g[s][i] + sum_p G[s][i, p] e[l, p]          out[s]: [E, n[s]] in param_dtype; the sums are fp32 (p ascending, then
+ *                                                             the bias)
+ * Row l of a weight generator's output, viewed [r, d] (down) or [d, r] (up), is the nn.Linear layout K2 / K1 / adapter_tail take.
+ * vlpet_hyper_gen_fwd is ONE launch for all S maps.  G, g, n, out (and dout, dG, dg below) are HOST arrays of S entries (dout: S * E,
+ * map-major); they are copied into the kernel arguments, so they may be freed or reused as soon as the call returns.
+ * vlpet_hyper_gen_bwd: dout[s * E + l] is an fp32 [n[s]] device pointer (as the K2 backward leaves dwd / dbd / dwu / dbu of non-leaf
+ * weights) or NULL, which means zeros.  All results are fp32 and overwritten:
+ *   dG[s][i, p] = sum_l dout[s][l][i] e[l, p]     dg[s][i] = sum_l dout[s][l][i]     de[l, p] = sum_s sum_i dout[s][l][i] G[s][i, p]
+ * Two launches (slabs of 256 rows of one map, then the sum of the slabs' de partials: 16 runs of consecutive slabs, each in slab order,
+ * then the runs in order); no atomics: two runs give the same bits.  workspace: vlpet_hyper_gen_workspace_bytes(S, n, E, P) bytes (0 for
+ * arguments the calls refuse).  The calls read no device memory on the host, allocate nothing and are capture-safe.
+ * Limits: 1 <= S <= 16, 1 <= E <= 64, 1 <= P <= 64, S * E <= 256 (the row pointers travel in the kernel arguments), n[s] >= 1.
+ * Argument errors (no launch), in this order: VLPET_E_NULL (a table, e, de or the workspace; with S in range, an entry of G, g, out,
+ * dG or dg); VLPET_E_DTYPE; VLPET_E_SHAPE (a limit above); VLPET_E_ALIGN (16 bytes; the entries of dout: 4); VLPET_E_WORKSPACE;
+ * VLPET_E_ALIAS (an output overlaps an input or another output). */
+size_t vlpet_hyper_gen_workspace_bytes(int S, const int* n, int E, int P);
+int vlpet_hyper_gen_fwd(int S, const void* const* G, const void* const* g, const int* n, const float* e, int E, int P,
+                        void* const* out, int param_dtype, vlpet_stream_t stream);
+int vlpet_hyper_gen_bwd(int S, const float* const* dout, const void* const* G, const int* n, const float* e, int E, int P,
+                        float* const* dG, float* const* dg, float* de, void* workspace, size_t workspace_bytes,
+                        int param_dtype, vlpet_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

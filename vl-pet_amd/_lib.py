@@ -180,6 +180,10 @@ SIGNATURES = {
     "vlpet_phm_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "vlpet_phm_expand_pair_fwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_int, c_int, c_void_p]),
     "vlpet_phm_expand_pair_bwd": (c_int, [c_void_p] * 11 + [c_size_t, c_int, c_int, c_int, c_int, c_void_p]),
+    "vlpet_hyper_gen_workspace_bytes": (c_size_t, [c_int, c_void_p, c_int, c_int]),
+    "vlpet_hyper_gen_fwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "vlpet_hyper_gen_bwd": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_size_t, c_int, c_void_p]),
 }
 
 

@@ -44,3 +44,18 @@ class AdapterConfig:
     shared_W_phm: bool = False
     factorized_phm_rule: bool = False
     kronecker_prod: bool = False
+
+
+@dataclass
+class MetaAdapterConfig(AdapterConfig):
+    """Hyperformer: a hyper-network generates the adapters' weights from task and layer embeddings (reference: adapters/config.py:58-75,
+    the class defaults; ``projected_task_embedding_dim`` is what ``--projected_task_embedding_dim`` sets, 8 in hyperformer.sh)."""
+    task_embedding_dim: int = 512
+    task_hidden_dim: int = 128
+    projected_task_embedding_dim: int = 64
+    unique_hyper_net: bool = True
+    unique_hyper_net_layer_norm: bool = True
+    efficient_unique_hyper_net: bool = False
+    # forms no flag of the reference reaches: refused with a ValueError that names the field
+    train_task_embeddings: bool = False
+    task_to_embeddings: Optional[dict] = None

@@ -9,7 +9,7 @@
 #include <stdio.h>
 #include <vector>
 
-#define VLPET_VERSION 680      // 680: vlpet_prefix_concat_dropout_fwd, vlpet_prefix_concat_dropout_bwd, vlpet_prefix_concat_chunks, vlpet_prefix_concat_ws_bytes (prefix_cat.hip: the joint encoder's input assembly with a broadcast prompt in front, prompt tuning); 670: vlpet_phm_expand_pair_fwd, vlpet_phm_expand_pair_bwd, vlpet_phm_workspace_bytes (phm.hip: Compacter's PHM weight expansion of one adapter and its backward); 660: vlpet_adapter_tail_fwd, vlpet_adapter_tail_applies, vlpet_adapter_tail_rows (adapter_tail.hip: sequential adapter + residual + norm in one launch, inference form); 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
+#define VLPET_VERSION 681      // 681: vlpet_hyper_gen_fwd, vlpet_hyper_gen_bwd, vlpet_hyper_gen_workspace_bytes (hyper.hip: Hyperformer's weight generator of one stack, S linear maps on the same E embedding rows, and its backward); 680: vlpet_prefix_concat_dropout_fwd, vlpet_prefix_concat_dropout_bwd, vlpet_prefix_concat_chunks, vlpet_prefix_concat_ws_bytes (prefix_cat.hip: the joint encoder's input assembly with a broadcast prompt in front, prompt tuning); 670: vlpet_phm_expand_pair_fwd, vlpet_phm_expand_pair_bwd, vlpet_phm_workspace_bytes (phm.hip: Compacter's PHM weight expansion of one adapter and its backward); 660: vlpet_adapter_tail_fwd, vlpet_adapter_tail_applies, vlpet_adapter_tail_rows (adapter_tail.hip: sequential adapter + residual + norm in one launch, inference form); 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
 #define VLPET_VERSION_R3 300      // 300: column-parallel K1 backward pass (pet_cols.hip), phases bits 3 / 4, vlpet_adapter_gate_bwd_form;
 #define VLPET_VERSION_R2 221      // 221: vlpet_sublayer_tail_reduce, vlpet_layernorm_bwd_xhat, vlpet_rmsnorm_{fwd,bwd}, vlpet_colsum;  round 2: LoRA dropout generator ABI, sliced AdamW, K3 training form; 210: strided attention entry points, streaming weight gradients; 220: low-rank visual projector
 
@@ -1851,4 +1851,91 @@ extern "C" int vlpet_phm_expand_pair_bwd(const float* dwt_d, const float* dwt_u,
     a.l[1].rule = rule_u; a.l[1].W = W_u; a.l[1].dwt = dwt_u; a.l[1].drule = drule_u; a.l[1].dW = dW_u; a.l[1].in = r; a.l[1].out = d;
     a.n = n; a.ws = reinterpret_cast<float*>(workspace);
     return herr(launch_phm_expand_bwd(a, param_dtype == VLPET_F32, (hipStream_t)stream));
+}
+
+// ---- Hyperformer: one stack's weight generator (S linear maps on the same E embedding rows) and its backward (hyper.hip)
+// -> 0 and the workgroups of every map's row slabs (blk0[s]: the first of map s), or VLPET_E_SHAPE
+static int hyper_geometry(int S, const int* n, int E, int P, int* blk0, int64_t* blocks) {
+    if (S < 1 || S > HYP_MAX_S || E < 1 || E > HYP_MAX_E || P < 1 || P > HYP_MAX_P || S * E > HYP_MAX_ROWPTRS) return VLPET_E_SHAPE;
+    int64_t b = 0;
+    for (int s = 0; s < S; ++s) {
+        if (n[s] < 1) return VLPET_E_SHAPE;
+        if (blk0) blk0[s] = (int)b;
+        b += ((int64_t)n[s] + HYP_ROWS - 1) / HYP_ROWS;
+        if (b > 0x7fffffffLL / (HYP_MAX_E * HYP_MAX_P)) return VLPET_E_SHAPE;
+    }
+    *blocks = b;
+    return 0;
+}
+extern "C" size_t vlpet_hyper_gen_workspace_bytes(int S, const int* n, int E, int P) {
+    int64_t blocks = 0;
+    if (!n || hyper_geometry(S, n, E, P, nullptr, &blocks) != 0) return 0;
+    return align256((size_t)blocks * E * P * sizeof(float));
+}
+
+extern "C" int vlpet_hyper_gen_fwd(int S, const void* const* G, const void* const* g, const int* n, const float* e, int E, int P,
+                                   void* const* out, int param_dtype, vlpet_stream_t stream) {
+    if (!G || !g || !n || !e || !out) return VLPET_E_NULL;
+    if (S >= 1 && S <= HYP_MAX_S)
+        for (int s = 0; s < S; ++s)
+            if (!G[s] || !g[s] || !out[s]) return VLPET_E_NULL;
+    if (!dtype_ok(param_dtype)) return VLPET_E_DTYPE;
+    HyperFwdArgs a{};
+    int blk0[HYP_MAX_S];
+    int64_t blocks = 0;
+    if (int rc = hyper_geometry(S, n, E, P, blk0, &blocks)) return rc;
+    if (!aligned16(e)) return VLPET_E_ALIGN;
+    for (int s = 0; s < S; ++s)
+        if (!aligned16(G[s]) || !aligned16(g[s]) || !aligned16(out[s])) return VLPET_E_ALIGN;
+    const size_t es = param_dtype == VLPET_F32 ? 4 : 2;
+    ByteRange in[2 * HYP_MAX_S + 1], o[HYP_MAX_S];
+    for (int s = 0; s < S; ++s) {
+        in[2 * s] = {G[s], (size_t)n[s] * P * es};
+        in[2 * s + 1] = {g[s], (size_t)n[s] * es};
+        o[s] = {out[s], (size_t)E * n[s] * es};
+    }
+    in[2 * S] = {e, (size_t)E * P * 4};
+    if (phm_outputs_alias(in, 2 * S + 1, o, S)) return VLPET_E_ALIAS;
+    for (int s = 0; s < S; ++s) a.m[s] = {G[s], g[s], out[s], n[s], blk0[s]};
+    a.e = e; a.S = S; a.E = E; a.P = P;
+    return herr(launch_hyper_gen_fwd(a, (int)blocks, param_dtype == VLPET_F32, (hipStream_t)stream));
+}
+
+extern "C" int vlpet_hyper_gen_bwd(int S, const float* const* dout, const void* const* G, const int* n, const float* e, int E, int P,
+                                   float* const* dG, float* const* dg, float* de, void* workspace, size_t workspace_bytes,
+                                   int param_dtype, vlpet_stream_t stream) {
+    if (!dout || !G || !n || !e || !dG || !dg || !de || !workspace) return VLPET_E_NULL;
+    if (S >= 1 && S <= HYP_MAX_S)
+        for (int s = 0; s < S; ++s)
+            if (!G[s] || !dG[s] || !dg[s]) return VLPET_E_NULL;
+    if (!dtype_ok(param_dtype)) return VLPET_E_DTYPE;
+    int blk0[HYP_MAX_S];
+    int64_t blocks = 0;
+    if (int rc = hyper_geometry(S, n, E, P, blk0, &blocks)) return rc;
+    if (!aligned16(e) || !aligned16(de) || !aligned16(workspace)) return VLPET_E_ALIGN;
+    for (int s = 0; s < S; ++s)
+        if (!aligned16(G[s]) || !aligned16(dG[s]) || !aligned16(dg[s])) return VLPET_E_ALIGN;
+    for (int k = 0; k < S * E; ++k)
+        if (reinterpret_cast<uintptr_t>(dout[k]) & 3) return VLPET_E_ALIGN;
+    const size_t need = align256((size_t)blocks * E * P * sizeof(float));
+    if (workspace_bytes < need) return VLPET_E_WORKSPACE;
+    const size_t es = param_dtype == VLPET_F32 ? 4 : 2;
+    ByteRange in[HYP_MAX_ROWPTRS + HYP_MAX_S + 1], o[2 * HYP_MAX_S + 2];
+    int n_in = 0, n_out = 0;
+    for (int s = 0; s < S; ++s) {
+        for (int l = 0; l < E; ++l)
+            if (dout[s * E + l]) in[n_in++] = {dout[s * E + l], (size_t)n[s] * 4};
+        in[n_in++] = {G[s], (size_t)n[s] * P * es};
+        o[n_out++] = {dG[s], (size_t)n[s] * P * 4};
+        o[n_out++] = {dg[s], (size_t)n[s] * 4};
+    }
+    in[n_in++] = {e, (size_t)E * P * 4};
+    o[n_out++] = {de, (size_t)E * P * 4};
+    o[n_out++] = {workspace, need};
+    if (phm_outputs_alias(in, n_in, o, n_out)) return VLPET_E_ALIAS;
+    HyperBwdArgs a{};
+    for (int s = 0; s < S; ++s) a.m[s] = {G[s], dG[s], dg[s], n[s], blk0[s]};
+    for (int k = 0; k < S * E; ++k) a.dout[k] = dout[k];
+    a.e = e; a.de = de; a.ws = reinterpret_cast<float*>(workspace); a.S = S; a.E = E; a.P = P;
+    return herr(launch_hyper_gen_bwd(a, (int)blocks, param_dtype == VLPET_F32, (hipStream_t)stream));
 }

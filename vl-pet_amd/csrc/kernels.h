@@ -512,3 +512,33 @@ struct PhmArgs {
 int64_t phm_layer_tiles(int in, int out, int n);     // workgroups of one layer
 hipError_t launch_phm_expand_fwd(const PhmArgs& a, int param_fp32, hipStream_t stream);
 hipError_t launch_phm_expand_bwd(const PhmArgs& a, int param_fp32, hipStream_t stream);     // two launches
+
+// Hyperformer's weight generator of one stack: S linear maps on the same E embedding rows, and its backward (hyper.hip)
+constexpr int HYP_MAX_S = 16, HYP_MAX_E = 64, HYP_MAX_P = 64, HYP_MAX_ROWPTRS = 256, HYP_ROWS = 256;
+struct HyperFwdMap {
+    const void* G;          // [n, P] parameter dtype
+    const void* g;          // [n] parameter dtype
+    void* out;              // [E, n] parameter dtype (written)
+    int n, blk0;            // blk0: the first workgroup of this map's row slabs
+};
+struct HyperFwdArgs {
+    HyperFwdMap m[HYP_MAX_S];
+    const float* e;         // [E, P] fp32
+    int S, E, P;
+};
+struct HyperBwdMap {
+    const void* G;
+    float* dG;              // [n, P] fp32 (written)
+    float* dg;              // [n] fp32 (written)
+    int n, blk0;
+};
+struct HyperBwdArgs {
+    HyperBwdMap m[HYP_MAX_S];
+    const float* dout[HYP_MAX_ROWPTRS];      // [s E + l]: [n_s] fp32 or nullptr (zeros)
+    const float* e;
+    float* de;              // [E, P] fp32 (written by the second launch)
+    float* ws;              // [workgroups][E, P] fp32
+    int S, E, P;
+};
+hipError_t launch_hyper_gen_fwd(const HyperFwdArgs& a, int blocks, int param_fp32, hipStream_t stream);
+hipError_t launch_hyper_gen_bwd(const HyperBwdArgs& a, int blocks, int param_fp32, hipStream_t stream);     // two launches

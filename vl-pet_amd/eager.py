@@ -47,6 +47,13 @@ def phm_adapter(x: torch.Tensor, rule_d, W_d, b_d, rule_u, W_u, b_u, act, keep_z
     return phm_linear(z, rule_u, W_u, b_u)
 
 
+def hyper_generate(maps, e: torch.Tensor):
+    """``rows[s][l] = G_s e[l] + g_s`` for ``maps`` = [(G_s [n_s, P], g_s [n_s])] and the E rows of ``e`` [E, P]: every layer's call of
+    every weight / bias generator of a stack's hyper-network (adapters/adapter_hypernetwork.py:43-51: one nn.Linear per generator on one
+    layer's embedding, then a view) as one F.linear per generator on all layers' embeddings."""
+    return [list(F.linear(e.to(G.dtype), G, g).unbind(0)) for G, g in maps]
+
+
 def adapter_gate(x1: Optional[torch.Tensor], x2: torch.Tensor, down_ws: Sequence[torch.Tensor], down_bs: Sequence[torch.Tensor],
                  up_w: torch.Tensor, up_b: torch.Tensor, gate_params, act, gate_act, mode: str,
                  delta_scale: float = 1.0, x2_scale: float = 1.0, gate_scale: float = 1.0) -> torch.Tensor:

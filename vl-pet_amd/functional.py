@@ -1034,3 +1034,112 @@ def phm_expand_pair(rule_d, W_d, rule_u, W_u, n: int):
     [n, d / n, r / n], W_u [n, r / n, d / n]; one dtype, fp32 or bf16), differentiable in all four.  They go to ``parallel_adapter`` /
     ``adapter_gate`` as ``wd`` / ``wu``.  A rule shared by both layers is the same tensor passed twice."""
     return _PhmExpandPairFn.apply(rule_d, W_d, rule_u, W_u, n)
+
+
+# ---- Hyperformer: the adapter weights of every layer of one stack, generated by csrc/hyper.hip
+HYPER_MAX_MAPS, HYPER_MAX_ROWS, HYPER_MAX_DIM, HYPER_MAX_ROW_POINTERS = 16, 64, 64, 256      # include/vlpet_hip.h; beyond: eager.hyper_generate
+HYPER_CALLS = 0            # generator launches issued (tests assert on it; a replayed graph does not count)
+
+
+def hyper_applies(n_maps: int, n_rows: int, dim: int, dtype=torch.float32) -> bool:
+    """whether the generator kernels take S = n_maps linear maps on E = n_rows embedding rows of width P = dim in ``dtype``"""
+    return (1 <= n_maps <= HYPER_MAX_MAPS and 1 <= n_rows <= HYPER_MAX_ROWS and 1 <= dim <= HYPER_MAX_DIM
+            and n_maps * n_rows <= HYPER_MAX_ROW_POINTERS and dtype in (torch.float32, torch.bfloat16))
+
+
+def _ptr_table(ptrs):
+    return (ctypes.c_void_p * len(ptrs))(*ptrs)
+
+
+def _hyper_check(maps, e):
+    """-> (weights, biases, n) of ``maps`` = [(G_s [n_s, P], g_s [n_s])], detached and contiguous; ``e`` [E, P] fp32"""
+    if not maps:
+        raise RuntimeError("vl-pet_amd: hyper_generate needs at least one (weight, bias) map")
+    Gs, gs = [m[0].detach() for m in maps], [m[1].detach() for m in maps]
+    _need_cuda(e, *Gs, *gs)
+    if e.dim() != 2 or e.dtype != torch.float32:
+        raise RuntimeError(f"vl-pet_amd: hyper_generate takes fp32 embeddings [E, P] (got {tuple(e.shape)}, {e.dtype})")
+    P = e.shape[1]
+    if len({t.dtype for t in Gs + gs}) != 1:
+        raise RuntimeError("vl-pet_amd: mixed parameter dtypes in one hyper-network")
+    for G, g in zip(Gs, gs):
+        if G.dim() != 2 or G.shape[1] != P or tuple(g.shape) != (G.shape[0],):
+            raise RuntimeError(f"vl-pet_amd: generator shapes {tuple(G.shape)}, {tuple(g.shape)} do not map embeddings of width {P}")
+    if not hyper_applies(len(maps), e.shape[0], P, Gs[0].dtype):
+        raise RuntimeError(f"vl-pet_amd: hyper_generate takes up to {HYPER_MAX_MAPS} maps, {HYPER_MAX_ROWS} embedding rows of width <= "
+                           f"{HYPER_MAX_DIM}, maps x rows <= {HYPER_MAX_ROW_POINTERS}, fp32 or bf16 parameters (got {len(maps)} maps, "
+                           f"embeddings {tuple(e.shape)}, {Gs[0].dtype})")
+    Gs = [t if t.is_contiguous() else t.contiguous() for t in Gs]
+    gs = [t if t.is_contiguous() else t.contiguous() for t in gs]
+    return Gs, gs, [int(G.shape[0]) for G in Gs]
+
+
+def hyper_generate_into(maps, e, out=None):
+    """``[out_s [E, n_s]]`` with ``out_s[l] = G_s e[l] + g_s`` for every map of ``maps`` = [(G_s [n_s, P], g_s [n_s])], in the
+    parameters' dtype: one launch, no autograd.  ``out``: an earlier result of the same geometry to refresh IN PLACE (its buffers may
+    be baked into a captured graph, as for ``pack_pair(out=)``)."""
+    global HYPER_CALLS
+    lib = _lib.load()
+    Gs, gs, n = _hyper_check(maps, e)
+    ed = e.detach()
+    ed = ed if ed.is_contiguous() else ed.contiguous()
+    E, P = ed.shape
+    ok = out is not None and len(out) == len(n) and all(
+        o.shape == (E, k) and o.dtype == Gs[0].dtype and o.device == Gs[0].device and o.is_contiguous() for o, k in zip(out, n))
+    outs = list(out) if ok else [torch.empty(E, k, dtype=Gs[0].dtype, device=Gs[0].device) for k in n]
+    tabs = (_ptr_table([t.data_ptr() for t in Gs]), _ptr_table([t.data_ptr() for t in gs]), (ctypes.c_int * len(n))(*n),
+            _ptr_table([t.data_ptr() for t in outs]))
+    rc = _timed("hyper_fwd", sum(n), lambda: lib.vlpet_hyper_gen_fwd(len(n), tabs[0], tabs[1], tabs[2], ed.data_ptr(), E, P, tabs[3],
+                                                                     _param_dtype(Gs[0]), _stream()))
+    _lib.check(rc, "vlpet_hyper_gen_fwd")
+    HYPER_CALLS += 1
+    return outs
+
+
+class _HyperGenerateFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, e, *flat):
+        maps = list(zip(flat[0::2], flat[1::2]))
+        ctx.save_for_backward(e, *flat)
+        outs = hyper_generate_into(maps, e)
+        # one output per map and row, so that a row nobody uses costs the backward nothing (its gradient arrives as None)
+        return tuple(o[l] for o in outs for l in range(o.shape[0]))
+
+    @staticmethod
+    def backward(ctx, *douts):
+        lib = _lib.load()
+        e, *flat = ctx.saved_tensors
+        maps = list(zip(flat[0::2], flat[1::2]))
+        Gs, _, n = _hyper_check(maps, e)
+        ed = e.detach()
+        ed = ed if ed.is_contiguous() else ed.contiguous()
+        E, P = ed.shape
+        # K2 / K1 hand the gradients of non-leaf weights back as fresh fp32 tensors (grad_slot finds no sink); an unused row has none
+        rows = [None if g is None else g.detach().reshape(-1).float().contiguous() for g in douts]
+        dG = [grad_slot(G, (k, P)) for (G, _), k in zip(maps, n)]
+        dg = [grad_slot(g, (k,)) for (_, g), k in zip(maps, n)]
+        de = torch.empty(E, P, dtype=torch.float32, device=ed.device)
+        n_tab = (ctypes.c_int * len(n))(*n)
+        nws = lib.vlpet_hyper_gen_workspace_bytes(len(n), n_tab, E, P)
+        ws = torch.empty(nws, dtype=torch.uint8, device=ed.device)
+        tabs = (_ptr_table([_ptr(t) for t in rows]), _ptr_table([t.data_ptr() for t in Gs]), _ptr_table([s.ptr for s in dG]),
+                _ptr_table([s.ptr for s in dg]))
+        rc = _timed("hyper_bwd", sum(n), lambda: lib.vlpet_hyper_gen_bwd(len(n), tabs[0], tabs[1], n_tab, ed.data_ptr(), E, P, tabs[2],
+                                                                         tabs[3], de.data_ptr(), ws.data_ptr(), nws,
+                                                                         _param_dtype(Gs[0]), _stream()))
+        _lib.check(rc, "vlpet_hyper_gen_bwd")
+        grads = []
+        for a, b in zip(dG, dg):
+            grads += [a.finish(), b.finish()]
+        return (de, *grads)
+
+
+def hyper_generate(maps, e):
+    """Hyperformer's weight generator for one stack: ``maps`` = [(G_s [n_s, P], g_s [n_s])] (the ``.0`` Linears of the weight and bias
+    generators, one dtype, fp32 or bf16), ``e`` [E, P] fp32 (the layers' projected embeddings).  Returns ``rows[s][l]`` [n_s] =
+    ``G_s e[l] + g_s`` in the parameters' dtype: one launch for all maps and rows, differentiable in every G_s, g_s and in e (two
+    launches).  Row l of a weight generator, viewed [r, d] / [d, r], goes to ``parallel_adapter`` / ``adapter_gate`` as ``wd`` / ``wu``."""
+    flat = [t for m in maps for t in m[:2]]
+    E = e.shape[0]
+    out = _HyperGenerateFn.apply(e, *flat)
+    return [list(out[s * E:(s + 1) * E]) for s in range(len(maps))]

@@ -31,12 +31,12 @@ from .. import attention as A
 from .. import decode as D
 from .. import functional as VF
 from .. import adapter_tail as AT
-from ..adapters import AdapterController
+from ..adapters import AdapterController, MetaLayersAdapterController, TaskEmbeddingController
 from ..encoder_pet import apply_pet, build_pet, has_pet
 from ..lora import LoRALinearController, LoraConfig
 from ..visual import Downsample, LowRankVisualEmbedding, VisualEmbedding
 from ..prompt import PromptController
-from .common import (COMPACTER_DEFAULTS, PROMPT_DEFAULTS, check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail,
+from .common import (COMPACTER_DEFAULTS, HYPERFORMER_DEFAULTS, PROMPT_DEFAULTS, block_adapters, fused_generated_tail, hyperformer, new_hyper_net, check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail,
                      install_shared_phm_rule, is_key_mask, make_adapter_config, make_prompt_config, sequential_adapters, shift_right, unpack_vis_inputs,
                      value_parallel_adapter)
 
@@ -75,7 +75,7 @@ def vlpet_config(**over) -> SimpleNamespace:
         use_lora=False, lora_dim=4, lora_alpha=32, lora_dropout=0.1, use_single_lora=False, reduction_factor=8,
         use_encoder_multihead_up_zero_init=False, use_encoder_gating_large_x_lowrank_up_zero_init=False,
         use_decoder_enc_vpa_up_zero_init=False, freeze_vis_emb=False,
-        **COMPACTER_DEFAULTS, **PROMPT_DEFAULTS,
+        **COMPACTER_DEFAULTS, **PROMPT_DEFAULTS, **HYPERFORMER_DEFAULTS,
     )
     for k, v in over.items():
         if not hasattr(c, k):
@@ -85,7 +85,7 @@ def vlpet_config(**over) -> SimpleNamespace:
     task_list = [t for t in c.tasks.replace(" ", ",").split(",") if t]
     c.task_list = task_list
     c.encoder_prompt_config = make_prompt_config(c, task_list)
-    if c.use_adapter or c.use_compacter or c.use_decoder_enc_attn_value_parallel_adapter_down_dim:
+    if c.use_adapter or c.use_compacter or c.use_hyperformer or c.use_decoder_enc_attn_value_parallel_adapter_down_dim:
         c.adapter_config = make_adapter_config(c, task_list)
     else:
         c.adapter_config = None
@@ -137,6 +137,14 @@ def _adapter_then_tail(ctl, task, residual, h, norm, p, training, gemm_link=None
         scale = float(ctl.config.scaling_factor) if ctl.config.use_scaling_factor else 1.0
         return AT.adapter_tail(h, residual, *ad.tail_weights(), norm, scale)
     return _tail_linked(residual, ctl(h, task), norm, p, training, gemm_link)
+
+
+def _generated_then_tail(meta, w, residual, h, norm, p, training, gemm_link=None):
+    """``_adapter_then_tail`` for Hyperformer: the adapter's weights ``w`` (adapters.AdapterWeights) were generated by the stack's
+    hyper-network -- my_transformers/modeling_bart.py:1253-1254, 1369-1370 (encoder), :1674-1675, 1738-1739, 1773-1774 (decoder)"""
+    if fused_generated_tail(FUSE_ADAPTER_TAIL, meta, w, h, residual, norm, p, training):
+        return AT.adapter_tail(h, residual, *w.tail_weights(), norm, 1.0)
+    return _tail_linked(residual, meta.fused(h, h, w), norm, p, training, gemm_link)
 
 
 # The same hand-over one op further: the input of a sublayer is also the input of its first frozen projection (q|k|v, q_proj,
@@ -411,17 +419,21 @@ class BartEncoderLayer(nn.Module):
         if sequential_adapters(config, "encoder"):
             self.attn_adapter = AdapterController(config.adapter_config)
             self.ff_adapter = AdapterController(config.adapter_config)
+        self.adapter_hypernet = MetaLayersAdapterController(config.adapter_config) if hyperformer(config) else None      # (:949-951)
         # the reference's BART encoder layer has no adapter / x2 scaling (my_transformers/modeling_bart.py:1147-1155 is a plain
         # h + up(...)); only the T5 layers read those flags (my_transformers/modeling_t5.py:373-377, 789-793)
         self.pet_config = copy.copy(config)
         self.pet_config.use_encoder_adapter_scaling = False
         self.pet_config.use_encoder_x2_scaling = False
 
-    def forward(self, hidden, attn_mask=None, task=None):
+    def forward(self, hidden, attn_mask=None, task=None, block_adapters=None):
         residual = hidden
         gl = _new_gemm_link(hidden)
         h = self.self_attn(hidden, attn_mask=attn_mask, task=task, in_link=gl)
-        if self.attn_adapter is not None:                                           # K2 + K5 | the fused launch
+        if self.adapter_hypernet is not None:                                       # generated adapter: K2 + K5 | the fused launch
+            hidden = _generated_then_tail(self.adapter_hypernet, block_adapters["self_attention"], residual, h, self.self_attn_layer_norm,
+                                          self.dropout, self.training, gl)
+        elif self.attn_adapter is not None:                                           # K2 + K5 | the fused launch
             hidden = _adapter_then_tail(self.attn_adapter, task, residual, h, self.self_attn_layer_norm, self.dropout, self.training, gl)
         elif has_pet(self, "attn"):                                                 # K1 + K5
             hidden = _pet_then_tail(self, "attn", residual, h, self.self_attn_layer_norm, self.dropout, self.training,
@@ -432,6 +444,9 @@ class BartEncoderLayer(nn.Module):
         gl = _new_gemm_link(hidden)
         h = ffn_activation(_first_linear(self.fc1, hidden, gl), "gelu", self.activation_dropout, self.training)
         h = _linear(self.fc2, h)
+        if self.adapter_hypernet is not None:
+            return _generated_then_tail(self.adapter_hypernet, block_adapters["feed_forward"], residual, h, self.final_layer_norm,
+                                        self.dropout, self.training, gl)
         if self.ff_adapter is not None:
             return _adapter_then_tail(self.ff_adapter, task, residual, h, self.final_layer_norm, self.dropout, self.training, gl)
         if has_pet(self, "ff"):                                                     # K1 + K5
@@ -462,40 +477,53 @@ class BartDecoderLayer(nn.Module):
             if config.add_adapter_cross_attn:
                 self.enc_attn_adapter = AdapterController(config.adapter_config)
             self.ff_adapter = AdapterController(config.adapter_config)
+        self.adapter_hypernet = MetaLayersAdapterController(config.adapter_config) if hyperformer(config) else None      # (:1563-1565)
+        self.add_adapter_cross_attn = bool(config.add_adapter_cross_attn)
 
-    def _tail(self, ctl, task, residual, h, norm, gl=None):
-        """the sublayer's tail: behind its sequential adapter when it has one"""
+    def _tail(self, ctl, task, residual, h, norm, gl=None, w=None):
+        """the sublayer's tail: behind its sequential adapter when it has one; ``w``: behind the generated adapter (Hyperformer)"""
+        if w is not None:
+            return _generated_then_tail(self.adapter_hypernet, w, residual, h, norm, self.dropout, self.training, gl)
         if ctl is not None:
             return _adapter_then_tail(ctl, task, residual, h, norm, self.dropout, self.training, gl)
         return _tail_linked(residual, h, norm, self.dropout, self.training, gl)                            # K5
 
-    def forward(self, hidden, enc, enc_mask=None, task=None, k_pre=None):
+    def _generated(self, block_adapters):
+        """(self-attention, cross-attention, feed-forward) generated adapters of this layer, None where there is none"""
+        if self.adapter_hypernet is None:
+            return None, None, None
+        b = block_adapters
+        return b["self_attention"], b["cross_attention"] if self.add_adapter_cross_attn else None, b["feed_forward"]
+
+    def forward(self, hidden, enc, enc_mask=None, task=None, k_pre=None, block_adapters=None):
+        ws, wx, wf = self._generated(block_adapters)
         residual = hidden
         gl = _new_gemm_link(hidden)
         h = self.self_attn(hidden, causal=True, task=task, in_link=gl)
-        hidden = self._tail(self.self_attn_adapter, task, residual, h, self.self_attn_layer_norm, gl)
+        hidden = self._tail(self.self_attn_adapter, task, residual, h, self.self_attn_layer_norm, gl, ws)
         residual = hidden
         gl = _new_gemm_link(hidden)
         h = self.encoder_attn(hidden, kv=enc, attn_mask=enc_mask, task=task, in_link=gl, k_pre=k_pre)      # K2 inside
-        hidden = self._tail(self.enc_attn_adapter, task, residual, h, self.encoder_attn_layer_norm, gl)
+        hidden = self._tail(self.enc_attn_adapter, task, residual, h, self.encoder_attn_layer_norm, gl, wx)
         residual = hidden
         gl = _new_gemm_link(hidden)
         h = ffn_activation(_first_linear(self.fc1, hidden, gl), "gelu", self.activation_dropout, self.training)
         h = _linear(self.fc2, h)
-        return self._tail(self.ff_adapter, task, residual, h, self.final_layer_norm, gl)
+        return self._tail(self.ff_adapter, task, residual, h, self.final_layer_norm, gl, wf)
 
 
-    def step(self, x, cache, pos, state, task=None):
+    def step(self, x, cache, pos, state, task=None, block_adapters=None):
         """generate(): the token x [B, 1, d] at position ``pos``; ``cache`` = this layer's (self k, self v, cross k, cross v) of
         ``state`` (decode.DecodeState)"""
         ks, vs, kx, vx = cache
+        ws, wx, wf = self._generated(block_adapters)
         kr, pd = state.key_rows, state.pos_dev
         h = self.self_attn.step_self(x, ks, vs, pos, task, key_rows=kr if kr is None or pd is not None else kr[pos & 1], pos_dev=pd)
-        x = self._tail(self.self_attn_adapter, task, x, h, self.self_attn_layer_norm)                       # K5 | adapter + K5 in one launch
+        x = self._tail(self.self_attn_adapter, task, x, h, self.self_attn_layer_norm, None, ws)             # K5 | adapter + K5 in one launch
         h = self.encoder_attn.step_cross(x, kx, vx, state.key_mask, task, group=state.group)
-        x = self._tail(self.enc_attn_adapter, task, x, h, self.encoder_attn_layer_norm)
+        x = self._tail(self.enc_attn_adapter, task, x, h, self.encoder_attn_layer_norm, None, wx)
         h = ffn_activation(_linear(self.fc1, x), "gelu", self.activation_dropout, self.training)
-        return self._tail(self.ff_adapter, task, x, _linear(self.fc2, h), self.final_layer_norm)
+        return self._tail(self.ff_adapter, task, x, _linear(self.fc2, h), self.final_layer_norm, None, wf)
 
 
 class LearnedPositionalEmbedding(nn.Embedding):
@@ -508,14 +536,30 @@ class LearnedPositionalEmbedding(nn.Embedding):
         return super().forward(torch.arange(2, L + 2, device=device))
 
 
+def _install_hyper_net(stack, config, task_embed, num_layers, include_cross_attention):
+    """my_transformers/modeling_bart.py:1978-1987, 2144-2153: the shared TaskEmbeddingController under the stack's own name too, and the
+    stack's hyper-network, registered right behind ``embed_tokens`` as there; without the flag no attribute and no state-dict key"""
+    if hyperformer(config):
+        stack.task_embed = task_embed
+        stack.adapter_layers_hyper_net = new_hyper_net(config, num_layers, include_cross_attention)
+
+
+def _stack_block_adapters(stack, task, x):
+    """every layer's generated adapters for ``task`` (one generator launch), or a list of None without Hyperformer"""
+    if getattr(stack, "adapter_layers_hyper_net", None) is None:
+        return [None] * len(stack.layers)
+    return block_adapters(stack.adapter_layers_hyper_net, stack.task_embed, task, x)
+
+
 class JointEncoder(nn.Module):
-    def __init__(self, config, embed_tokens):
+    def __init__(self, config, embed_tokens, task_embed=None):
         super().__init__()
         self.config = config
         d = config.d_model
         self.dropout = config.dropout
         self.embed_scale = math.sqrt(d) if config.scale_embedding else 1.0
         self.embed_tokens = embed_tokens
+        _install_hyper_net(self, config, task_embed, config.encoder_layers, False)
         self.embed_positions = LearnedPositionalEmbedding(config.max_position_embeddings, d)
         self.layers = nn.ModuleList([BartEncoderLayer(config) for _ in range(config.encoder_layers)])
         self.layernorm_embedding = HostLayerNorm(d)
@@ -552,8 +596,8 @@ class JointEncoder(nn.Module):
             full = torch.cat([attention_mask.bool(), torch.ones(B, vis.shape[1], dtype=torch.bool,
                                                                 device=x.device)], dim=1)
             mask = full[:, None, None, :]
-        for layer in self.layers:
-            x = layer(x, mask, task)
+        for layer, ba in zip(self.layers, _stack_block_adapters(self, task, x)):
+            x = layer(x, mask, task, ba)
         return x, mask
 
     def _forward_prompted(self, input_ids, vis_inputs, attention_mask, task, no_padding):
@@ -577,18 +621,19 @@ class JointEncoder(nn.Module):
         if attention_mask is not None:
             ones = lambda n: torch.ones(B, n, dtype=torch.bool, device=x.device)
             mask = torch.cat([ones(P), attention_mask.bool(), ones(vis.shape[1])], dim=1)[:, None, None, :]
-        for layer in self.layers:
-            x = layer(x, mask, task)
+        for layer, ba in zip(self.layers, _stack_block_adapters(self, task, x)):
+            x = layer(x, mask, task, ba)
         return x, mask
 
 
 class BartDecoder(nn.Module):
-    def __init__(self, config, embed_tokens):
+    def __init__(self, config, embed_tokens, task_embed=None):
         super().__init__()
         d = config.d_model
         self.dropout = config.dropout
         self.embed_scale = math.sqrt(d) if config.scale_embedding else 1.0
         self.embed_tokens = embed_tokens
+        _install_hyper_net(self, config, task_embed, config.decoder_layers, True)
         self.embed_positions = LearnedPositionalEmbedding(config.max_position_embeddings, d)
         self.layers = nn.ModuleList([BartDecoderLayer(config) for _ in range(config.decoder_layers)])
         self.layernorm_embedding = HostLayerNorm(d)
@@ -601,8 +646,10 @@ class BartDecoder(nn.Module):
         fused_keys = self._cross_keys_ok(enc, enc_mask)
         encs = VF.fanout(enc, n + (1 if fused_keys else 0))        # one gradient sum for the encoder output instead of autograd's pairwise adds
         ks = self._cross_keys(encs[n]) if fused_keys else None
+        bas = _stack_block_adapters(self, task, x)
         for i, (layer, e) in enumerate(zip(self.layers, encs)):
-            x = layer(x, e, enc_mask, task, k_pre=None if ks is None else (ks[0][i], None if ks[1] is None else (ks[1], i)))
+            x = layer(x, e, enc_mask, task, k_pre=None if ks is None else (ks[0][i], None if ks[1] is None else (ks[1], i)),
+                      block_adapters=bas[i])
         return x
 
     def _cross_keys_ok(self, enc, enc_mask) -> bool:
@@ -635,7 +682,12 @@ class BartDecoder(nn.Module):
         vs = [l.encoder_attn.cross_values(enc, task) for l in self.layers]
         return D.new_decode_state(enc, enc.shape[2], max_length, ks, vs, key_mask, num_beams)
 
-    def step(self, tok, pos, state, task=None):
+    def block_adapters(self, task, x):
+        """generate(): every layer's generated adapters for ``task``, once per call -- under no_grad they are the controller's cached
+        buffers of that task, refreshed in place, so a captured step keeps reading valid memory"""
+        return _stack_block_adapters(self, task, x)
+
+    def step(self, tok, pos, state, task=None, block_adapters=None):
         """generate(): hidden state [B, d] of the tokens ``tok`` [B] at position ``pos`` (learned position pos + 2); with
         ``state.pos_dev`` the position is the device word's (a gather) and ``pos`` is not read"""
         if state.pos_dev is not None:
@@ -644,8 +696,9 @@ class BartDecoder(nn.Module):
             p = self.embed_positions.weight[pos + 2]
         x = self.embed_tokens(tok)[:, None] * self.embed_scale + p
         x = F.dropout(self.layernorm_embedding(x), p=self.dropout, training=self.training)
-        for layer, c in zip(self.layers, state.layers):
-            x = layer.step(x, c, pos, state, task)
+        bas = block_adapters if block_adapters is not None else [None] * len(self.layers)
+        for layer, c, ba in zip(self.layers, state.layers, bas):
+            x = layer.step(x, c, pos, state, task, ba)
         return x[:, 0]
 
 
@@ -653,8 +706,12 @@ class VLBartModel(nn.Module):
     def __init__(self, config):
         super().__init__()
         self.shared = nn.Embedding(config.vocab_size, config.d_model, padding_idx=config.pad_token_id)
-        self.encoder = JointEncoder(config, self.shared)
-        self.decoder = BartDecoder(config, self.shared)
+        # src/modeling_bart.py:1303-1313: ONE TaskEmbeddingController, registered here and under both stacks
+        task_embed = None           # (without the flag no attribute at all: the module tree of every other flag set is unchanged)
+        if hyperformer(config):
+            self.shared_task_embed = task_embed = TaskEmbeddingController(config.adapter_config)
+        self.encoder = JointEncoder(config, self.shared, task_embed)
+        self.decoder = BartDecoder(config, self.shared, task_embed)
 
 
 shift_tokens_right = shift_right
@@ -726,13 +783,14 @@ class VLBart(nn.Module):
             key_mask = None if mask is None else mask[:, 0, 0, :].contiguous()
             dec = self.model.decoder
             state = dec.init_cache(enc, key_mask, task, max_length, num_beams=int(num_beams))
+            bas = dec.block_adapters(task, enc)
             V = self.model.shared.weight.shape[0]
             head = _padded_head(self.model.shared.weight, enc.dtype)
             bias = self._logits_bias()
 
             def make_step(st):
                 def step(tok, pos):
-                    logits = F.linear(dec.step(tok, pos, st, task), head)
+                    logits = F.linear(dec.step(tok, pos, st, task, bas), head)
                     if bias is not None:
                         logits[:, :V] += bias[0].to(logits.dtype)
                     return logits

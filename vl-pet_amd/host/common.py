@@ -8,7 +8,7 @@ import copy
 import torch
 
 from .. import functional as VF
-from ..adapters import AdapterConfig, AdapterController
+from ..adapters import AdapterConfig, AdapterController, MetaAdapterConfig
 from ..prompt import EncoderPromptConfig
 
 
@@ -51,6 +51,31 @@ def sequential_adapters(config, side: str) -> bool:
     return bool(config.use_adapter or getattr(config, "use_compacter", False)) and not getattr(config, f"no_{side}_adapter")
 
 
+# the Hyperformer flags of both hosts (param.py:147-157; scripts/image-text/hyperformer.sh: --use_hyperformer --unique_hyper_net
+# --projected_task_embedding_dim 8 --reduction_factor 8); -1 = the config class's default (64)
+HYPERFORMER_DEFAULTS = dict(use_hyperformer=False, unique_hyper_net=False, efficient_unique_hyper_net=False, projected_task_embedding_dim=-1)
+
+
+def hyperformer(config) -> bool:
+    return bool(getattr(config, "use_hyperformer", False))
+
+
+def new_hyper_net(config, num_layers: int, include_cross_attention: bool):
+    """the stack's controller as the reference picks it (my_transformers/modeling_bart.py:1980-1987, 2146-2153: the efficient form wins
+    when both flags are set)"""
+    from ..adapters import AdapterLayersHyperNetController, AdapterLayersOneHyperNetController
+    ac = config.adapter_config
+    cls = AdapterLayersOneHyperNetController if ac.efficient_unique_hyper_net else AdapterLayersHyperNetController
+    return cls(ac, num_layers, include_cross_attention)
+
+
+def block_adapters(hyper_net, task_embed, task, x):
+    """every layer's generated adapters of one stack for ``task``: a list over layers of {block: AdapterWeights}, packed for the dtype of
+    the activations ``x`` on the GPU -- ONE generator launch (none on a no_grad cache hit)"""
+    io = VF._io_dtype(x) if x.is_cuda and x.dtype in (torch.float32, torch.bfloat16) else None
+    return hyper_net.generate(task_embed(task), task=task, io_dtype=io)
+
+
 # the Compacter flags of both hosts (param.py:148-170, defaults as there; scripts/*/single_compacter.sh sets division 2, no shared rule,
 # no factorization)
 COMPACTER_DEFAULTS = dict(use_compacter=False, hypercomplex_division=4, phm_rank=1, shared_phm_rule=True, factorized_phm=True,
@@ -77,6 +102,14 @@ def make_prompt_config(c, task_list):
 
 def make_adapter_config(c, task_list) -> AdapterConfig:
     """the ``adapter_config`` of a host config namespace (trainer_base.py:141-178); with ``use_compacter`` the hypercomplex fields"""
+    if hyperformer(c):          # trainer_base.py:127-128, 143-146, 165-166: the MetaAdapterConfig with its class defaults
+        ac = MetaAdapterConfig(tasks=task_list, input_dim=c.d_model, d_model=c.d_model, use_single_adapter=c.use_single_adapter,
+                               reduction_factor=c.reduction_factor, use_adapter_down_dim=bool(c.use_adapter_down_dim),
+                               adapter_down_dim=c.adapter_down_dim, unique_hyper_net=bool(c.unique_hyper_net),
+                               efficient_unique_hyper_net=bool(c.efficient_unique_hyper_net))
+        if int(c.projected_task_embedding_dim) != -1:
+            ac.projected_task_embedding_dim = int(c.projected_task_embedding_dim)
+        return ac
     ac = AdapterConfig(tasks=task_list, input_dim=c.d_model, d_model=c.d_model, use_single_adapter=c.use_single_adapter,
                        reduction_factor=c.reduction_factor, use_adapter_down_dim=bool(c.use_adapter_down_dim),
                        adapter_down_dim=c.adapter_down_dim)
@@ -115,8 +148,17 @@ def check_sequential_adapter_flags(config) -> None:
     """The launch scripts never combine sequential encoder adapters with the multi-head adapter (K1) or a gate, nor sequential decoder
     adapters with the value-parallel adapter; the reference resolves such a mix by the order of its if / elif chains.  Refused here
     rather than guessed.  More than one adapter kind at once is refused as there (trainer_base.py:125)."""
-    if config.use_adapter and getattr(config, "use_compacter", False):
-        raise ValueError("use_adapter and use_compacter: at most one kind of adapters")
+    kinds = [f for f in ("use_hyperformer", "use_adapter", "use_compacter") if getattr(config, f, False)]
+    if len(kinds) > 1:
+        raise ValueError(" and ".join(kinds) + ": at most one kind of adapters")
+    if hyperformer(config):
+        if not (config.unique_hyper_net or config.efficient_unique_hyper_net):
+            raise ValueError("use_hyperformer needs unique_hyper_net or efficient_unique_hyper_net (my_transformers/modeling_bart.py:1987)")
+        clash = [f for f in ("use_encoder_adapter_down_multihead", "use_decoder_enc_attn_value_parallel_adapter_down_dim", "use_lora")
+                 + GATE_FLAGS if getattr(config, f, False)]
+        if clash:
+            raise ValueError("use_hyperformer (generated adapters behind every block of both stacks) cannot be combined with "
+                             + ", ".join(clash))
     if sequential_adapters(config, "encoder"):
         clash = [f for f in ("use_encoder_adapter_down_multihead",) + GATE_FLAGS if getattr(config, f, False)]
         if clash:
@@ -155,6 +197,21 @@ def fused_adapter_tail(enabled, ctl, task, h, residual, norm, p, training):
     if M == 0 or M > AT.ADAPTER_TAIL_MAX_ROWS or not AT.applies(M, d, ad.down_sample_size, h.dtype):
         return None
     return ad
+
+
+def fused_generated_tail(enabled, meta, w, h, residual, norm, p, training) -> bool:
+    """``fused_adapter_tail`` for a GENERATED (wd, bd, wu, bu) set (Hyperformer): whether "adapter, then tail" may run as the one fused
+    launch -- switched on, on the GPU, no dropout, no gradient needed, gelu_new without track_z, a shape the kernel takes."""
+    from .. import adapter_tail as AT
+    if not enabled or not h.is_cuda or (training and p > 0) or meta.eager or w.pack is None:
+        return False
+    if torch.is_grad_enabled():
+        ts = [h, residual, *w.tail_weights()] + ([] if norm is None else list(norm.parameters()))
+        if any(t.requires_grad for t in ts):
+            return False
+    d = h.shape[-1]
+    M = h.numel() // d
+    return 0 < M <= AT.ADAPTER_TAIL_MAX_ROWS and bool(AT.applies(M, d, w.down_w.shape[0], h.dtype))
 
 
 def unpack_vis_inputs(vis_inputs, downsample, dtype):

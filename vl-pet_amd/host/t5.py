@@ -24,12 +24,12 @@ from .. import attention as A
 from .. import decode as D
 from .. import functional as VF
 from .. import adapter_tail as AT
-from ..adapters import AdapterController
+from ..adapters import AdapterController, MetaLayersAdapterController, TaskEmbeddingController
 from ..encoder_pet import apply_pet, build_pet, has_pet
 from ..visual import Downsample, T5LayerNorm, VisualEmbedding
 from ..prompt import PromptController
 from .bart import TASKS, _linear
-from .common import (COMPACTER_DEFAULTS, PROMPT_DEFAULTS, check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail,
+from .common import (COMPACTER_DEFAULTS, HYPERFORMER_DEFAULTS, PROMPT_DEFAULTS, block_adapters, fused_generated_tail, hyperformer, new_hyper_net, check_sequential_adapter_flags, derived_weights, eval_no_grad, fused_adapter_tail,
                      install_shared_phm_rule, make_adapter_config, make_prompt_config, sequential_adapters, shift_right, unpack_vis_inputs,
                      value_parallel_adapter)
 
@@ -112,8 +112,18 @@ def _adapter_then_tail(ctl, task, hidden, y, p, training, link, layer):
     return _tail_linked(hidden, ctl(y, task), p, training, link, layer=layer)
 
 
-def _tail_or_adapter(ctl, task, hidden, y, p, training, link, layer):
-    """the sublayer's tail: behind its sequential adapter when it has one"""
+def _generated_then_tail(meta, w, hidden, y, p, training, link, layer):
+    """``_adapter_then_tail`` for Hyperformer: the adapter's weights ``w`` (adapters.AdapterWeights) were generated by the stack's
+    hyper-network -- my_transformers/modeling_t5.py:381-382, 797-798, 888-889"""
+    if fused_generated_tail(FUSE_ADAPTER_TAIL and sublayer_tail is _HIP_SUBLAYER_TAIL, meta, w, y, hidden, None, p, training):
+        return AT.adapter_tail(y, hidden, *w.tail_weights(), None, 1.0)
+    return _tail_linked(hidden, meta.fused(y, y, w), p, training, link, layer=layer)
+
+
+def _tail_or_adapter(ctl, task, hidden, y, p, training, link, layer, w=None):
+    """the sublayer's tail: behind its sequential adapter when it has one; ``w``: behind the generated adapter (Hyperformer)"""
+    if w is not None:
+        return _generated_then_tail(layer.adapter_hypernet, w, hidden, y, p, training, link, layer)
     if ctl is not None:
         return _adapter_then_tail(ctl, task, hidden, y, p, training, link, layer)
     return _tail_linked(hidden, y, p, training, link, layer=layer)             # K5 (+ the next sublayer's norm)
@@ -174,7 +184,7 @@ def vlt5_config(**over) -> SimpleNamespace:
         use_lora=False, reduction_factor=8,
         use_encoder_multihead_up_zero_init=True, use_encoder_gating_large_x_lowrank_up_zero_init=True,
         use_decoder_enc_vpa_up_zero_init=True, freeze_vis_emb=False,
-        **COMPACTER_DEFAULTS, **PROMPT_DEFAULTS,
+        **COMPACTER_DEFAULTS, **PROMPT_DEFAULTS, **HYPERFORMER_DEFAULTS,
     )
     for k, v in over.items():
         if not hasattr(c, k):
@@ -402,6 +412,12 @@ class T5DenseReluDense(nn.Module):
         return _linear(self.wo, h)
 
 
+def _generated(sub, block_adapters, block):
+    """the generated adapter of sublayer module ``sub`` for its ``block`` type, None where it has none (no Hyperformer, or the
+    cross-attention without add_adapter_cross_attn)"""
+    return None if sub.adapter_hypernet is None else block_adapters[block]
+
+
 class T5LayerSelfAttention(nn.Module):
     def __init__(self, config, is_decoder, has_relative_attention_bias):
         super().__init__()
@@ -412,13 +428,14 @@ class T5LayerSelfAttention(nn.Module):
             build_pet(self, config, config.d_model, ("attn",))
         # my_transformers/modeling_t5.py:701-702, 744-745
         self.attn_adapter = AdapterController(config.adapter_config) if sequential_adapters(config, "decoder" if is_decoder else "encoder") else None
+        self.adapter_hypernet = MetaLayersAdapterController(config.adapter_config) if hyperformer(config) else None      # (:749-751)
 
-    def forward(self, hidden, bias, task=None):
+    def forward(self, hidden, bias, task=None, block_adapters=None):
         nl = _new_norm_link(hidden)
         y = self.SelfAttention(_normed(self.layer_norm, hidden, nl), bias)
         if not self.is_decoder and has_pet(self, "attn"):                                 # K1 (x1 = un-normalised stream) + K5
             return _pet_then_tail(self, "attn", hidden, y, None, self.p, self.training, self.config, norm_link=nl)
-        return _tail_or_adapter(self.attn_adapter, task, hidden, y, self.p, self.training, nl, self)
+        return _tail_or_adapter(self.attn_adapter, task, hidden, y, self.p, self.training, nl, self, _generated(self, block_adapters, "self_attention"))
 
 
 class T5LayerCrossAttention(nn.Module):
@@ -431,11 +448,13 @@ class T5LayerCrossAttention(nn.Module):
         # my_transformers/modeling_t5.py:847-850
         self.enc_attn_adapter = (AdapterController(config.adapter_config)
                                  if sequential_adapters(config, "decoder") and config.add_adapter_cross_attn else None)
+        self.adapter_hypernet = (MetaLayersAdapterController(config.adapter_config)
+                                 if hyperformer(config) and config.add_adapter_cross_attn else None)                    # (:852-854)
 
-    def forward(self, hidden, enc, bias, task=None, k_pre=None):
+    def forward(self, hidden, enc, bias, task=None, k_pre=None, block_adapters=None):
         nl = _new_norm_link(hidden)
         y = self.EncDecAttention(_normed(self.layer_norm, hidden, nl), bias, kv=enc, task=task, k_pre=k_pre)
-        return _tail_or_adapter(self.enc_attn_adapter, task, hidden, y, self.p, self.training, nl, self)
+        return _tail_or_adapter(self.enc_attn_adapter, task, hidden, y, self.p, self.training, nl, self, _generated(self, block_adapters, "cross_attention"))
 
 
 class T5LayerFF(nn.Module):
@@ -448,13 +467,14 @@ class T5LayerFF(nn.Module):
             build_pet(self, config, config.d_model, ("ff",))
         # my_transformers/modeling_t5.py:307-308, 350-351
         self.ff_adapter = AdapterController(config.adapter_config) if sequential_adapters(config, "decoder" if is_decoder else "encoder") else None
+        self.adapter_hypernet = MetaLayersAdapterController(config.adapter_config) if hyperformer(config) else None      # (:355-357)
 
-    def forward(self, hidden, task=None):
+    def forward(self, hidden, task=None, block_adapters=None):
         nl = _new_norm_link(hidden)
         y = self.DenseReluDense(_normed(self.layer_norm, hidden, nl))
         if not self.is_decoder and has_pet(self, "ff"):
             return _pet_then_tail(self, "ff", hidden, y, None, self.p, self.training, self.config, norm_link=nl)      # K1 + K5
-        return _tail_or_adapter(self.ff_adapter, task, hidden, y, self.p, self.training, nl, self)
+        return _tail_or_adapter(self.ff_adapter, task, hidden, y, self.p, self.training, nl, self, _generated(self, block_adapters, "feed_forward"))
 
 
 class T5Block(nn.Module):
@@ -467,14 +487,14 @@ class T5Block(nn.Module):
         layers.append(T5LayerFF(config, is_decoder))
         self.layer = nn.ModuleList(layers)
 
-    def forward(self, hidden, self_bias, enc=None, cross_bias=None, task=None, k_pre=None):
-        hidden = self.layer[0](hidden, self_bias, task)
+    def forward(self, hidden, self_bias, enc=None, cross_bias=None, task=None, k_pre=None, block_adapters=None):
+        hidden = self.layer[0](hidden, self_bias, task, block_adapters)
         if self.is_decoder:
-            hidden = self.layer[1](hidden, enc, cross_bias, task, k_pre=k_pre)
-        return self.layer[-1](hidden, task)
+            hidden = self.layer[1](hidden, enc, cross_bias, task, k_pre=k_pre, block_adapters=block_adapters)
+        return self.layer[-1](hidden, task, block_adapters)
 
 
-def _block_step(blk, x, cache, pos, state, bias_row, task=None):
+def _block_step(blk, x, cache, pos, state, bias_row, task=None, block_adapters=None):
     """generate(): one decoder block on the token x [B, 1, d]; ``cache`` = this block's (self k, self v, cross k, cross v) of ``state``
     (decode.DecodeState), ``bias_row`` = row ``pos`` of its bias table.  The tails are forward's (_tail_linked: on the GPU each fused
     with the next sublayer's norm)."""
@@ -483,11 +503,11 @@ def _block_step(blk, x, cache, pos, state, bias_row, task=None):
     kr, pd = state.key_rows, state.pos_dev
     y = sa.SelfAttention.step_self(sa.layer_norm(x), ks, vs, pos, bias_row,
                                    key_rows=kr if kr is None or pd is not None else kr[pos & 1], pos_dev=pd)
-    x = _tail_or_adapter(sa.attn_adapter, task, x, y, sa.p, sa.training, None, sa)
+    x = _tail_or_adapter(sa.attn_adapter, task, x, y, sa.p, sa.training, None, sa, _generated(sa, block_adapters, "self_attention"))
     y = ca.EncDecAttention.step_cross(ca.layer_norm(x), kx, vx, state.key_mask, group=state.group)
-    x = _tail_or_adapter(ca.enc_attn_adapter, task, x, y, ca.p, ca.training, None, ca)
+    x = _tail_or_adapter(ca.enc_attn_adapter, task, x, y, ca.p, ca.training, None, ca, _generated(ca, block_adapters, "cross_attention"))
     y = ff.DenseReluDense(ff.layer_norm(x))
-    return _tail_or_adapter(ff.ff_adapter, task, x, y, ff.p, ff.training, None, ff)
+    return _tail_or_adapter(ff.ff_adapter, task, x, y, ff.p, ff.training, None, ff, _generated(ff, block_adapters, "feed_forward"))
 
 
 def _pad_bias(mask, dtype):
@@ -495,11 +515,28 @@ def _pad_bias(mask, dtype):
     return (1.0 - mask[:, None, None, :].to(torch.float32)) * -10000.0
 
 
+def _install_hyper_net(stack, config, task_embed, num_layers, is_decoder):
+    """my_transformers/modeling_t5.py:1097-1106: the shared TaskEmbeddingController under the stack's own name too, and the stack's
+    hyper-network (with the cross-attention generators in the decoder), registered right behind ``embed_tokens`` as there; without the
+    flag no attribute and no state-dict key"""
+    if hyperformer(config):
+        stack.task_embed = task_embed
+        stack.adapter_layers_hyper_net = new_hyper_net(config, num_layers, is_decoder)
+
+
+def _stack_block_adapters(stack, task, x):
+    """every block's generated adapters for ``task`` (one generator launch), or a list of None without Hyperformer"""
+    if getattr(stack, "adapter_layers_hyper_net", None) is None:
+        return [None] * len(stack.block)
+    return block_adapters(stack.adapter_layers_hyper_net, stack.task_embed, task, x)
+
+
 class JointEncoder(nn.Module):
-    def __init__(self, config, embed_tokens):
+    def __init__(self, config, embed_tokens, task_embed=None):
         super().__init__()
         self.config = config
         self.embed_tokens = embed_tokens
+        _install_hyper_net(self, config, task_embed, config.num_layers, False)
         self.block = nn.ModuleList([T5Block(config, False, i == 0) for i in range(config.num_layers)])
         self.final_layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         _wire_next_norms(self.block, self.final_layer_norm)
@@ -540,17 +577,18 @@ class JointEncoder(nn.Module):
         rel = text_bias.new_zeros(1, text_bias.shape[1], L + V, L + V)
         rel[:, :, :L, :L] = text_bias
         bias = AttnSpec(rel, full, causal=False, rel_trainable=sa0.relative_attention_bias.weight.requires_grad and torch.is_grad_enabled())
-        for blk in self.block:
-            x = blk(x, bias, task=task)
+        for blk, ba in zip(self.block, _stack_block_adapters(self, task, x)):
+            x = blk(x, bias, task=task, block_adapters=ba)
         x = F.dropout(self.final_layer_norm(x), p=self.p, training=self.training)
         return x, full
 
 
 class T5Decoder(nn.Module):
-    def __init__(self, config, embed_tokens):
+    def __init__(self, config, embed_tokens, task_embed=None):
         super().__init__()
         self.config = config
         self.embed_tokens = embed_tokens
+        _install_hyper_net(self, config, task_embed, config.num_decoder_layers, True)
         self.block = nn.ModuleList([T5Block(config, True, i == 0) for i in range(config.num_decoder_layers)])
         self.final_layer_norm = T5LayerNorm(config.d_model, eps=config.layer_norm_epsilon)
         _wire_next_norms(self.block, self.final_layer_norm)
@@ -584,8 +622,10 @@ class T5Decoder(nn.Module):
         fused_keys = self._cross_keys_ok(enc, cross_bias)
         encs = VF.fanout(enc, n + (1 if fused_keys else 0))         # one gradient sum for the encoder output instead of autograd's pairwise adds
         ks = self._cross_keys(encs[n]) if fused_keys else None
+        bas = _stack_block_adapters(self, task, x)
         for i, (blk, e) in enumerate(zip(self.block, encs)):
-            x = blk(x, self_bias, e, cross_bias, task, k_pre=None if ks is None else (ks[0][i], None if ks[1] is None else (ks[1], i)))
+            x = blk(x, self_bias, e, cross_bias, task, k_pre=None if ks is None else (ks[0][i], None if ks[1] is None else (ks[1], i)),
+                    block_adapters=bas[i])
         return F.dropout(self.final_layer_norm(x), p=self.p, training=self.training)
 
 
@@ -603,11 +643,16 @@ class T5Decoder(nn.Module):
         table = sa0.compute_bias(max_length, max_length)[0].permute(1, 0, 2).float().contiguous()        # [H, q, k] -> [q, H, k]
         return D.new_decode_state(enc, sa0.inner, max_length, ks, vs, key_mask, num_beams, bias_table=table)
 
-    def step(self, tok, pos, state, task=None):
+    def block_adapters(self, task, x):
+        """generate(): every block's generated adapters for ``task``, once per call (host/bart.py BartDecoder.block_adapters)"""
+        return _stack_block_adapters(self, task, x)
+
+    def step(self, tok, pos, state, task=None, block_adapters=None):
         x = F.dropout(self.embed_tokens(tok)[:, None], p=self.p, training=self.training)
         bias_row = state.bias_table if state.pos_dev is not None else state.bias_table[pos]    # (the kernel takes row *pos_dev)
-        for blk, c in zip(self.block, state.layers):
-            x = _block_step(blk, x, c, pos, state, bias_row, task)
+        bas = block_adapters if block_adapters is not None else [None] * len(self.block)
+        for blk, c, ba in zip(self.block, state.layers, bas):
+            x = _block_step(blk, x, c, pos, state, bias_row, task, ba)
         return F.dropout(self.final_layer_norm(x), p=self.p, training=self.training)[:, 0]
 
 
@@ -619,8 +664,12 @@ class VLT5(nn.Module):
         super().__init__()
         self.config = config
         self.shared = nn.Embedding(config.vocab_size, config.d_model)
-        self.encoder = JointEncoder(config, self.shared)
-        self.decoder = T5Decoder(config, self.shared)
+        # my_transformers/modeling_t5.py:1651-1666: ONE TaskEmbeddingController, registered here and under both stacks
+        task_embed = None           # (without the flag no attribute at all: the module tree of every other flag set is unchanged)
+        if hyperformer(config):
+            self.shared_task_embed = task_embed = TaskEmbeddingController(config.adapter_config)
+        self.encoder = JointEncoder(config, self.shared, task_embed)
+        self.decoder = T5Decoder(config, self.shared, task_embed)
         install_shared_phm_rule(self, [self.encoder, self.decoder], config.adapter_config)        # (Compacter with shared_phm_rule)
         self.apply(self._init_weights)
         self.register_load_state_dict_post_hook(lambda module, incompatible: VF.invalidate_caches())   # (see host/bart.py)
@@ -665,12 +714,13 @@ class VLT5(nn.Module):
         with eval_no_grad(self):
             enc, keep = self.encoder(input_ids, vis_inputs, attention_mask, task)
             state = self.decoder.init_cache(enc, (keep > 0.5).contiguous(), task, max_length, num_beams=int(num_beams))
+            bas = self.decoder.block_adapters(task, enc)
             V = self.shared.weight.shape[0]
             head = _padded_head(self.shared.weight, enc.dtype)
             scale = cfg.d_model ** -0.5
 
             def make_step(st):
-                return lambda tok, pos: F.linear(self.decoder.step(tok, pos, st, task) * scale, head)
+                return lambda tok, pos: F.linear(self.decoder.step(tok, pos, st, task, bas) * scale, head)
             if graph:
                 gs = D.GenSettings(cfg.decoder_start_token_id, eos, int(pad), int(max_length), int(min_length),
                                    int(no_repeat_ngram_size), int(num_beams), float(length_penalty), bool(early_stopping), False)

@@ -71,8 +71,14 @@ def trainable_names(model: nn.Module, config) -> List[str]:
     if getattr(config, "encoder_prompt_len", 0) > 0 or getattr(config, "decoder_prompt_len", 0) > 0:
         from .prompt import PromptController
         prompt_params = {id(p) for m in model.modules() if isinstance(m, PromptController) for p in m.parameters()}
+    # Hyperformer: every parameter of the TaskEmbeddingController and of both stacks' hyper-network controllers (trainer_base.py:401-405)
+    hyper_params = set()
+    if getattr(config, "use_hyperformer", False):
+        from .adapters import AdapterLayersHyperNetController, AdapterLayersOneHyperNetController, TaskEmbeddingController
+        kinds = (TaskEmbeddingController, AdapterLayersHyperNetController, AdapterLayersOneHyperNetController)
+        hyper_params = {id(p) for m in model.modules() if isinstance(m, kinds) for p in m.parameters()}
     for n, p in model.named_parameters():
-        on = id(p) in norm_params or id(p) in prompt_params
+        on = id(p) in norm_params or id(p) in prompt_params or id(p) in hyper_params
         if not config.freeze_vis_emb and "visual_embedding" in n:
             on = True
         if config.use_lora and ("lora" in n or "bias" in n):
@@ -235,10 +241,10 @@ def _flat_order(named):
 
 def _has_per_task_params(names, params) -> bool:
     """True when some trainable parameter belongs to ONE task (``...adapters.<task>.*`` / ``lora_As.<task>`` /
-    ``prompt_modules.prompts.<task>.*`` entries that are distinct tensors per task).  Shared modules registered under every task key (use_single_adapter /
+    ``prompt_modules.prompts.<task>.*`` / Hyperformer's ``task_to_embeddings.<task>`` entries that are distinct tensors per task).  Shared modules registered under every task key (use_single_adapter /
     use_single_lora, adapters/adapter_controller.py:49-58, lora/controller.py:72-80) are one tensor with one name."""
     import re
-    pat = re.compile(r"(.*\.(?:adapters|lora_As|lora_Bs|prompts))\.([^.]+)(\..*)?$")
+    pat = re.compile(r"(.*\.(?:adapters|lora_As|lora_Bs|prompts|task_to_embeddings))\.([^.]+)(\..*)?$")
     seen = {}
     for n in names:
         m = pat.match(n)
@@ -354,6 +360,15 @@ class FlatGrads:
     def active(self):
         """Per parameter: did it receive a gradient in the current step (meaningful when hooks are registered)."""
         return [e == self.epoch for e in self._ready_epoch]
+
+    def active_indices(self):
+        return [i for i, e in enumerate(self._ready_epoch) if e == self.epoch]
+
+    def mark_active(self, indices):
+        """A replayed step runs no hooks: the parameters its capture saw receive a gradient are the ones every replay of that graph
+        writes (the graph's key holds the task, and the task decides which per-task parameters take part)."""
+        for i in indices:
+            self._ready_epoch[i] = self.epoch
 
     def _make_hook(self, i):
         def hook(param):
@@ -578,7 +593,9 @@ class Trainer:
     (iv) every weight-derived buffer refreshed without the Python forward: the PET fragment packs by ``repack_all(True)`` right
     after the optimizer kernel (into their existing buffers), the epoch-keyed caches (K4 pack, IO-dtype copies of trainable
     weights) by their own rebuild kernels, which are stale at capture time and therefore part of the graph.
-    Not captured: per-task adapters / LoRA (the active parameter set is host state) -- such trainers stay eager."""
+    Per-task parameters (adapters / LoRA / prompts / Hyperformer's task embeddings of one task): the set a step touches follows from the
+    task, which is part of a graph's key; the capture records it, a replay hands it to the optimizer (FlatGrads.mark_active), whose
+    per-parameter step counts stay on the host.  Not captured: weight gradients on a side stream."""
 
     def __init__(self, model: nn.Module, config, lr=1e-3, clip=5.0, total_steps=1000, warmup_ratio=0.1,
                  world_size=1, n_buckets=3, process_group=None, overlap_wgrad=False, force_collectives=False, graph=False,
@@ -622,8 +639,11 @@ class Trainer:
     def enable_graph(self):
         if not self.flat.flat.is_cuda:
             raise RuntimeError("vl-pet_amd: Trainer(graph=True) needs the GPU product path")
-        if self.flat.per_task or overlap_stream_active():
+        if overlap_stream_active():
             return False                 # host-side state decides what a step does: stay eager
+        # (per-task parameters -- adapters / LoRA / prompts / Hyperformer's task embeddings of ONE task: which of them a step touches is
+        # host state too, but it is a function of the task, and the task is part of a graph's key; the capture records the set and every
+        # replay hands it to the optimizer, whose per-parameter step counts and skips stay on the host, outside the graph)
         from . import _lib
         if self.seed_ctr is None:
             self.seed_ctr = torch.zeros(1, dtype=torch.int64, device=self.flat.flat.device)
@@ -763,6 +783,7 @@ class Trainer:
             with torch.cuda.graph(g, pool=self._graph_pool, capture_error_mode="thread_local"):
                 loss = self._fwd_bwd(static).detach()     # (detached: keeping the graph's root would keep its AccumulateGrad nodes, and
                                                           #  their capture stream, alive into later eager steps)
+                active = self.flat.active_indices() if self.flat.per_task else None
                 if self.capture_collectives:              # the buckets left from inside the backward; their joins belong to the graph too
                     self.flat.finish(average=False)
         except Exception as e:      # a model whose step cannot be captured (host sync, data-dependent shape): stay eager, loudly
@@ -778,7 +799,7 @@ class Trainer:
             VF.TIMER = timer
             self.flat.begin_step(zero=False)        # (the capture ran the sinks' host-side bookkeeping, not their kernels)
         self._graph_pool = g.pool()
-        ent = (g, static, loss)
+        ent = (g, static, loss, active)
         self._graphs[key] = ent
         return ent
 
@@ -809,11 +830,13 @@ class Trainer:
                 return self._eager_step_in_graph_mode(batch)
         else:
             self._graphs.move_to_end(key)
-        g, static, loss = ent
+        g, static, loss, active = ent
         for (k, i, src), (_, _, dst) in zip(self._leaves(batch), self._leaves(static)):
             if src.data_ptr() != dst.data_ptr():
                 dst.copy_(src, non_blocking=True)
         g.replay()
+        if active is not None:
+            self.flat.mark_active(active)
         self._finish_step(exchanged=self.capture_collectives)
         return loss.detach().clone()
 
