@@ -480,6 +480,28 @@ int vlpet_act_dropout_fwd(const void* x, void* out, uint8_t* keep_out, int64_t n
                           int io_dtype, vlpet_stream_t stream);
 int vlpet_act_dropout_bwd(const void* dy, const void* x, void* dx, int64_t n, int act, float p, uint64_t seed,
                           int io_dtype, vlpet_stream_t stream);
+/* ---- Bias gradients where the data already is (BitFit: `--unfreeze_bias`, trainer_base.py:469-475 trains every parameter whose name
+ * contains "bias") ------------------------------------------------------------------------------------------------------------
+ * vlpet_colsum_seg: column sums of a STRIDED matrix x [M, n] (IO dtype, row stride ld >= n elements, ld a multiple of 16 bytes) whose
+ * n = n_segments * w columns (1 <= n_segments <= 16, w % 16 == 0, n <= 65,536) are segments of w: segment s is summed over the M rows in
+ * fp32 and OVERWRITES out[s] [w]; out is a HOST array of n_segments device pointers, a NULL entry = segment not wanted (nothing is
+ * written for it; all NULL: no launch).  One call gives the q | k | v bias gradients of a fused projection, or the k_proj bias gradients
+ * of every decoder layer from the shared cross-key gradient, straight into the slots of a flat gradient buffer.
+ * workspace: vlpet_colsum_seg_workspace_bytes(M, n) bytes.  Two launches, no atomics; the order of every sum is a function of (M, n), so
+ * two calls give the same bits.  replaces: autograd's dy.sum(0) per nn.Linear bias (my_transformers/modeling_bart.py:791-811). */
+size_t vlpet_colsum_seg_workspace_bytes(int64_t M, int n);
+int vlpet_colsum_seg(const void* x, int64_t M, int n_segments, int w, int64_t ld, float* const* out, float* workspace,
+                     size_t workspace_bytes, int io_dtype, vlpet_stream_t stream);
+/* vlpet_act_dropout_bwd over [M, n_cols] (n_cols % 8 == 0) that also leaves the column sums of the dx it stores (the fc1 bias gradient,
+ * my_transformers/modeling_bart.py:1264) without a second read of dx: dx is bit for bit what vlpet_act_dropout_bwd writes for
+ * n = M * n_cols and the same act / p / seed (same mask: group = flat element index / 8; the step counter applies), and the values summed
+ * are dx AS STORED, after the rounding to the IO dtype.  Per-workgroup fp32 partials [nb][n_cols] go to `workspace`
+ * (nb <= min(ceil(M / 4), 2048); workspace_bytes >= nb * n_cols * 4 is checked) and *n_partials = nb (optional).  out [n_cols] (fp32,
+ * OVERWRITTEN): when non-NULL the call also launches the reduce; when NULL the caller does (vlpet_sublayer_tail_reduce(workspace, nb,
+ * n_cols / 2, out, out + n_cols / 2) or a vlpet_reduce_batch job of d = n_cols / 2).  No atomics, fixed order. */
+int vlpet_act_dropout_bwd_cols(const void* dy, const void* x, void* dx, int64_t M, int n_cols, int act, float p, uint64_t seed,
+                               float* workspace, size_t workspace_bytes, float* out, int* n_partials, int io_dtype,
+                               vlpet_stream_t stream);
 /* The joint encoder's input assembly: x [B, La + Lv, d] = dropout(cat([a [B, La, d], v [B, Lv, d]], dim = 1), p) in one pass, and its
  * backward dx -> da, dv (either NULL: not wanted) with the mask regenerated from (p, seed) -- instead of a concatenation pass, a dropout
  * pass that also writes a byte mask, a masked-scale pass and one copy per slice of the gradient.

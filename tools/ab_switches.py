@@ -4,7 +4,8 @@ VLPET_AB=1): the product package itself reads nothing from the environment at im
     VLPET_EAGER_FFN_ACT=1, VLPET_EAGER_LM_LOSS=1, VLPET_EAGER_ATTENTION=1, VLPET_EAGER_RMS_NORM=1, VLPET_SPLIT_WIDE=1, VLPET_SDPA=flash|efficient|math, VLPET_NO_DEFER_REDUCES=1,
     VLPET_K4_FORM=gemm|library|fused, VLPET_SAVE_PRENORM=auto|0|1, VLPET_NO_TAIL_NORM_FUSION=1, VLPET_NO_ALIAS_RESIDUAL_GRAD=1,
     VLPET_K1_BWD_FROM_X2=1, VLPET_FINALIZE_LAUNCH=1, VLPET_NO_POS_KERNEL=1, VLPET_NO_FANOUT_SUM=1, VLPET_NO_FUSED_CROSS_KEYS=1, VLPET_NO_CONCAT_DROPOUT=1,
-    VLPET_NO_PREFIX_CONCAT=1, VLPET_LONG_ATTENTION=1, VLPET_LONG_ATTENTION_TRAIN=1, VLPET_FUSE_ADAPTER_TAIL=0|1"""
+    VLPET_NO_PREFIX_CONCAT=1, VLPET_LONG_ATTENTION=1, VLPET_LONG_ATTENTION_TRAIN=1, VLPET_FUSE_ADAPTER_TAIL=0|1,
+    VLPET_NO_BIAS_GRAD_SITES=1"""
 import os
 
 
@@ -54,6 +55,7 @@ def apply():
     import vlpet_amd.act as ACT
     put(ACT, "FUSE_CONCAT_DROPOUT", not on("VLPET_NO_CONCAT_DROPOUT"))          # the joint encoder's cat + dropout as one pass each way | torch.cat + F.dropout
     put(ACT, "FUSE_PREFIX_CONCAT", not on("VLPET_NO_PREFIX_CONCAT"))            # ... with the encoder prompt in front (prompt tuning) | expand + torch.cat + F.dropout
+    put(VF, "FUSE_BIAS_GRAD_SITES", not on("VLPET_NO_BIAS_GRAD_SITES"))         # BitFit: bias gradients summed where the data is (fused q|k|v / cross keys / fc1 + activation) | one vlpet_colsum pair per bias
     put(VF, "FANOUT_SUM", not on("VLPET_NO_FANOUT_SUM"))                     # the encoder output's gradient summed in one launch (vlpet_sum_n) | autograd's pairwise adds
     put(VF, "K1_BWD_FINALIZE_LAUNCH", on("VLPET_FINALIZE_LAUNCH"))              # VLPET_FINALIZE_LAUNCH=1: the gated K1 backward ends in a finalize launch (round 3) instead of the in-launch reduce-scatter
     fat = os.environ.get("VLPET_FUSE_ADAPTER_TAIL")                             # sequential adapter + tail as one launch where it applies (unset: each host's default)

@@ -148,6 +148,10 @@ SIGNATURES = {
     "vlpet_ce_loss_bwd": (c_int, [c_void_p] * 5 + [c_int64, c_int, c_int, c_int, c_void_p]),
     "vlpet_act_dropout_fwd": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_float, c_uint64, c_int, c_void_p]),
     "vlpet_act_dropout_bwd": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_float, c_uint64, c_int, c_void_p]),
+    "vlpet_colsum_seg_workspace_bytes": (c_size_t, [c_int64, c_int]),
+    "vlpet_colsum_seg": (c_int, [c_void_p, c_int64, c_int, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_int, c_void_p]),
+    "vlpet_act_dropout_bwd_cols": (c_int, [c_void_p] * 3 + [c_int64, c_int, c_int, c_float, c_uint64, c_void_p, c_size_t, c_void_p,
+                                           c_void_p, c_int, c_void_p]),
     "vlpet_attn_decode": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_void_p, c_void_p,
                                   c_int64, c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int,
                                   c_int, c_float, c_int, c_void_p]),

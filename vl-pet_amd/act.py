@@ -7,6 +7,8 @@ reference keeps x, act(x) and a byte mask); the mask is a function of (seed, ele
 One 64-bit seed per call from torch's CPU generator, as the sublayer tail does.  No CPU fallback."""
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -64,6 +66,94 @@ def act_dropout(x: torch.Tensor, act: str = "gelu", p: float = 0.0, training: bo
     if seed is None:
         seed = _draw_seed() if pe > 0.0 else 0
     return _ActDropFn.apply(x, ACTS[act], pe, int(seed), bool(return_mask))
+
+
+# ------------------------------------------------------------------------------------------------ fc1 + activation, trainable fc1 bias
+class _LinearActDropFn(torch.autograd.Function):
+    """``dropout(act(x W^T + b), p)`` with a FROZEN weight and a TRAINABLE bias (BitFit): the backward runs the activation backward that
+    also leaves the column partials of its result (vlpet_act_dropout_bwd_cols), reduces them into the bias's slot, then runs the dgrad
+    GEMM onto whatever the sublayer's tail parked (the hand-over of functional._LinearAccFn) -- the [M, ffn] gradient is not read a
+    second time for the bias."""
+
+    @staticmethod
+    def forward(ctx, x, w, b, link, act, p, seed):
+        from . import functional as VF
+        lib = _lib.load()
+        _need_cuda(x)
+        ctx.link = link.arm() if (link is not None and ctx.needs_input_grad[0]) else None
+        pre = torch.nn.functional.linear(x, w, VF.io_view(b, x.dtype).detach()).contiguous()
+        out = torch.empty_like(pre)
+        n, io = pre.numel(), _io_dtype(pre)
+        rc = _timed("ffn_act_fwd", n // pre.shape[-1], lambda: lib.vlpet_act_dropout_fwd(
+            pre.data_ptr(), out.data_ptr(), None, n, act, float(p), seed, io, _stream()))
+        _lib.check(rc, "vlpet_act_dropout_fwd")
+        ctx.save_for_backward(pre, w, b)
+        ctx.cfg = (act, float(p), seed, io)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        from . import functional as VF
+        lib = _lib.load()
+        pre, w, b = ctx.saved_tensors
+        act, p, seed, io = ctx.cfg
+        link, ctx.link = ctx.link, None
+        dy = dout.contiguous()
+        if dy.dtype != pre.dtype:
+            dy = dy.to(pre.dtype)
+        n = pre.shape[-1]
+        M = pre.numel() // n
+        slot = VF.grad_slot(b, (n,))
+        dpre = act_bwd_cols_into(dy, pre, act, p, seed, io, slot)
+        db = slot.finish()
+        dx = None
+        if ctx.needs_input_grad[0]:
+            xshape = (*pre.shape[:-1], w.shape[1])
+            d2 = dpre.view(-1, n)
+            base = link.take(xshape, w.dtype, writable=True) if link is not None else None
+            dx = (d2 @ w if base is None else base.view(-1, w.shape[1]).addmm_(d2, w)).view(xshape)
+        return dx, None, db, None, None, None, None
+
+
+def act_bwd_cols_into(dy: torch.Tensor, pre: torch.Tensor, act: int, p: float, seed: int, io: int, slot) -> torch.Tensor:
+    """-> dpre = dy * mask / (1 - p) * act'(pre) (bit for bit vlpet_act_dropout_bwd's), its column sums into ``slot.t`` [n]: now, or --
+    for a slot of the trainer's flat buffer under DEFER_REDUCES -- with the step's other reductions (functional.flush_reduces)."""
+    from . import functional as VF
+    lib = _lib.load()
+    n = pre.shape[-1]
+    M = pre.numel() // n
+    dpre = torch.empty_like(pre)
+    nb = min((M + 3) // 4, 2048)                    # an upper bound of the partial rows (include/vlpet_hip.h); the call reports the count
+    ws = torch.empty(nb * n, dtype=torch.float32, device=pre.device)
+    got = ctypes.c_int(0)
+    defer = VF.DEFER_REDUCES and slot.sunk
+    rc = _timed("ffn_act_bwd_cols", M, lambda: lib.vlpet_act_dropout_bwd_cols(
+        dy.data_ptr(), pre.data_ptr(), dpre.data_ptr(), M, n, act, p, seed, ws.data_ptr(), ws.numel() * 4,
+        None if defer else slot.ptr, ctypes.addressof(got), io, _stream()))
+    _lib.check(rc, "vlpet_act_dropout_bwd_cols")
+    if defer:
+        tf = slot.t.reshape(-1)
+        VF.reduce_partials(ws, got.value, n // 2, tf[:n // 2], tf[n // 2:], True)
+    VF.BITFIT_CALLS["act"] += 1
+    return dpre
+
+
+def linear_act_dropout_ok(x: torch.Tensor, fc1, act: str) -> bool:
+    from . import functional as VF
+    w, b = fc1.weight, fc1.bias
+    return (VF.FUSE_BIAS_GRAD_SITES and act in ACTS and b is not None and b.requires_grad and not w.requires_grad and x.is_cuda
+            and x.dtype in (torch.bfloat16, torch.float32) and w.shape[0] % 8 == 0 and w.shape[0] % 2 == 0 and x.numel() > 0
+            and torch.is_grad_enabled())
+
+
+def linear_act_dropout(x: torch.Tensor, fc1, act: str = "gelu", p: float = 0.0, training: bool = False, link=None, seed=None):
+    """``dropout(act(fc1(x)), p)`` for an ``nn.Linear`` with a frozen weight and a trainable bias (see _LinearActDropFn); ``link``: the
+    sublayer's hand-over, as for host.bart._first_linear."""
+    pe = float(p) if training else 0.0
+    if seed is None:
+        seed = _draw_seed() if pe > 0.0 else 0
+    w = fc1.weight if fc1.weight.dtype == x.dtype else fc1.weight.to(x.dtype)
+    return _LinearActDropFn.apply(x, w, fc1.bias, link, ACTS[act], pe, int(seed))
 
 
 # ------------------------------------------------------------------------------------------------ joint-encoder input assembly

@@ -9,7 +9,7 @@
 #include <stdio.h>
 #include <vector>
 
-#define VLPET_VERSION 681      // 681: vlpet_hyper_gen_fwd, vlpet_hyper_gen_bwd, vlpet_hyper_gen_workspace_bytes (hyper.hip: Hyperformer's weight generator of one stack, S linear maps on the same E embedding rows, and its backward); 680: vlpet_prefix_concat_dropout_fwd, vlpet_prefix_concat_dropout_bwd, vlpet_prefix_concat_chunks, vlpet_prefix_concat_ws_bytes (prefix_cat.hip: the joint encoder's input assembly with a broadcast prompt in front, prompt tuning); 670: vlpet_phm_expand_pair_fwd, vlpet_phm_expand_pair_bwd, vlpet_phm_workspace_bytes (phm.hip: Compacter's PHM weight expansion of one adapter and its backward); 660: vlpet_adapter_tail_fwd, vlpet_adapter_tail_applies, vlpet_adapter_tail_rows (adapter_tail.hip: sequential adapter + residual + norm in one launch, inference form); 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
+#define VLPET_VERSION 690      // 690: vlpet_colsum_seg, vlpet_colsum_seg_workspace_bytes, vlpet_act_dropout_bwd_cols (biasgrad.hip: segmented column sums of a strided matrix and the FFN activation backward that leaves the column partials of its result -- the bias gradients of the BitFit runs); 681: vlpet_hyper_gen_fwd, vlpet_hyper_gen_bwd, vlpet_hyper_gen_workspace_bytes (hyper.hip: Hyperformer's weight generator of one stack, S linear maps on the same E embedding rows, and its backward); 680: vlpet_prefix_concat_dropout_fwd, vlpet_prefix_concat_dropout_bwd, vlpet_prefix_concat_chunks, vlpet_prefix_concat_ws_bytes (prefix_cat.hip: the joint encoder's input assembly with a broadcast prompt in front, prompt tuning); 670: vlpet_phm_expand_pair_fwd, vlpet_phm_expand_pair_bwd, vlpet_phm_workspace_bytes (phm.hip: Compacter's PHM weight expansion of one adapter and its backward); 660: vlpet_adapter_tail_fwd, vlpet_adapter_tail_applies, vlpet_adapter_tail_rows (adapter_tail.hip: sequential adapter + residual + norm in one launch, inference form); 651: vlpet_attn_long_fwd_train, vlpet_attn_long_bwd (attn_long.hip with dropout, attn_long_bwd.hip: the training form of the attention up to 1,024 keys / queries); 650: vlpet_attn_long_fwd (attn_long.hip: attention forward up to 1,024 keys / queries, no dropout); 640: vlpet_attn_decode_at, vlpet_greedy_pick_at, vlpet_beam_rows_at, vlpet_beam_advance_at (decode.hip: the step position read from device memory, for a replayed decode step); 630: vlpet_attn_decode_beam, vlpet_beam_rows, vlpet_beam_advance (decode.hip: beam search); 620: vlpet_attn_decode, vlpet_greedy_pick (decode.hip: cached greedy generation); 610: vlpet_set_in_launch_reduce and vlpet_finalize_defer / _pending / _discard / _flush removed (the in-launch reduce is chosen per call: phases bit 5); 600 (round 6): in-launch reduce-scatter of the K1 backward (cols_reduce.h; vlpet_adapter_gate_bwd_finalize_launch, phases bit 5), K4 give-up repair inside the call (vlpet_visproj_gemm_exchange_bytes; larger workspace), vlpet_test_hold_cus; 500 (round 5): vlpet_visproj_fwd_gemm (K4 as a tiled GEMM + exchanged statistics), vlpet_sublayer_tail_rms_fwd / vlpet_rmsnorm_tail_bwd, vlpet_adapter_gate_bwd_saved_y (backward from the forward's output), vlpet_finalize_defer / _flush; 420: vlpet_lora_delta_fwd_r8 (K3 at rank <= 8 as a streaming kernel, lora8.hip); 410: vlpet_set_seed_counter (dropout seeds under graph replay), two-pass K2 / K3 forward; 400: two-pass K1 forward (pet_fwd2p.hip), vlpet_sublayer_tail_bwd_out;
 #define VLPET_VERSION_R3 300      // 300: column-parallel K1 backward pass (pet_cols.hip), phases bits 3 / 4, vlpet_adapter_gate_bwd_form;
 #define VLPET_VERSION_R2 221      // 221: vlpet_sublayer_tail_reduce, vlpet_layernorm_bwd_xhat, vlpet_rmsnorm_{fwd,bwd}, vlpet_colsum;  round 2: LoRA dropout generator ABI, sliced AdamW, K3 training form; 210: strided attention entry points, streaming weight gradients; 220: low-rank visual projector
 
@@ -1622,6 +1622,50 @@ extern "C" int vlpet_act_dropout_bwd(const void* dy, const void* x, void* dx, in
     a.x = x; a.dy = dy; a.out = dx; a.keep_out = nullptr; a.n = n; a.act = act; a.thr = tail_thr(p);
     a.keep_scale = a.thr ? 1.0f / (1.0f - p) : 1.0f; a.seed = seed; a.seed_ctr = g_seed_ctr.load();
     return herr(launch_act_dropout(a, true, io_dtype == VLPET_F32, (hipStream_t)stream));
+}
+
+// ---- bias gradients where the data already is (biasgrad.hip) ---------------------------------------------------------------
+extern "C" size_t vlpet_colsum_seg_workspace_bytes(int64_t M, int n) {
+    if (M <= 0 || n <= 0) return 0;
+    return colsum_seg_ws_floats(M, n) * sizeof(float);
+}
+extern "C" int vlpet_colsum_seg(const void* x, int64_t M, int n_segments, int w, int64_t ld, float* const* out, float* workspace,
+                                size_t workspace_bytes, int io_dtype, vlpet_stream_t stream) {
+    if (M <= 0 || n_segments <= 0 || n_segments > VLPET_COLSUM_SEGS || w <= 0 || w % 16 != 0 || w > 65536) return VLPET_E_SHAPE;
+    const int n = n_segments * w;
+    if (n > 65536 || ld < n) return VLPET_E_SHAPE;
+    if (!dtype_ok(io_dtype)) return VLPET_E_DTYPE;
+    if (ld % (io_dtype == VLPET_F32 ? 4 : 8) != 0) return VLPET_E_ALIGN;      // every row starts on a 16-byte boundary
+    if (!x || !out || !workspace) return VLPET_E_NULL;
+    if (!aligned16(x) || !aligned16(workspace)) return VLPET_E_ALIGN;
+    if (workspace_bytes < vlpet_colsum_seg_workspace_bytes(M, n)) return VLPET_E_WORKSPACE;
+    SegOut so{};
+    bool any = false;
+    for (int s = 0; s < n_segments; ++s) {
+        so.p[s] = out[s];
+        any = any || out[s] != nullptr;
+        if (reinterpret_cast<uintptr_t>(out[s]) & 3) return VLPET_E_ALIGN;
+    }
+    if (!any) return 0;                     // no segment wanted: nothing to launch
+    return herr(launch_colsum_seg(x, M, n, ld, w, so, workspace, io_dtype == VLPET_F32, (hipStream_t)stream));
+}
+
+extern "C" int vlpet_act_dropout_bwd_cols(const void* dy, const void* x, void* dx, int64_t M, int n_cols, int act, float p, uint64_t seed,
+                                          float* workspace, size_t workspace_bytes, float* out, int* n_partials, int io_dtype,
+                                          vlpet_stream_t stream) {
+    if (M <= 0 || n_cols <= 0 || n_cols % 8 != 0) return VLPET_E_SHAPE;
+    if (int rc = act_common(M * (int64_t)n_cols, act, p, io_dtype)) return rc;
+    if (!dy || !x || !dx || !workspace || (!out && !n_partials)) return VLPET_E_NULL;
+    if (!aligned16(dy) || !aligned16(x) || !aligned16(dx) || !aligned16(workspace)) return VLPET_E_ALIGN;
+    const int nb = act_cols_partials(M, n_cols);
+    if (workspace_bytes < (size_t)nb * (size_t)n_cols * sizeof(float)) return VLPET_E_WORKSPACE;
+    ActColsArgs a{};
+    a.x = x; a.dy = dy; a.dx = dx; a.part = workspace; a.M = M; a.n_cols = n_cols; a.act = act; a.thr = tail_thr(p);
+    a.keep_scale = a.thr ? 1.0f / (1.0f - p) : 1.0f; a.seed = seed; a.seed_ctr = g_seed_ctr.load();
+    if (int rc = herr(launch_act_dropout_bwd_cols(a, io_dtype == VLPET_F32, (hipStream_t)stream))) return rc;
+    if (n_partials) *n_partials = nb;
+    if (!out) return 0;                     // the caller reduces (vlpet_sublayer_tail_reduce / vlpet_reduce_batch with d = n_cols / 2)
+    return herr(launch_tail_reduce(workspace, nb, n_cols / 2, out, out + n_cols / 2, (hipStream_t)stream));
 }
 
 // ---- Downsample ---------------------------------------------------------------------------------------------

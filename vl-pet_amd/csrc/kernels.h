@@ -410,6 +410,22 @@ struct ActDropArgs {
     const uint64_t* seed_ctr;   // optional device step counter mixed into the seed (rng.h vlpet_eff_seed)
 };
 hipError_t launch_act_dropout(const ActDropArgs& a, bool bwd, int io_fp32, hipStream_t stream);
+// Bias gradients where the data already is (biasgrad.hip).  Segmented column sums of a strided matrix: x [M, n], row stride ld, n = S w;
+// segment s -> out.p[s] [w] (nullptr: not wanted); part = colsum_seg_ws_floats(M, n) floats.
+#define VLPET_COLSUM_SEGS 16
+struct SegOut { float* p[VLPET_COLSUM_SEGS]; };
+size_t colsum_seg_ws_floats(int64_t M, int n);
+hipError_t launch_colsum_seg(const void* x, int64_t M, int n, int64_t ld, int w, const SegOut& out, float* part, int io_fp32,
+                             hipStream_t stream);
+// ... and the FFN activation backward over [M, n_cols] that leaves the column partials of the dx it stores: part [act_cols_partials(M, n_cols)][n_cols]
+struct ActColsArgs {
+    const void* x; const void* dy; void* dx;      // [M, n_cols]
+    float* part;
+    int64_t M; int n_cols; int act;
+    uint32_t thr; float keep_scale; uint64_t seed; const uint64_t* seed_ctr;      // as ActDropArgs
+};
+int act_cols_partials(int64_t M, int n_cols);
+hipError_t launch_act_dropout_bwd_cols(const ActColsArgs& a, int io_fp32, hipStream_t stream);
 // x = dropout(cat([a, v], dim = 1), p) over [B, La | Lv, d] (actdrop.hip); bwd: x = dx in, a / v = da / dv out (nullptr: not wanted)
 hipError_t launch_cat_dropout(const void* a, const void* v, void* x, int64_t B, int La, int Lv, int d, uint32_t thr, float keep_scale,
                               uint64_t seed, const uint64_t* seed_ctr, bool bwd, int io_fp32, hipStream_t stream);

@@ -450,16 +450,17 @@ class _CrossKeyProjFn(torch.autograd.Function):
     into the blocks of one gradient buffer (attention.KeyGradSlot) and ONE GEMM with K = n * E produces d/dx."""
 
     @staticmethod
-    def forward(ctx, x, w_all, b_all, n, slot):
+    def forward(ctx, x, w_all, b_all, n, slot, *biases):
+        # ``biases``: the layers' k_proj.bias parameters where any of them trains (BitFit), else nothing; b_all is their current fused copy
         y = F.linear(x, w_all, b_all)
         E = w_all.shape[0] // n
-        ctx.save_for_backward(w_all)
+        ctx.save_for_backward(w_all, *biases)
         ctx.slot, ctx.n, ctx.xshape = slot, n, x.shape
         return tuple(y[..., i * E:(i + 1) * E] for i in range(n))
 
     @staticmethod
     def backward(ctx, *dks):
-        (w_all,) = ctx.saved_tensors
+        w_all, *biases = ctx.saved_tensors
         n, slot = ctx.n, ctx.slot
         ctx.slot = None
         E = w_all.shape[0] // n
@@ -469,24 +470,37 @@ class _CrossKeyProjFn(torch.autograd.Function):
         whole = buf is not None and all(
             dk is not None and dk.data_ptr() == buf.data_ptr() + i * E * buf.element_size() and dk.shape[:-1] == buf.shape[:-1]
             and dk.stride() == buf.stride() for i, dk in enumerate(dks))
+        bslots = [grad_slot(b, (E,)) if (ctx.needs_input_grad[5 + i] and dks[i] is not None) else None for i, b in enumerate(biases)]
         if whole:
             dx = buf.view(-1, n * E) @ w_all
+            if any(sl is not None for sl in bslots):        # every layer's k_proj.bias gradient: ONE segmented sum over the shared dk buffer
+                full = buf.view(-1, n * E)                  # (more layers than one call takes segments: 16 at a time)
+                for s0 in range(0, n, MAX_COLSUM_SEGS):
+                    part = bslots[s0:s0 + MAX_COLSUM_SEGS]
+                    if any(sl is not None for sl in part):
+                        colsum_seg_into(full[:, s0 * E:(s0 + len(part)) * E], part, E)
         else:                       # (a consumer that went another way: per-block products)
             dx = None
             for i, dk in enumerate(dks):
                 if dk is None:
                     continue
-                t = dk.reshape(-1, E).to(w_all.dtype) @ w_all[i * E:(i + 1) * E]
+                d2 = dk.reshape(-1, E).to(w_all.dtype)
+                t = d2 @ w_all[i * E:(i + 1) * E]
                 dx = t if dx is None else dx.add_(t)
-        return (None if dx is None else dx.view(ctx.xshape)), None, None, None, None
+                if biases and bslots[i] is not None:
+                    BITFIT_CALLS["fallback"] += 1
+                    colsum_seg_into(d2, [bslots[i]], E)
+        return ((None if dx is None else dx.view(ctx.xshape)), None, None, None, None) + tuple(None if sl is None else sl.finish() for sl in bslots)
 
 
-def cross_key_blocks(x: torch.Tensor, w_all: torch.Tensor, b_all: torch.Tensor, n: int):
+def cross_key_blocks(x: torch.Tensor, w_all: torch.Tensor, b_all: torch.Tensor, n: int, biases=()):
     """(k_0 .. k_{n-1}, slot): the n key projections of ``x`` as column blocks of one GEMM's output and the KeyGradSlot their attention
-    calls pass on (``short_attention(..., k_slot=(slot, i))``)."""
+    calls pass on (``short_attention(..., k_slot=(slot, i))``).  ``biases``: the n bias parameters when any of them trains (BitFit) --
+    their gradients are one segmented column sum over the shared dk buffer."""
     from .attention import KeyGradSlot
-    slot = KeyGradSlot(n, w_all.shape[0] // n) if (x.requires_grad and torch.is_grad_enabled()) else None
-    return _CrossKeyProjFn.apply(x, w_all, b_all, n, slot), slot
+    biases = tuple(biases) if (torch.is_grad_enabled() and any(b is not None and b.requires_grad for b in biases)) else ()
+    slot = KeyGradSlot(n, w_all.shape[0] // n) if ((x.requires_grad or biases) and torch.is_grad_enabled()) else None
+    return _CrossKeyProjFn.apply(x, w_all, b_all, n, slot, *biases), slot
 
 
 class ResidualLink:
@@ -667,6 +681,140 @@ def linear_acc(x: torch.Tensor, link: Optional[ResidualLink], *mods):
         ws.append(w if w.dtype == x.dtype else w.to(x.dtype))
         bs.append(b if b is None or b.dtype == x.dtype else b.to(x.dtype))
     return _LinearAccFn.apply(x, link, *ws, *bs)
+
+
+# ---- BitFit: bias gradients produced where the data already is (csrc/biasgrad.hip) ------------------------------------------------
+# A/B switch (tools/ab_switches.py: VLPET_NO_BIAS_GRAD_SITES=1): False = a model with trainable biases next to frozen projections takes
+# the separate-projection path with one vlpet_colsum pair per bias (linear_train_bias), as a hand-unfrozen model did before these sites.
+FUSE_BIAS_GRAD_SITES = True
+# launches issued (tests assert on them; a replayed graph does not count): segmented column sums, fused activation backwards, and
+# calls that wanted a site but had to take linear_train_bias / act_dropout instead
+BITFIT_CALLS = {"seg": 0, "act": 0, "fallback": 0}
+MAX_COLSUM_SEGS = 16       # segments of one vlpet_colsum_seg call (include/vlpet_hip.h)
+
+
+def colsum_seg_into(dy2: torch.Tensor, slots, w: int):
+    """Column sums of ``dy2 [M, len(slots) * w]`` (any row stride), segment s into ``slots[s].t`` (a GradSlot, or None: not wanted):
+    one vlpet_colsum_seg call.  Not deferred (DEFER_REDUCES is bypassed: the call's second launch writes every wanted slot at once,
+    there is no per-parameter reduction left to batch)."""
+    import ctypes
+    lib = _lib.load()
+    S, (M, n) = len(slots), dy2.shape
+    if dy2.stride(1) != 1:
+        dy2 = dy2.contiguous()
+    nbytes = lib.vlpet_colsum_seg_workspace_bytes(M, n)
+    ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dy2.device)
+    ptrs = (ctypes.c_void_p * S)(*[None if sl is None else sl.ptr for sl in slots])
+    rc = _timed("colsum_seg", M, lambda: lib.vlpet_colsum_seg(dy2.data_ptr(), M, S, w, dy2.stride(0), ptrs, ws.data_ptr(), nbytes,
+                                                              _io_dtype(dy2), _stream()))
+    _lib.check(rc, "vlpet_colsum_seg")
+    BITFIT_CALLS["seg"] += 1
+
+
+class _LinearAccBiasFn(torch.autograd.Function):
+    """_LinearAccFn for ONE fused GEMM of n projections (``w_all [n E, in]``, frozen) whose biases may train: ``biases`` are the n
+    modules' bias parameters, ``b_all`` their concatenation in the activation dtype.  The input gradient accumulates onto the parked one
+    exactly as in _LinearAccFn; the gradients of the trainable biases are one segmented column sum of the fused dy, each segment
+    straight into its bias's slot (GradSlot.finish as in _LinearTrainBiasFn); a frozen bias is a NULL segment."""
+
+    @staticmethod
+    def forward(ctx, x, link, w_all, b_all, *biases):
+        ctx.link = link.arm() if (link is not None and ctx.needs_input_grad[0]) else None
+        ctx.save_for_backward(w_all, *biases)
+        ctx.xshape = x.shape
+        return F.linear(x, w_all, b_all)
+
+    @staticmethod
+    def backward(ctx, dy):
+        w_all, *biases = ctx.saved_tensors
+        link, ctx.link = ctx.link, None
+        n = dy.shape[-1]
+        dy2 = _flat(dy, n)
+        if dy2.dtype != w_all.dtype:
+            dy2 = dy2.to(w_all.dtype)
+        dx = None
+        if ctx.needs_input_grad[0]:
+            acc = link.take(ctx.xshape, w_all.dtype, writable=True) if link is not None else None
+            dx = (dy2 @ w_all if acc is None else acc.view(-1, ctx.xshape[-1]).addmm_(dy2, w_all)).view(ctx.xshape)
+        w = n // len(biases)
+        slots = [grad_slot(b, (w,)) if ctx.needs_input_grad[4 + i] else None for i, b in enumerate(biases)]
+        if any(sl is not None for sl in slots):
+            colsum_seg_into(dy2, slots, w)
+        return (dx, None, None, None) + tuple(None if sl is None else sl.finish() for sl in slots)
+
+
+class _LinearAccSepBiasFn(torch.autograd.Function):
+    """_LinearAccFn (n SEPARATE GEMMs of one input, one input gradient on top of the parked one) whose biases may train: the consumers
+    hand back n separate dy tensors, so each trainable bias gets the segmented sum of its own dy (one segment)."""
+
+    @staticmethod
+    def forward(ctx, x, link, n, *args):
+        ws, bios, biases = args[:n], args[n:2 * n], args[2 * n:]
+        ctx.link = link.arm() if (link is not None and ctx.needs_input_grad[0]) else None
+        ctx.save_for_backward(*ws, *biases)
+        ctx.xshape, ctx.n = x.shape, n
+        outs = tuple(F.linear(x, w, b) for w, b in zip(ws, bios))
+        return outs if n > 1 else outs[0]
+
+    @staticmethod
+    def backward(ctx, *dys):
+        n = ctx.n
+        ws, biases = ctx.saved_tensors[:n], ctx.saved_tensors[n:]
+        link, ctx.link = ctx.link, None
+        acc = link.take(ctx.xshape, ws[0].dtype, writable=True) if (link is not None and ctx.needs_input_grad[0]) else None
+        if acc is not None:
+            acc = acc.view(-1, ctx.xshape[-1])
+        dbs = []
+        for i, (dy, w, b) in enumerate(zip(dys, ws, biases)):
+            if dy is None:
+                dbs.append(None)
+                continue
+            dy2 = _flat(dy, dy.shape[-1])
+            if dy2.dtype != w.dtype:
+                dy2 = dy2.to(w.dtype)
+            if ctx.needs_input_grad[0]:
+                if acc is None:
+                    acc = dy2 @ w
+                else:
+                    acc.addmm_(dy2, w)
+            if ctx.needs_input_grad[3 + 2 * n + i]:
+                sl = grad_slot(b, (dy2.shape[1],))
+                colsum_seg_into(dy2, [sl], dy2.shape[1])
+                dbs.append(sl.finish())
+            else:
+                dbs.append(None)
+        dx = acc.view(ctx.xshape) if acc is not None else None
+        return (dx, None, None) + (None,) * (2 * n) + tuple(dbs)
+
+
+def linear_acc_sep_bias_ok(x: torch.Tensor, *mods) -> bool:
+    return (FUSE_BIAS_GRAD_SITES and x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and x.numel() > 0 and torch.is_grad_enabled()
+            and all(m.bias is not None and not m.weight.requires_grad and m.weight.shape[0] % 16 == 0 and m.weight.shape[0] <= 65536
+                    for m in mods) and any(m.bias.requires_grad for m in mods))
+
+
+def linear_acc_sep_bias(x: torch.Tensor, link: Optional[ResidualLink], *mods):
+    """linear_acc for ``nn.Linear`` modules with frozen weights and any subset of trainable biases (BitFit's cross-attention k | v)."""
+    ws = [m.weight if m.weight.dtype == x.dtype else m.weight.to(x.dtype) for m in mods]
+    bios = [io_view(m.bias, x.dtype).detach() for m in mods]
+    return _LinearAccSepBiasFn.apply(x, link, len(mods), *ws, *bios, *[m.bias for m in mods])
+
+
+def linear_acc_bias_ok(x: torch.Tensor, w_all: torch.Tensor, biases) -> bool:
+    """Whether linear_acc_bias applies: the switch, CUDA bf16 / fp32 activations, the fused weight frozen and in that dtype, at most 16
+    segments of a width that is a multiple of 16, at least one trainable bias."""
+    n = len(biases)
+    return (FUSE_BIAS_GRAD_SITES and x.is_cuda and x.dtype in (torch.bfloat16, torch.float32) and w_all.dtype == x.dtype
+            and not w_all.requires_grad and 1 <= n <= 16 and w_all.shape[0] % n == 0 and (w_all.shape[0] // n) % 16 == 0
+            and w_all.shape[0] <= 65536 and all(b is not None for b in biases) and any(b.requires_grad for b in biases)
+            and x.numel() > 0 and torch.is_grad_enabled())
+
+
+def linear_acc_bias(x: torch.Tensor, link: Optional[ResidualLink], w_all: torch.Tensor, b_all: torch.Tensor, biases) -> torch.Tensor:
+    """``x w_all^T + b_all`` as ONE GEMM (the fused output; the caller slices its column blocks).  ``b_all``: the concatenation of
+    ``biases`` in the activation dtype, CURRENT -- host.common.derived_weights keys it on WEIGHTS_EPOCH while a bias trains, so it is
+    rebuilt after every optimizer step and, inside a captured step, by a node of the graph."""
+    return _LinearAccBiasFn.apply(x, link, w_all, b_all, *biases)
 
 
 def _saved_block(ctx, nbytes, device):

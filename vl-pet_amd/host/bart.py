@@ -68,7 +68,7 @@ def vlpet_config(**over) -> SimpleNamespace:
         use_encoder_gating_scaling=False, encoder_gating_scaling_factor=1.0,
         use_encoder_adapter_scaling=False, encoder_adapter_scaling_factor=1.0,
         use_encoder_x2_scaling=False, encoder_x2_scaling_factor=1.0,
-        unfreeze_encoder_layer_norms=True, unfreeze_layer_norms=False,
+        unfreeze_encoder_layer_norms=True, unfreeze_layer_norms=False, unfreeze_bias=False,
         use_decoder_enc_attn_value_parallel_adapter_down_dim=True, decoder_enc_attn_value_parallel_adapter_down_dim=96,
         use_decoder_enc_attn_value_parallel_adapter_scaling=False,
         decoder_enc_attn_value_parallel_adapter_scaling_factor=1.0,
@@ -195,6 +195,21 @@ def _tail_linked(residual, h, norm, p, training, link):
     return sublayer_tail(residual, h, norm, p, training, link=link)
 
 
+def _ffn_in(fc1, x, link, act, p, training, sites=True):
+    """``ffn_activation(fc1(x))`` of a feed-forward sublayer.  BitFit (frozen weight, trainable bias): one autograd pair whose backward
+    sums the bias gradient inside the activation backward (act.linear_act_dropout); else _first_linear + ffn_activation.  ``sites``:
+    False keeps a flag set on the path it always took (the LoRA runs, which also train every bias)."""
+    # (a harness that swapped ``ffn_activation`` for its own restatement keeps it: the site replaces the HIP pass only)
+    if (sites and not EAGER_FFN_ACT and ffn_activation is _HIP_FFN_ACTIVATION and isinstance(fc1, nn.Linear) and fc1.bias is not None
+            and fc1.bias.requires_grad and not fc1.weight.requires_grad and torch.is_grad_enabled() and VF.FUSE_BIAS_GRAD_SITES
+            and x.is_cuda and x.dtype in (torch.bfloat16, torch.float32)):
+        from ..act import linear_act_dropout, linear_act_dropout_ok
+        if linear_act_dropout_ok(x, fc1, act):
+            return linear_act_dropout(x, fc1, act, p, training, link)
+        VF.BITFIT_CALLS["fallback"] += 1            # eligible by device and dtype, refused by shape
+    return ffn_activation(_first_linear(fc1, x, link), act, p, training)
+
+
 def ffn_activation(x, act, p, training):
     """``dropout(act(fc1 output), p)`` of the feed-forward sublayer: one fused HIP pass (vlpet_amd.act); the parity /
     CPU-baseline harnesses swap this module attribute for the eager pair."""
@@ -205,6 +220,7 @@ def ffn_activation(x, act, p, training):
 
 
 EAGER_FFN_ACT = False     # A/B switch (tools/ab_switches.py): the two elementwise torch passes instead
+_HIP_FFN_ACTIVATION = ffn_activation
 
 
 def lm_loss(h, weight, labels, bias=None):
@@ -327,18 +343,32 @@ class BartAttention(nn.Module):
         if kv is None and FUSE_QKV and not self.use_lora and not EAGER_ATTENTION:
             # self-attention with frozen projections: one [E -> 3E] GEMM each way, the attention kernels read / write the
             # q | k | v column blocks in place (one input gradient instead of three that autograd would have to sum)
-            frozen = not any(t.requires_grad for m in (self.q_proj, self.k_proj, self.v_proj) for t in (m.weight, m.bias))
-            kind = _route(L, L, self.dropout, self.training, hidden, grad=in_link is not None)
-            if (frozen and (attn_mask is None or is_key_mask(attn_mask)) and hidden.is_cuda and hidden.dtype == torch.bfloat16
+            qkv_mods = (self.q_proj, self.k_proj, self.v_proj)
+            frozen = not any(t.requires_grad for m in qkv_mods for t in (m.weight, m.bias))
+            # BitFit: frozen weights, any subset of the three biases trainable -- the same fused GEMM, the bias gradients as one segmented
+            # column sum of the fused dy (functional.linear_acc_bias)
+            only_biases = not frozen and not any(m.weight.requires_grad for m in qkv_mods) and VF.FUSE_BIAS_GRAD_SITES
+            bias_sites = only_biases and torch.is_grad_enabled()
+            if only_biases and not bias_sites:      # evaluation of such a model (no_grad): nothing trains here, the fused bias is current
+                frozen = True                       # (host.common.derived_weights keys it on the optimizer's epoch)
+            kind = _route(L, L, self.dropout, self.training, hidden, grad=in_link is not None or bias_sites)
+            if ((frozen or bias_sites) and (attn_mask is None or is_key_mask(attn_mask)) and hidden.is_cuda and hidden.dtype == torch.bfloat16
                     and kind is not None and self.head_dim == A.HEAD_DIM):
                 w, b = self._fused_qkv(hidden.dtype)
-                if in_link is not None:
+                biases = tuple(m.bias for m in qkv_mods)
+                if bias_sites and VF.linear_acc_bias_ok(hidden, w, biases):
+                    qkv = VF.linear_acc_bias(hidden, in_link, w, b, biases)     # (``b`` is keyed on the optimizer's epoch: derived_weights)
+                elif bias_sites:
+                    VF.BITFIT_CALLS["fallback"] += 1
+                    qkv = None
+                elif in_link is not None:
                     qkv = VF.linear_acc(hidden, in_link, (w, b))
                 else:
                     qkv = F.linear(hidden, w, b)
-                km = None if attn_mask is None else attn_mask[:, 0, 0, :]
-                out = A.attend_qkv(kind, qkv, self.num_heads, km, causal and attn_mask is None, self.dropout, self.training)
-                return _linear(self.out_proj, out)
+                if qkv is not None:
+                    km = None if attn_mask is None else attn_mask[:, 0, 0, :]
+                    out = A.attend_qkv(kind, qkv, self.num_heads, km, causal and attn_mask is None, self.dropout, self.training)
+                    return _linear(self.out_proj, out)
         if self.use_lora:
             q = self.q_proj(hidden, task)
             v = self.v_proj(src, task)
@@ -346,13 +376,17 @@ class BartAttention(nn.Module):
         else:
             # (self-attention off the fused path: hidden feeds three projections -- only q_proj takes the sublayer's link)
             q = _first_linear(self.q_proj, hidden, in_link)
-            kv_link = _new_gemm_link(src) if (kv is not None and _frozen(self.k_proj, self.v_proj)) else None
+            kv_frozen = kv is not None and _frozen(self.k_proj, self.v_proj)
+            # BitFit: frozen weights, trainable biases -- the same single input gradient, each bias summed from its own dy
+            kv_bias = kv is not None and not kv_frozen and VF.linear_acc_sep_bias_ok(src, self.k_proj, self.v_proj)
+            kv_link = _new_gemm_link(src) if (kv_frozen or kv_bias) else None
             if kv_link is not None:
+                acc = VF.linear_acc_sep_bias if kv_bias else VF.linear_acc
                 k_slot = None
                 if k_pre is not None:
-                    (k, k_slot), v = k_pre, VF.linear_acc(src, kv_link, self.v_proj)
+                    (k, k_slot), v = k_pre, acc(src, kv_link, self.v_proj)
                 else:
-                    k, v = VF.linear_acc(src, kv_link, self.k_proj, self.v_proj)      # one gradient for the encoder output, K2's included
+                    k, v = acc(src, kv_link, self.k_proj, self.v_proj)      # one gradient for the encoder output, K2's included
                 if self.attn_value_parallel_adapter is not None:
                     v = self.attn_value_parallel_adapter(src, task, y=v, link=kv_link)
                 out = attention_core(q, k, v, self.num_heads, attn_mask, causal, self.dropout, self.training, k_slot=k_slot)
@@ -442,7 +476,7 @@ class BartEncoderLayer(nn.Module):
             hidden = _tail_linked(residual, h, self.self_attn_layer_norm, self.dropout, self.training, gl)   # K5
         residual = hidden
         gl = _new_gemm_link(hidden)
-        h = ffn_activation(_first_linear(self.fc1, hidden, gl), "gelu", self.activation_dropout, self.training)
+        h = _ffn_in(self.fc1, hidden, gl, "gelu", self.activation_dropout, self.training, sites=not self.config.use_lora)
         h = _linear(self.fc2, h)
         if self.adapter_hypernet is not None:
             return _generated_then_tail(self.adapter_hypernet, block_adapters["feed_forward"], residual, h, self.final_layer_norm,
@@ -507,7 +541,7 @@ class BartDecoderLayer(nn.Module):
         hidden = self._tail(self.enc_attn_adapter, task, residual, h, self.encoder_attn_layer_norm, gl, wx)
         residual = hidden
         gl = _new_gemm_link(hidden)
-        h = ffn_activation(_first_linear(self.fc1, hidden, gl), "gelu", self.activation_dropout, self.training)
+        h = _ffn_in(self.fc1, hidden, gl, "gelu", self.activation_dropout, self.training, sites=not self.config.use_lora)
         h = _linear(self.fc2, h)
         return self._tail(self.ff_adapter, task, residual, h, self.final_layer_norm, gl, wf)
 
@@ -664,11 +698,14 @@ class BartDecoder(nn.Module):
             return False
         if enc_mask is not None and not is_key_mask(enc_mask):
             return False
-        return all((not l.encoder_attn.use_lora) and _frozen(l.encoder_attn.k_proj, l.encoder_attn.v_proj) for l in self.layers)
+        def ok(a):          # frozen plain projections -- or (BitFit) frozen weights with trainable biases, whose gradients the fused form sums
+            return not a.use_lora and (_frozen(a.k_proj, a.v_proj) or VF.linear_acc_sep_bias_ok(enc, a.k_proj, a.v_proj))
+        return all(ok(l.encoder_attn) for l in self.layers)
 
     def _cross_keys(self, enc):
-        w, b = derived_weights(self, "_ck_cache", [l.encoder_attn.k_proj for l in self.layers], enc.dtype)
-        return VF.cross_key_blocks(enc, w, b, len(self.layers))
+        mods = [l.encoder_attn.k_proj for l in self.layers]
+        w, b = derived_weights(self, "_ck_cache", mods, enc.dtype)
+        return VF.cross_key_blocks(enc, w, b, len(mods), [m.bias for m in mods])
 
 
     def init_cache(self, enc, key_mask, task, max_length, num_beams=1):

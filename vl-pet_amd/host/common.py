@@ -16,17 +16,24 @@ def derived_weights(owner, slot, mods, dtype):
     """``(cat of the modules' weights [sum out, in], cat of their biases or None)`` in ``dtype``: the fused q | k | v projection of a
     self-attention, the fused cross-attention key projection of a decoder.  A derived cache kept as the plain attribute ``slot`` of
     ``owner`` -- never a parameter or buffer: the state dict keeps the separate modules -- and rebuilt when one of the tensors
-    changes (data pointer, version), after a cast of the frozen weights or a checkpoint load (functional.FROZEN_EPOCH)."""
-    key = tuple((m.weight.data_ptr(), m.weight._version) if m.bias is None else
-                (m.weight.data_ptr(), m.weight._version, m.bias.data_ptr(), m.bias._version) for m in mods) + (dtype, VF.FROZEN_EPOCH)
+    changes (data pointer, version), after a cast of the frozen weights or a checkpoint load (functional.FROZEN_EPOCH).  The two halves
+    are keyed apart, and a half with a TRAINABLE tensor in it (BitFit: the biases) also carries the optimizer's epoch
+    (functional.WEIGHTS_EPOCH): the fused flat-buffer AdamW writes through raw pointers and bumps no version counter, so without it the
+    fused bias would be as old as the cache."""
+    def key_of(ts):
+        k = tuple((t.data_ptr(), t._version) for t in ts) + (dtype, VF.FROZEN_EPOCH)
+        return k + (VF.WEIGHTS_EPOCH,) if any(t.requires_grad for t in ts) else k
+    ws = [m.weight for m in mods]
+    bs = [] if mods[0].bias is None else [m.bias for m in mods]
+    wkey, bkey = key_of(ws), key_of(bs)
     c = getattr(owner, slot, None)
-    if c is None or c[0] != key:
+    if c is None or c[0] != wkey or c[2] != bkey:
         with torch.no_grad():
-            w = torch.cat([m.weight.to(dtype) for m in mods], 0).contiguous()
-            b = None if mods[0].bias is None else torch.cat([m.bias.to(dtype) for m in mods], 0).contiguous()
-        c = (key, w, b)
+            w = c[1] if (c is not None and c[0] == wkey) else torch.cat([t.to(dtype) for t in ws], 0).contiguous()
+            b = None if not bs else (c[3] if (c is not None and c[2] == bkey) else torch.cat([VF.io_view(t, dtype) for t in bs], 0).contiguous())      # (io_view: a trainable bias comes from the trainer's IO shadow when that is current -- no cast launch)
+        c = (wkey, w, bkey, b)
         setattr(owner, slot, c)
-    return c[1], c[2]
+    return c[1], c[3]
 
 
 def value_parallel_adapter(config) -> AdapterController:

@@ -177,7 +177,7 @@ def vlt5_config(**over) -> SimpleNamespace:
         use_encoder_gating_scaling=True, encoder_gating_scaling_factor=0.3,
         use_encoder_adapter_scaling=False, encoder_adapter_scaling_factor=1.0,
         use_encoder_x2_scaling=False, encoder_x2_scaling_factor=1.0,
-        unfreeze_encoder_layer_norms=True, unfreeze_layer_norms=False,
+        unfreeze_encoder_layer_norms=True, unfreeze_layer_norms=False, unfreeze_bias=False,
         use_decoder_enc_attn_value_parallel_adapter_down_dim=True, decoder_enc_attn_value_parallel_adapter_down_dim=96,
         use_decoder_enc_attn_value_parallel_adapter_scaling=False,
         decoder_enc_attn_value_parallel_adapter_scaling_factor=1.0,

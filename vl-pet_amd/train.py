@@ -83,6 +83,8 @@ def trainable_names(model: nn.Module, config) -> List[str]:
             on = True
         if config.use_lora and ("lora" in n or "bias" in n):
             on = True
+        if getattr(config, "unfreeze_bias", False) and "bias" in n:      # BitFit (trainer_base.py:469-475)
+            on = True
         if config.unfreeze_encoder_layer_norms and "encoder." in n and ("layer_norm" in n or "layernorm" in n):
             on = True
         if any_gate and "gating" in n:
